@@ -1,6 +1,8 @@
 """Benchmark of the PGGAN / WGAN-GP training step on MI355X (contract: see the task brief / DESIGN.md section 5).
 
     python bench.py --gpus N --steps K --warmup W          # starts the N rank processes itself when N > 1
+    python bench.py --gpus 1 --steps K --warmup W --full   # + sub-records, per-kernel roofline, CPU baseline (see below)
+    python bench.py ... --dump-outputs DIR                 # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full iteration of the reference's inner loop (train.py:357-385): D step (W loss + drift + gradient
@@ -11,7 +13,11 @@ The headline `value` is measured in the reference's arithmetic: fp32 storage, fp
 v_mfma_f32_16x16x4_f32 (the reference computes in the default dtype, train.py:136-144), `dtype: "f32"`.  The 16- and 32-channel
 layers on large images run in Winograd F(2x2, 3x3) form -- still fp32 throughout, but 16 products per 2x2 output tile and channel
 pair instead of 36, i.e. NOT the same products as the direct form; every such kernel instance is labelled in `conv_family` with
-the fraction of its algorithmic flops it actually executes on the matrix pipe (`executed_mfma_frac`).  The faster split-bf16
+the fraction of its algorithmic flops it actually executes on the matrix pipe (`executed_mfma_frac`).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the line, with
+`roofline` and `conv_family` null.  Everything else is measured with --full only: the reduced-precision sub-records, the per-kernel
+probe behind `roofline` / `conv_family` (with the live PMC traffic) and `cpu_baseline`.  With --full the faster split-bf16
 convolution mode (3 bf16 MFMAs per fp32 product group, 16-bit-mantissa operands) is timed by the same protocol right afterwards
 and reported as the labelled sub-record `"bf16x3"` of the same JSON line, with the relative error it shows against the fp32 mode
 on identical weights and draws (`max_rel_err`).  It is never the headline.  A second sub-record, `"bf16"`, is BASELINE.json's C2
@@ -25,7 +31,7 @@ legitimately exceed 1.0 (it has, in isolation: 1.03 for 32 -> 32 at 128x128).  I
 how busy the pipe is.  For pipe occupancy read `executed_mfma_frac` (= frac x 4/9), and for the other roof `gbs / 8000`
 (`conv_family.instances[*].hbm_frac`): a Winograd instance is "at its roof" when either of those two is near 1, not when `frac` is.
 
-Rank 0 prints ONE JSON line: images/s over all ranks, plus
+Rank 0 prints ONE JSON line: images/s over all ranks and `ms_per_step` (one timed step), plus, with --full,
   roofline     -- the dominant kernel = the conv template instance (forward / input-gradient / weight-gradient entry points) with the
                   largest summed time, timed with HIP events on its launch stream: exact-fp32 instances against the fp32 MFMA
                   roof (157.3 TFLOP/s: achieved = 2*9*K*N*pixels of its launches / their summed duration), split-bf16 instances
@@ -57,6 +63,8 @@ D_WIDTHS = [16, 16, 32, 32, 64, 128]
 PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md, chip-level parameters
 PEAK_HBM_GBS = 8000.0          # HBM3E spec peak (about 6.3 TB/s is achievable with a float4 copy)
 PROFILE_TAG = "r04"            # profiles/<tag>_traffic_<precision>.json holds the PMC traffic per kernel
+DUMP_MAX_ELEMS = 1 << 20       # --dump-outputs: larger tensors are written as a seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: bound on the whole set
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -192,6 +200,33 @@ def build_nets(pkg, res, alpha, device):
         G.set_resolution(res, alpha)
         D.set_resolution(res, alpha)
     return G.to(device), D.to(device)
+
+
+def step_outputs(trainer, stats, max_elems=DUMP_MAX_ELEMS):
+    """What a caller of the timed step holds after its last step, as float32 host arrays by name: the step's losses and scores, and both
+    nets' parameters after the Adam updates.  A tensor of more than `max_elems` elements (the generator's 16.8 M-element stem at 512x512)
+    contributes a fixed, seeded sample of `max_elems` of its elements, in index order, so that the whole set stays near 8 MB."""
+    import numpy as np
+    import torch
+    out = {k: v.detach().float().cpu().numpy().reshape(-1) for k, v in stats.items()}
+    for tag, flat in (("G", trainer.flat_g), ("D", trainer.flat_d)):
+        for name, p in zip(flat.names, flat.params):
+            v = p.detach().reshape(-1)
+            if v.numel() > max_elems:
+                idx = np.sort(np.random.default_rng(0).choice(v.numel(), max_elems, replace=False))
+                v = v[torch.from_numpy(idx).to(v.device)]
+            out[f"{tag}.{name}"] = v.float().cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"outputs of {total / 2**20:.1f} MiB exceed the {DUMP_MAX_BYTES >> 20} MiB limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_model_name():
@@ -344,13 +379,12 @@ def run_mode(pkg, args, precision, device, world, rank, use_dist):
     # launch mode: HIP-graph replay of the whole iteration on one GPU (captured once); three graphs with the eager gradient
     # exchanges between them when there is a process group
     use_graph = args.graph != 0
-    probe = None if args.no_probe else ConvProbe(pkg._C)
+    probe = ConvProbe(pkg._C) if args.full and not args.no_probe else None
 
     def step(i):
         if use_graph:
-            trainer.replay(pool[i % len(pool)])
-        else:
-            trainer.train_iteration(pool[i % len(pool)])
+            return trainer.replay(pool[i % len(pool)])
+        return trainer.train_iteration(pool[i % len(pool)])
 
     if use_graph:
         try:
@@ -374,10 +408,12 @@ def run_mode(pkg, args, precision, device, world, rank, use_dist):
         trainer.comm_timing = []           # (tag, start event, end event) per gradient exchange, on the communication stream
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        stats = step(i)
     fence()
     elapsed = time.perf_counter() - t0
     pkg._C.set_probe(None)
+    # taken before anything below runs more steps on the same trainer
+    outputs = step_outputs(trainer, stats) if args.dump_outputs and rank == 0 and precision == args.precision else None
     own_elapsed = elapsed
     exchange_ms = None
     if use_dist:
@@ -409,7 +445,7 @@ def run_mode(pkg, args, precision, device, world, rank, use_dist):
         ranks = rank_report([r.tolist() for r in allr])
 
     out = {"elapsed": elapsed, "ranks": ranks, "launch": ("hip-graph replay" + (" (3 segments, eager gradient exchange between)" if use_dist else ""))
-           if use_graph else "eager", "roofline": None, "conv_family": None}
+           if use_graph else "eager", "roofline": None, "conv_family": None, "outputs": outputs}
     if rank == 0 and probe is not None and probe.records:
         summ = probe.summary()
         dom = max(summ, key=lambda k: summ[k]["seconds"])
@@ -549,14 +585,20 @@ def main():
                     help="arithmetic of the headline: exact fp32 MFMA (the reference's arithmetic), split-bf16 (3 bf16 MFMAs per "
                          "product, fp32 storage and accumulate), or bf16 (bf16 activation storage, one bf16 MFMA per product)")
     ap.add_argument("--sub-record", type=int, default=-1, help="1: also time the reduced-precision modes and report them as the labelled "
-                                                               "sub-records 'bf16x3' and 'bf16'; 0: do not; -1: only on one GPU")
+                                                               "sub-records 'bf16x3' and 'bf16'; 0: do not; -1: only with --full on one GPU")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the gradient exchange even with one rank (path test)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="do not time the dominant kernel with HIP events")
-    ap.add_argument("--live-traffic", type=int, default=-1, help="roofline.traffic of the headline's dominant kernel from two rocprofv3 counter "
-                    "passes over a child run, inside this invocation (one GPU only); 0: use the committed summary under profiles/")
+    ap.add_argument("--full", action="store_true", help="measure more than the headline: the sub-records (--sub-record), the dominant kernel "
+                    "and conv family by HIP events (--no-probe) with live PMC traffic (--live-traffic), and the CPU baseline (--no-cpu-baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: do not time the dominant kernel with HIP events")
+    ap.add_argument("--live-traffic", type=int, default=-1, help="with --full: roofline.traffic of the headline's dominant kernel from two "
+                    "rocprofv3 counter passes over a child run, inside this invocation (one GPU only); 0: use the committed summary under profiles/")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (losses, scores, both nets' "
+                    f"parameters; a tensor above {DUMP_MAX_ELEMS} elements as a seeded sample of that many) as float32 DIR/<name>.npy")
     ap.add_argument("--launch-check", action="store_true", help="start the ranks, all-reduce over gloo on the CPU, print one line (no GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not launched and args.gpus > 1:
@@ -597,7 +639,7 @@ def main():
     pkg = load_package()
     pkg._C.lib()
     head = run_mode(pkg, args, args.precision, device, world, rank, use_dist)
-    want_sub = args.sub_record == 1 or (args.sub_record == -1 and world == 1 and not args.force_dist)
+    want_sub = args.sub_record == 1 or (args.sub_record == -1 and args.full and world == 1 and not args.force_dist)
     subs = {}
     if want_sub and args.precision == "f32":
         for mode in ("bf16x3", "bf16"):
@@ -642,8 +684,10 @@ def main():
                          "step_algorithmic_gbs": v2 * e_alg * esz_of[mode] / 1e9,
                          "step_frac_of_hbm_peak": v2 * e_alg * esz_of[mode] / 1e9 / PEAK_HBM_GBS,
                          "roofline": sub["roofline"], "conv_family": sub["conv_family"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.res, args.alpha, batch=args.batch)
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, head["outputs"])
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

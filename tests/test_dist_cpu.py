@@ -258,6 +258,42 @@ def test_bench_line_reports_every_rank_and_the_exchanges():
     assert not bench.is_winograd_instance("conv3x3_mid_kernel<4, 2, 1, 2, 0, 0, 1, 0>") and not bench.is_split_bf16_instance("conv3x3_wino_kernel<2, 2, 8, 8, 1, 0>")
 
 
+def test_bench_dumped_outputs_are_named_sampled_and_bounded(tmp_path):
+    """`bench.py --dump-outputs`: the step's statistics and every parameter of both nets by name, float32; a tensor above the element
+    bound is written as a sample whose indices depend on nothing but its size, so two runs (or two builds) compare element for element."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    torch.manual_seed(0)
+    G = pkg.models.Generator_PG([32, 16], image_size_init=8, latent_dim=64)
+    D = pkg.models.Discriminator_PG([16, 32], image_size_init=8)
+    tr = types.SimpleNamespace(flat_g=pkg.train.FlatParams(G), flat_d=pkg.train.FlatParams(D))
+    stats = {"D_loss": torch.tensor(1.5), "G_loss": torch.tensor(-0.25, dtype=torch.float64)}
+    stem = tr.flat_g.params[0]
+    assert stem.numel() > 1000
+    out = bench.step_outputs(tr, stats, max_elems=1000)
+    again = bench.step_outputs(tr, stats, max_elems=1000)
+    names = {f"G.{n}" for n in tr.flat_g.names} | {f"D.{n}" for n in tr.flat_d.names} | {"D_loss", "G_loss"}
+    assert set(out) == names
+    assert all(a.dtype == np.float32 for a in out.values())
+    assert out["G_loss"].tolist() == [-0.25]
+    big = out[f"G.{tr.flat_g.names[0]}"]
+    assert big.shape == (1000,) and np.array_equal(big, again[f"G.{tr.flat_g.names[0]}"])
+    assert np.isin(big, stem.detach().reshape(-1).numpy()).all()
+    for n, p in zip(tr.flat_d.names, tr.flat_d.params):
+        if p.numel() <= 1000:
+            assert np.array_equal(out[f"D.{n}"], p.detach().reshape(-1).numpy())
+    bench.write_outputs(str(tmp_path / "dump"), out)
+    assert sorted(os.listdir(tmp_path / "dump")) == sorted(n + ".npy" for n in names)
+    assert np.array_equal(np.load(tmp_path / "dump" / "D_loss.npy"), out["D_loss"])
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / "too_big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+
+
 def test_bench_parent_never_imports_torch():
     """The launcher process must not initialise HIP: it does not even import torch (checked on the source: everything above
     `launch_ranks` is stdlib, torch is imported inside the rank-side functions only)."""

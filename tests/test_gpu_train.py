@@ -461,3 +461,33 @@ def test_capture_survives_garbage_left_by_earlier_trainers(ngan):
         gc.set_threshold(*old)
     gc.collect()
     assert all(torch.isfinite(p).all() for p in t3.G.parameters())
+
+
+def test_plain_bench_run_dumps_reproducible_outputs(tmp_path):
+    """`bench.py` without --full: the headline and `ms_per_step` for exactly --steps timed steps, nothing of what --full adds, and
+    --dump-outputs writes the last step's losses and parameters, the same in two runs with the same arguments (a small shape)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--res", "16",
+                            "--batch", "4", "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        runs.append(json.loads(lines[0]))
+    for out in runs:
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["dtype"] == "f32" and out["higher_is_better"] is True
+        assert abs(out["value"] - 4 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+        assert out["roofline"] is None and out["conv_family"] is None
+        assert not {"bf16x3", "bf16", "cpu_baseline"} & set(out)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"D_loss.npy", "G_loss.npy", "score_real.npy", "score_fake.npy", "D_grad_pen.npy"} <= set(names)
+    assert any(n.startswith("G.") for n in names) and any(n.startswith("D.") for n in names)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, b, err_msg=n)

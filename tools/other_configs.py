@@ -8,10 +8,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONFIGS = ["--res 16 --batch 16 --alpha 1.0", "--res 64 --batch 64 --alpha 0.5", "--res 256 --batch 32 --alpha 1.0", "--res 512 --batch 8 --alpha 1.0",
            "--res 512 --batch 16 --alpha 0.5", "--res 128 --batch 64 --alpha 1.0"]
-print("python bench.py <shape flags> --steps 20 --warmup 5 --no-cpu-baseline --live-traffic 0 on one MI355X: the shapes of BASELINE.json's configs C1 - C5 "
+print("python bench.py <shape flags> --steps 20 --warmup 5 --full --no-cpu-baseline --live-traffic 0 on one MI355X: the shapes of BASELINE.json's configs C1 - C5 "
       "(and two more) in the three arithmetic modes: exact fp32 (headline), split-bf16 and bf16 activation storage (sub-records)", flush=True)
 for cfg in CONFIGS:
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *cfg.split(), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--live-traffic", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *cfg.split(), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--live-traffic", "0"],
                        capture_output=True, text=True, timeout=600)
     print("==", cfg, flush=True)
     try:
