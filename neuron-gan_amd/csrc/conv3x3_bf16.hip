@@ -33,6 +33,10 @@
 //   * workgroup -> tile: bands per XCD (blockIdx & 7) so that neighbouring tiles' halos meet in one L2.
 // Resample / epilogue / store mode are run-time (wave-uniform) branches, not template parameters: 16 (K, N) pairs x 4 tile shapes
 // are already 64 instances (conv3x3_bf16_impl.h, instantiated per K in conv3x3_bf16_k*.hip).
+// Any other contraction width -- a multiple of 16 up to 1024 (48, 96, 256, 512, 1024 ...: the reference's wide presets) -- runs in the
+// wide instances (conv3x3_bf16_wide_kernel, conv3x3_bf16_wide.hip): the K = 128 kernel looped over 128-channel slices of x, the last
+// slice zero-padded in staging and packing (no padded copy of x), one set of fp32 accumulators, one epilogue, one rounding.  A
+// compatibility path like fp32's wide layers: it re-stages the halo tile per slice and is not tuned.
 #include "conv3x3_bf16_impl.h"
 
 namespace {
@@ -44,6 +48,8 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, __bf16* __
 }
 
 bool bf16_channels_ok(int c) { return c == 16 || c == 32 || c == 64 || c == 128; }
+// contraction widths of the wide instances: every other multiple of 16 up to 1024, in 128-channel slices (conv3x3_bf16_impl.h)
+bool bf16_wide_ok(int k) { return k > 0 && k <= 1024 && k % 16 == 0 && !bf16_channels_ok(k); }
 
 // tile shape (pixel groups of 16 per workgroup, narrow = 16-pixel-wide tiles).  N <= 32: 8 rows of 32 while that still gives two
 // workgroups per CU, else 4, else 2 rows (4 x 16 for images at most 16 wide).  N >= 64: 64 pixels, 32 when that leaves CUs idle.
@@ -61,13 +67,16 @@ void pick_tile(int B, int H, int W, int N, int& pgt, bool& narrow) {
 }  // namespace
 
 long ngan::conv3x3_bf16_elements(int K, int N) {
-    if (!bf16_channels_ok(K) || !bf16_channels_ok(N)) return 0;
+    if (!bf16_channels_ok(N)) return 0;
+    if (bf16_wide_ok(K)) return 36L * ((K + 127) / 128) * (N / 16) * 512;       // 128-channel slices, the last one zero-padded
+    if (!bf16_channels_ok(K)) return 0;
     return (long)(K == 16 ? 5 : 9 * (K / 32)) * (N / 16) * 512;
 }
 
 int ngan::conv3x3_bf16_pack_launch(const float* w, float* packed, int Cout, int Cin, int mode, float scale, hipStream_t s) {
     const long tot = conv3x3_bf16_elements(mode == 0 ? Cin : Cout, mode == 0 ? Cout : Cin);
-    NGAN_REQUIRE(tot > 0, NGAN_ERR_SHAPE, "conv3x3_pack_weights: precision 5 (bf16) takes 16 / 32 / 64 / 128 channels (Cin=%d, Cout=%d)", Cin, Cout);
+    NGAN_REQUIRE(tot > 0, NGAN_ERR_SHAPE, "conv3x3_pack_weights: precision 5 (bf16) takes outputs 16 / 32 / 64 / 128 and a contraction of up to 1024 "
+                 "channels, a multiple of 16 (Cin=%d, Cout=%d, mode %d)", Cin, Cout, mode);
     hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(ngan::ceil_div(tot, 256)), dim3(256), 0, s, w, reinterpret_cast<__bf16*>(packed), Cout, Cin,
                        mode, scale, tot);
     return ngan::launch_status("ngan_conv3x3_pack_weights(bf16)");
@@ -76,7 +85,10 @@ int ngan::conv3x3_bf16_pack_launch(const float* w, float* packed, int Cout, int 
 int ngan::conv3x3_bf16_kernel_name(int B, int H, int W, int K, int N, char* buf, int len) {
     int pgt; bool narrow;
     pick_tile(B, H, W, N, pgt, narrow);
-    snprintf(buf, len, "conv3x3_bf16_kernel<%d, %d, %d, %s, %s>", K, N, pgt, N >= 64 ? "true" : "false", narrow ? "true" : "false");
+    if (bf16_wide_ok(K))
+        snprintf(buf, len, "conv3x3_bf16_wide_kernel<%d, %d, %s, %s>", N, pgt, N >= 64 ? "true" : "false", narrow ? "true" : "false");
+    else
+        snprintf(buf, len, "conv3x3_bf16_kernel<%d, %d, %d, %s, %s>", K, N, pgt, N >= 64 ? "true" : "false", narrow ? "true" : "false");
     return NGAN_OK;
 }
 
@@ -86,7 +98,8 @@ extern "C" int ngan_bf16_conv3x3_fwd(const ngan_bf16* x, const float* packed, co
                                      float slope, float eps, void* stream) {
     NGAN_REQUIRE(x && packed && (y || epilogue == EPI_TO_IMAGE), NGAN_ERR_ARG, "bf16_conv3x3_fwd: null pointer");
     NGAN_REQUIRE(B > 0 && H > 0 && W > 0, NGAN_ERR_SHAPE, "bf16_conv3x3_fwd: bad dims B=%d H=%d W=%d", B, H, W);
-    NGAN_REQUIRE(bf16_channels_ok(K) && bf16_channels_ok(N), NGAN_ERR_SHAPE, "bf16_conv3x3_fwd: K=%d, N=%d must be 16 / 32 / 64 / 128", K, N);
+    NGAN_REQUIRE((bf16_channels_ok(K) || bf16_wide_ok(K)) && bf16_channels_ok(N), NGAN_ERR_SHAPE,
+                 "bf16_conv3x3_fwd: K=%d must be a multiple of 16 up to 1024, N=%d one of 16 / 32 / 64 / 128", K, N);
     NGAN_REQUIRE(resample >= 0 && resample <= 2, NGAN_ERR_ARG, "bf16_conv3x3_fwd: resample %d", resample);
     NGAN_REQUIRE(epilogue >= EPI_NONE && epilogue <= EPI_TO_IMAGE, NGAN_ERR_ARG, "bf16_conv3x3_fwd: epilogue %d", epilogue);
     NGAN_REQUIRE(out_mode == 0 || (out_mode == 1 && (epilogue == EPI_NONE || epilogue == EPI_PN_BWD) && resample == 0), NGAN_ERR_ARG,
@@ -103,10 +116,11 @@ extern "C" int ngan_bf16_conv3x3_fwd(const ngan_bf16* x, const float* packed, co
     ConvArgsB a{reinterpret_cast<const __bf16*>(x), reinterpret_cast<const __bf16*>(packed), bias, reinterpret_cast<__bf16*>(y),
                 (epilogue == EPI_LRELU_PN || epilogue == EPI_TO_IMAGE) ? rnorm : nullptr, B, H, W, 0, 0, 0, 0, resample, epilogue, out_mode, slope, eps,
                 epilogue == EPI_PN_BWD ? reinterpret_cast<const __bf16*>(aux_in) : nullptr,
-                epilogue == EPI_TO_IMAGE ? reinterpret_cast<const float*>(aux_in) : nullptr, aux_rn, aux_out};
+                epilogue == EPI_TO_IMAGE ? reinterpret_cast<const float*>(aux_in) : nullptr, aux_rn, aux_out, K};
     hipStream_t s = (hipStream_t)stream;
     int pgt; bool narrow;
     pick_tile(B, H, W, N, pgt, narrow);
+    if (bf16_wide_ok(K)) return ngan::conv3x3_bf16_launch_wide(a, N, pgt, narrow, s);
     switch (K) {
         case 16: return ngan::conv3x3_bf16_launch_k16(a, N, pgt, narrow, s);
         case 32: return ngan::conv3x3_bf16_launch_k32(a, N, pgt, narrow, s);

@@ -1,5 +1,6 @@
-// Kernel template of the bf16-storage 3x3 convolution (precision code 5); included by conv3x3_bf16_k{16,32,64,128}.hip, one translation
-// unit per contraction width so that the 64 instances build in parallel.  Design notes: conv3x3_bf16.hip.
+// Kernel template of the bf16-storage 3x3 convolution (precision code 5); included by conv3x3_bf16_k{16,32,64,128}.hip and
+// conv3x3_bf16_wide.hip, one translation unit per contraction width so that the instances build in parallel.  Design notes:
+// conv3x3_bf16.hip.
 #pragma once
 #include "conv3x3_internal.h"
 
@@ -10,12 +11,14 @@ struct ConvArgsB {
     int resample, epilogue, out_mode;
     float slope, eps;
     const __bf16* ay; const float* wimg; const float* arn; float* aout;
+    int kc;                                   // channels of x (K, or for the wide instances any other multiple of 16 up to 1024)
 };
 // one launcher per contraction width (conv3x3_bf16_k*.hip): picks the instance for (N, tile shape) and launches it
 int conv3x3_bf16_launch_k16(ConvArgsB a, int N, int pgt, bool narrow, hipStream_t s);
 int conv3x3_bf16_launch_k32(ConvArgsB a, int N, int pgt, bool narrow, hipStream_t s);
 int conv3x3_bf16_launch_k64(ConvArgsB a, int N, int pgt, bool narrow, hipStream_t s);
 int conv3x3_bf16_launch_k128(ConvArgsB a, int N, int pgt, bool narrow, hipStream_t s);
+int conv3x3_bf16_launch_wide(ConvArgsB a, int N, int pgt, bool narrow, hipStream_t s);    // a.kc not in {16, 32, 64, 128}
 }  // namespace ngan
 using ngan::ConvArgsB;
 
@@ -55,19 +58,21 @@ __device__ __forceinline__ void st4bf(__amdgpu_buffer_rsrc_t rs, unsigned off, f
 // eight); capping the registers (launch bounds, lane coordinates behind an opaque barrier) made it spill 44 - 125 registers to scratch
 // instead of recomputing, and the 16 -> 16 forward went from 63 to 152 us.  The one-tile-per-workgroup form below stays: what hides its
 // staging and epilogue latency is occupancy (64 registers, 14 KB of LDS: eight workgroups per CU).
-template <int K, int N, int PGT, bool NS, bool NARROW>
-// (the 16 -> 16 instances fit 64 registers: eight workgroups per CU instead of four.  303 VALU + 190 SALU + 20 MFMA instructions per wave and
-// tile: 47 % of every SIMD's cycles go into vector-instruction issue and some instruction is active 91 % of the time -- the kernel is bound
-// by the instructions of its staging and epilogue, and the extra waves give the issue logic something to pick from while others wait;
-// PMC record and its corrected reading: profiles/r04_pmc_bf16_1616.txt)
-__global__ __launch_bounds__(256, (!NS && K == 16 && N == 16) ? 8 : 1) void conv3x3_bf16_kernel(ConvArgsB a) {
+// WIDE (conv3x3_bf16_wide_kernel, K = 128): the contraction runs over the a.kc channels of x in slices of 128 -- stage one slice of the
+// halo tile (the K = 128 staging and swizzle; channels at and beyond a.kc are out-of-range offsets: zeros), contract its 36 steps into
+// the same fp32 accumulators, stage the next.  The epilogue runs once, after the last slice, and the only bf16 rounding is the store's.
+// The packed weights are the K = 128 layout one slice after another (bf16_weight), streamed through the register ring 9 steps ahead
+// (9 divides 36: a ring slot holds the same step of every slice).
+template <int K, int N, int PGT, bool NS, bool NARROW, bool WIDE>
+__device__ __forceinline__ void conv3x3_bf16_body(const ConvArgsB& a) {
     constexpr int P = K / 8, NT = N / 16, KS = K >= 32 ? K / 32 : 1, S = K == 16 ? 5 : 9 * KS;
     constexpr int TW = NARROW ? 16 : 32, GPR = TW / 16, TH = PGT / GPR, HH = TH + 2, HW = TW + 2, NPIX = HH * HW;
     constexpr int NCHUNK = NPIX * P, NCH = (NCHUNK + 255) / 256;
     constexpr int NTW = NS ? NT / 4 : NT, PGW = NS ? PGT : PGT / 4;
-    constexpr bool WREG = S * NTW <= 18;                     // the wave's weight fragments fit its registers for the whole tile
-    constexpr int RD = S < 8 ? S : 8;                        // otherwise: a register ring, RD contraction steps ahead of their use
+    constexpr bool WREG = !WIDE && S * NTW <= 18;            // the wave's weight fragments fit its registers for the whole tile
+    constexpr int RD = WIDE ? 9 : S < 8 ? S : 8;             // otherwise: a register ring, RD contraction steps ahead of their use
     static_assert(PGT % GPR == 0 && (NS || PGT % 4 == 0) && (!NS || NT % 4 == 0), "tile split");
+    static_assert(!WIDE || (K == 128 && S % RD == 0), "wide: 128-channel slices, the ring depth divides a slice's steps");
     constexpr int PH = (TH + 1) / 2 + 2, PW = TW / 2 + 2, NPCH = PH * PW * P, NPC = (NPCH + 255) / 256;   // low-resolution patch of a bilinear input
     __shared__ u32x4 tile[NPIX * P];
     __shared__ u32x4 patch[NPCH];
@@ -80,6 +85,8 @@ __global__ __launch_bounds__(256, (!NS && K == 16 && N == 16) ? 8 : 1) void conv
     const int y0 = tyi * TH, x0 = txi * TW;
     const int H = a.H, W = a.W;
     const int j0 = NS ? wave * NTW : 0;                      // this wave's first output tile
+    const int KG = WIDE ? a.kc : K;                          // channels per pixel of x in memory
+    const int NSL = WIDE ? (KG + 127) / 128 : 1, SG = NSL * S;   // contraction slices, steps over all slices
 
     // column swizzle of the 16-byte chunk index (conv3x3_bf16.hip)
     auto swz = [](int X) -> int { return P > 2 ? 2 * ((X / (16 / P)) & (P / 2 - 1)) : 0; };
@@ -96,88 +103,93 @@ __global__ __launch_bounds__(256, (!NS && K == 16 && N == 16) ? 8 : 1) void conv
     // ---- stage the halo tile: HH x HW pixels x K channels, 16 bytes per item, resampled on the way.  Loads go through a buffer
     // descriptor of the tile's image: a row above / below the image is an out-of-range offset by itself (zeros: the conv padding),
     // a column outside costs one select; no branch around any load.
-    if (a.resample == NGAN_RESAMPLE_NONE) {
-        const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.x + (long)b * H * W * K, (unsigned)(H * W * K) * 2u);
-        const int tile_off = ((y0 - 1) * W + x0 - 1) * K * 2;
-        u32x4 v[NCH];
+    // cb: first channel of the slice (0 unless WIDE)
+    auto stage = [&](int cb) {
+        if (a.resample == NGAN_RESAMPLE_NONE) {
+            const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.x + (long)b * H * W * KG, (unsigned)(H * W * KG) * 2u);
+            const int tile_off = ((y0 - 1) * W + x0 - 1) * KG * 2;
+            u32x4 v[NCH];
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int e = tid + i * 256;
-            const int pix = e / P, sl = e % P, hy = pix / HW, hx = pix % HW;
-            const bool ok = e < NCHUNK && (unsigned)(x0 + hx - 1) < (unsigned)W && (unsigned)(y0 + hy - 1) < (unsigned)H;
-            v[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (unsigned)(tile_off + ((hy * W + hx) * K + sl * 8) * 2) : BF16_OOB, 0, 0));
-        }
+            for (int i = 0; i < NCH; ++i) {
+                const int e = tid + i * 256;
+                const int pix = e / P, sl = e % P, hy = pix / HW, hx = pix % HW;
+                const bool ok = e < NCHUNK && (unsigned)(x0 + hx - 1) < (unsigned)W && (unsigned)(y0 + hy - 1) < (unsigned)H && (!WIDE || cb + sl * 8 < KG);
+                v[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (unsigned)(tile_off + ((hy * W + hx) * KG + cb + sl * 8) * 2) : BF16_OOB, 0, 0));
+            }
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int e = tid + i * 256;
-            const int pix = e / P, sl = e % P, hx = pix % HW;
-            if (e < NCHUNK) tile[pix * P + (sl ^ swz(hx))] = v[i];
-        }
-    } else if (a.resample == NGAN_RESAMPLE_POOL2) {
-        // x is (B, 2H, 2W, K); a staged element is the 2x2 mean, associated like ngan_pool2_fwd: 0.25 * ((a + b) + (c + d))
-        const int W2 = 2 * W;
-        const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.x + (long)b * 4 * H * W * K, (unsigned)(4 * H * W * K) * 2u);
+            for (int i = 0; i < NCH; ++i) {
+                const int e = tid + i * 256;
+                const int pix = e / P, sl = e % P, hx = pix % HW;
+                if (e < NCHUNK) tile[pix * P + (sl ^ swz(hx))] = v[i];
+            }
+        } else if (a.resample == NGAN_RESAMPLE_POOL2) {
+            // x is (B, 2H, 2W, K); a staged element is the 2x2 mean, associated like ngan_pool2_fwd: 0.25 * ((a + b) + (c + d))
+            const int W2 = 2 * W;
+            const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.x + (long)b * 4 * H * W * KG, (unsigned)(4 * H * W * KG) * 2u);
 #pragma unroll 2
-        for (int i = 0; i < NCH; ++i) {
-            const int e = tid + i * 256;
-            const int pix = e / P, sl = e % P, hy = pix / HW, hx = pix % HW;
-            const int gy = y0 + hy - 1, gx = x0 + hx - 1;
-            const bool ok = e < NCHUNK && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-            const unsigned o = ok ? (unsigned)(((2 * gy * W2 + 2 * gx) * K + sl * 8) * 2) : BF16_OOB;
-            const unsigned o1 = ok ? o + K * 2 : BF16_OOB, o2 = ok ? o + W2 * K * 2 : BF16_OOB, o3 = ok ? o + (W2 + 1) * K * 2 : BF16_OOB;
-            const f8 p00 = unpack8(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 0)));
-            const f8 p01 = unpack8(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o1, 0, 0)));
-            const f8 p10 = unpack8(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o2, 0, 0)));
-            const f8 p11 = unpack8(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o3, 0, 0)));
-            f8 r;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) r.v[c] = 0.25f * ((p00.v[c] + p01.v[c]) + (p10.v[c] + p11.v[c]));
-            if (e < NCHUNK) tile[pix * P + (sl ^ swz(hx))] = pack8(r);
-        }
-    } else {
-        // x is (B, H/2, W/2, K); bilinear x2, align_corners = False (models.py:87-89), the taps and the association of up2_fwd_kernel.
-        // The LOW-resolution patch under the halo tile ((TH + 1) / 2 + 2 rows x TW / 2 + 2 columns, clamped coordinates = the taps'
-        // edge rule) is staged once -- one or two 16-byte loads per thread instead of four dependent loads per staged item -- and
-        // expanded LDS -> LDS.  Hi-res index Y blends low-res rows i0 = (Y - 1) >> 1 and i0 + 1 with weights (.75, .25) for odd Y and
-        // (.25, .75) for even Y; rows / columns outside the hi-res image are the conv's zero padding, not a blend.
-        const int h = H >> 1, w = W >> 1;
-        const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.x + (long)b * h * w * K, (unsigned)(h * w * K) * 2u);
-        const int ly0 = (y0 - 2) >> 1, lx0 = (x0 - 2) >> 1;
-        u32x4 pv[NPC];
-#pragma unroll
-        for (int i = 0; i < NPC; ++i) {
-            const int e = tid + i * 256;
-            const int pp = e / P, sl = e % P, pr = pp / PW, pc = pp % PW;
-            const int ly = min(max(ly0 + pr, 0), h - 1), lx = min(max(lx0 + pc, 0), w - 1);
-            pv[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, e < NPCH ? (unsigned)(((ly * w + lx) * K + sl * 8) * 2) : BF16_OOB, 0, 0));
-        }
-#pragma unroll
-        for (int i = 0; i < NPC; ++i)
-            if (tid + i * 256 < NPCH) patch[tid + i * 256] = pv[i];
-        __syncthreads();
-#pragma unroll 2
-        for (int i = 0; i < NCH; ++i) {
-            const int e = tid + i * 256;
-            const int pix = e / P, sl = e % P, hy = pix / HW, hx = pix % HW;
-            const int Y = y0 + hy - 1, X = x0 + hx - 1;
-            const bool ok = (unsigned)Y < (unsigned)H && (unsigned)X < (unsigned)W;
-            const int r0 = ((Y - 1) >> 1) - ly0, c0 = ((X - 1) >> 1) - lx0;
-            const float wya = (Y & 1) ? 0.75f : 0.25f, wxa = (X & 1) ? 0.75f : 0.25f, wyb = 1.0f - wya, wxb = 1.0f - wxa;
-            u32x4 o = (u32x4){0u, 0u, 0u, 0u};
-            if (e < NCHUNK && ok) {
-                const u32x4* pr0 = patch + (r0 * PW + c0) * P + sl;
-                const f8 t0 = unpack8(pr0[0]), t1 = unpack8(pr0[P]), b0 = unpack8(pr0[PW * P]), b1 = unpack8(pr0[PW * P + P]);
+            for (int i = 0; i < NCH; ++i) {
+                const int e = tid + i * 256;
+                const int pix = e / P, sl = e % P, hy = pix / HW, hx = pix % HW;
+                const int gy = y0 + hy - 1, gx = x0 + hx - 1;
+                const bool ok = e < NCHUNK && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W && (!WIDE || cb + sl * 8 < KG);
+                const unsigned o = ok ? (unsigned)(((2 * gy * W2 + 2 * gx) * KG + cb + sl * 8) * 2) : BF16_OOB;
+                const unsigned o1 = ok ? o + KG * 2 : BF16_OOB, o2 = ok ? o + W2 * KG * 2 : BF16_OOB, o3 = ok ? o + (W2 + 1) * KG * 2 : BF16_OOB;
+                const f8 p00 = unpack8(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 0)));
+                const f8 p01 = unpack8(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o1, 0, 0)));
+                const f8 p10 = unpack8(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o2, 0, 0)));
+                const f8 p11 = unpack8(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o3, 0, 0)));
                 f8 r;
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const float top = fmaf(t1.v[c], wxb, t0.v[c] * wxa), bot = fmaf(b1.v[c], wxb, b0.v[c] * wxa);
-                    r.v[c] = fmaf(bot, wyb, top * wya);
-                }
-                o = pack8(r);
+                for (int c = 0; c < 8; ++c) r.v[c] = 0.25f * ((p00.v[c] + p01.v[c]) + (p10.v[c] + p11.v[c]));
+                if (e < NCHUNK) tile[pix * P + (sl ^ swz(hx))] = pack8(r);
             }
-            if (e < NCHUNK) tile[pix * P + (sl ^ swz(hx))] = o;
+        } else {
+            // x is (B, H/2, W/2, K); bilinear x2, align_corners = False (models.py:87-89), the taps and the association of up2_fwd_kernel.
+            // The LOW-resolution patch under the halo tile ((TH + 1) / 2 + 2 rows x TW / 2 + 2 columns, clamped coordinates = the taps'
+            // edge rule) is staged once -- one or two 16-byte loads per thread instead of four dependent loads per staged item -- and
+            // expanded LDS -> LDS.  Hi-res index Y blends low-res rows i0 = (Y - 1) >> 1 and i0 + 1 with weights (.75, .25) for odd Y and
+            // (.25, .75) for even Y; rows / columns outside the hi-res image are the conv's zero padding, not a blend.
+            const int h = H >> 1, w = W >> 1;
+            const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.x + (long)b * h * w * KG, (unsigned)(h * w * KG) * 2u);
+            const int ly0 = (y0 - 2) >> 1, lx0 = (x0 - 2) >> 1;
+            u32x4 pv[NPC];
+#pragma unroll
+            for (int i = 0; i < NPC; ++i) {
+                const int e = tid + i * 256;
+                const int pp = e / P, sl = e % P, pr = pp / PW, pc = pp % PW;
+                const int ly = min(max(ly0 + pr, 0), h - 1), lx = min(max(lx0 + pc, 0), w - 1);
+                const bool ok = e < NPCH && (!WIDE || cb + sl * 8 < KG);
+                pv[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (unsigned)(((ly * w + lx) * KG + cb + sl * 8) * 2) : BF16_OOB, 0, 0));
+            }
+#pragma unroll
+            for (int i = 0; i < NPC; ++i)
+                if (tid + i * 256 < NPCH) patch[tid + i * 256] = pv[i];
+            __syncthreads();
+#pragma unroll 2
+            for (int i = 0; i < NCH; ++i) {
+                const int e = tid + i * 256;
+                const int pix = e / P, sl = e % P, hy = pix / HW, hx = pix % HW;
+                const int Y = y0 + hy - 1, X = x0 + hx - 1;
+                const bool ok = (unsigned)Y < (unsigned)H && (unsigned)X < (unsigned)W;
+                const int r0 = ((Y - 1) >> 1) - ly0, c0 = ((X - 1) >> 1) - lx0;
+                const float wya = (Y & 1) ? 0.75f : 0.25f, wxa = (X & 1) ? 0.75f : 0.25f, wyb = 1.0f - wya, wxb = 1.0f - wxa;
+                u32x4 o = (u32x4){0u, 0u, 0u, 0u};
+                if (e < NCHUNK && ok) {
+                    const u32x4* pr0 = patch + (r0 * PW + c0) * P + sl;
+                    const f8 t0 = unpack8(pr0[0]), t1 = unpack8(pr0[P]), b0 = unpack8(pr0[PW * P]), b1 = unpack8(pr0[PW * P + P]);
+                    f8 r;
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) {
+                        const float top = fmaf(t1.v[c], wxb, t0.v[c] * wxa), bot = fmaf(b1.v[c], wxb, b0.v[c] * wxa);
+                        r.v[c] = fmaf(bot, wyb, top * wya);
+                    }
+                    o = pack8(r);
+                }
+                if (e < NCHUNK) tile[pix * P + (sl ^ swz(hx))] = o;
+            }
         }
-    }
+    };
+    stage(0);
     __syncthreads();
 
     // ---- contraction.  Pixel group gi of this wave: tile row gi / GPR, columns 16 (gi % GPR) + p.  The B-operand fragment of
@@ -209,21 +221,31 @@ __global__ __launch_bounds__(256, (!NS && K == 16 && N == 16) ? 8 : 1) void conv
     for (int pg = 0; pg < PGW; ++pg)
 #pragma unroll
         for (int j = 0; j < NTW; ++j) acc[pg][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // s0: the slice's first step in the packed weights (0 unless WIDE)
+    auto contract = [&](int s0) {
 #pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const int to = toff(s);
-        bf16x8 bf[PGW];
+        for (int s = 0; s < S; ++s) {
+            const int to = toff(s);
+            bf16x8 bf[PGW];
 #pragma unroll
-        for (int pg = 0; pg < PGW; ++pg) bf[pg] = __builtin_bit_cast(bf16x8, tile[pbase[pg] + to]);
+            for (int pg = 0; pg < PGW; ++pg) bf[pg] = __builtin_bit_cast(bf16x8, tile[pbase[pg] + to]);
 #pragma unroll
-        for (int j = 0; j < NTW; ++j)
+            for (int j = 0; j < NTW; ++j)
 #pragma unroll
-            for (int pg = 0; pg < PGW; ++pg)
-                acc[pg][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[WREG ? s : s % RD][j], bf[pg], acc[pg][j], 0, 0, 0);
-        if (!WREG && s + RD < S) {
+                for (int pg = 0; pg < PGW; ++pg)
+                    acc[pg][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[WREG ? s : s % RD][j], bf[pg], acc[pg][j], 0, 0, 0);
+            if (!WREG && s0 + s + RD < SG) {
 #pragma unroll
-            for (int j = 0; j < NTW; ++j) wr[s % RD][j] = wfrag(s + RD, j);
+                for (int j = 0; j < NTW; ++j) wr[s % RD][j] = wfrag(s0 + s + RD, j);
+            }
         }
+    };
+    contract(0);
+    for (int ksl = 1; ksl < NSL; ++ksl) {                    // WIDE: the remaining 128-channel slices
+        __syncthreads();                                     // every wave is done with the previous slice's tile and patch
+        stage(128 * ksl);
+        __syncthreads();
+        contract(ksl * S);
     }
 
     // ---- epilogue: lane (p, q) holds channels 16 (j0 + j) + 4 q .. + 3 of pixel (prow, pcol) of each of its groups.  A per-pixel sum
@@ -420,13 +442,29 @@ __global__ __launch_bounds__(256, (!NS && K == 16 && N == 16) ? 8 : 1) void conv
 }
 
 template <int K, int N, int PGT, bool NS, bool NARROW>
+// (the 16 -> 16 instances fit 64 registers: eight workgroups per CU instead of four.  303 VALU + 190 SALU + 20 MFMA instructions per wave and
+// tile: 47 % of every SIMD's cycles go into vector-instruction issue and some instruction is active 91 % of the time -- the kernel is bound
+// by the instructions of its staging and epilogue, and the extra waves give the issue logic something to pick from while others wait;
+// PMC record and its corrected reading: profiles/r04_pmc_bf16_1616.txt)
+__global__ __launch_bounds__(256, (!NS && K == 16 && N == 16) ? 8 : 1) void conv3x3_bf16_kernel(ConvArgsB a) {
+    conv3x3_bf16_body<K, N, PGT, NS, NARROW, false>(a);
+}
+
+// contraction over any multiple of 16 channels up to 1024 other than 16 / 32 / 64 / 128 (a.kc), in 128-channel slices
+template <int N, int PGT, bool NS, bool NARROW>
+__global__ __launch_bounds__(256) void conv3x3_bf16_wide_kernel(ConvArgsB a) {
+    conv3x3_bf16_body<128, N, PGT, NS, NARROW, true>(a);
+}
+
+template <int K, int N, int PGT, bool NS, bool NARROW, bool WIDE>
 int launch_bf16(ConvArgsB a, hipStream_t s) {
     constexpr int TW = NARROW ? 16 : 32, TH = PGT / (TW / 16);
     a.tiles_x = ngan::ceil_div(a.W, TW);
     a.tiles_y = ngan::ceil_div(a.H, TH);
     a.n_tiles = a.B * a.tiles_x * a.tiles_y;
     a.band = ngan::ceil_div(a.n_tiles, 8);
-    hipLaunchKernelGGL((conv3x3_bf16_kernel<K, N, PGT, NS, NARROW>), dim3(8 * a.band), dim3(256), 0, s, a);
+    if constexpr (WIDE) hipLaunchKernelGGL((conv3x3_bf16_wide_kernel<N, PGT, NS, NARROW>), dim3(8 * a.band), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((conv3x3_bf16_kernel<K, N, PGT, NS, NARROW>), dim3(8 * a.band), dim3(256), 0, s, a);
     return ngan::launch_status("ngan_bf16_conv3x3_fwd");
 }
 
@@ -434,26 +472,26 @@ int launch_bf16(ConvArgsB a, hipStream_t s) {
 // N = 64 / 128: output-tile split, PGT = 4 / 2, wide or narrow.  (PGT = 8 -- 128 pixels per workgroup, half the L2 weight traffic of a launch
 // with >= 256 such tiles -- was built and measured on BASELINE.json's C2, whose 128 -> 128 layers see 128 images of 16 x 16: iteration
 // 2.39 -> 2.47 ms.  Fewer, longer MFMA chains cost more than the weight stream they save; not kept.)
-template <int K, int N>
+template <int K, int N, bool WIDE>
 int dispatch_tile(const ConvArgsB& a, int pgt, bool narrow, hipStream_t s) {
     if constexpr (N <= 32) {
-        if (narrow) return launch_bf16<K, N, 4, false, true>(a, s);
-        if (pgt == 16) return launch_bf16<K, N, 16, false, false>(a, s);
-        if (pgt == 8) return launch_bf16<K, N, 8, false, false>(a, s);
-        return launch_bf16<K, N, 4, false, false>(a, s);
+        if (narrow) return launch_bf16<K, N, 4, false, true, WIDE>(a, s);
+        if (pgt == 16) return launch_bf16<K, N, 16, false, false, WIDE>(a, s);
+        if (pgt == 8) return launch_bf16<K, N, 8, false, false, WIDE>(a, s);
+        return launch_bf16<K, N, 4, false, false, WIDE>(a, s);
     } else {
-        if (narrow) return pgt == 4 ? launch_bf16<K, N, 4, true, true>(a, s) : launch_bf16<K, N, 2, true, true>(a, s);
-        return pgt == 4 ? launch_bf16<K, N, 4, true, false>(a, s) : launch_bf16<K, N, 2, true, false>(a, s);
+        if (narrow) return pgt == 4 ? launch_bf16<K, N, 4, true, true, WIDE>(a, s) : launch_bf16<K, N, 2, true, true, WIDE>(a, s);
+        return pgt == 4 ? launch_bf16<K, N, 4, true, false, WIDE>(a, s) : launch_bf16<K, N, 2, true, false, WIDE>(a, s);
     }
 }
 
-template <int K>
+template <int K, bool WIDE = false>
 int dispatch_n(const ConvArgsB& a, int N, int pgt, bool narrow, hipStream_t s) {
     switch (N) {
-        case 16: return dispatch_tile<K, 16>(a, pgt, narrow, s);
-        case 32: return dispatch_tile<K, 32>(a, pgt, narrow, s);
-        case 64: return dispatch_tile<K, 64>(a, pgt, narrow, s);
-        default: return dispatch_tile<K, 128>(a, pgt, narrow, s);
+        case 16: return dispatch_tile<K, 16, WIDE>(a, pgt, narrow, s);
+        case 32: return dispatch_tile<K, 32, WIDE>(a, pgt, narrow, s);
+        case 64: return dispatch_tile<K, 64, WIDE>(a, pgt, narrow, s);
+        default: return dispatch_tile<K, 128, WIDE>(a, pgt, narrow, s);
     }
 }
 

@@ -114,7 +114,8 @@ __device__ __forceinline__ void pin_registers_after(float4& v, float& dep) {
 
 // plain-bf16 packing: fp32 OIHW master weights * scale -> bf16, layout [step][n-tile j][lane][8]; lane l holds output channel
 // n = 16 j + (l & 15) and contraction index kk = 8 (l >> 4) + e.  K = 16: step = tap pair (kk < 16 -> tap 2 step, else 2 step + 1; tap 9 is
-// zero padding), 5 steps; K = 32 KS: step = tap * KS + ks, channel 32 ks + kk.  mode 1 (input gradient): contraction over the
+// zero padding), 5 steps; K = 32 KS (32, 64, 128): step = tap * KS + ks, channel 32 ks + kk; any other K (the wide instances): the
+// K = 128 layout per 128-channel slice sl, step = 36 sl + 4 tap + ks, channel 128 sl + 32 ks + kk, zero at and beyond K.  mode 1 (input gradient): contraction over the
 // OUTPUT channels of the layer, taps flipped.
 __device__ __forceinline__ __bf16 bf16_weight(const float* __restrict__ w, int Cout, int Cin, int mode, float scale, long idx) {
     const int K = mode == 0 ? Cin : Cout, N = mode == 0 ? Cout : Cin;
@@ -123,10 +124,15 @@ __device__ __forceinline__ __bf16 bf16_weight(const float* __restrict__ w, int C
     const long r = idx >> 9;
     const int j = r % NT, step = r / NT;
     const int n = j * 16 + (lane & 15), kk = 8 * (lane >> 4) + e;
-    const int tap = K == 16 ? 2 * step + (kk >> 4) : step / KS;
-    const int k = K == 16 ? (kk & 15) : (step % KS) * 32 + kk;
+    int tap = K == 16 ? 2 * step + (kk >> 4) : step / KS;
+    int k = K == 16 ? (kk & 15) : (step % KS) * 32 + kk;
+    if (K > 128 || (K & (K - 1))) {           // wide instances: the K = 128 layout per 128-channel slice, zeros beyond K
+        const int sl = step / 36, s = step % 36;
+        tap = s >> 2;
+        k = sl * 128 + (s & 3) * 32 + kk;
+    }
     float v = 0.f;
-    if (tap < 9) v = mode == 0 ? w[((long)n * Cin + k) * 9 + tap] : w[((long)k * Cin + n) * 9 + (8 - tap)];
+    if (tap < 9 && k < K) v = mode == 0 ? w[((long)n * Cin + k) * 9 + tap] : w[((long)k * Cin + n) * 9 + (8 - tap)];
     return (__bf16)(v * scale);
 }
 

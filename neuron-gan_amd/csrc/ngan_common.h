@@ -38,17 +38,23 @@ int reduce_partials_acc(const float* partials, int nparts, int M, long stride, f
 int reduce_partials_split(const float* partials, int nparts, int M, long stride, float* out, int M1, float* out2, float scale,
                           hipStream_t s);
 
-// wide.hip: the same operators for channel counts outside the lane-group kernels' range (C % 4 == 0, any size)
-int wide_pn_fwd(const float* c, const float* bias, float* y, float* rn, long npix, int C, float slope, float eps, hipStream_t s);
-int wide_pn_bwd(const float* gy, const float* gy2, const float* gr, const float* y, const float* rn, float* gc, long npix, int C, float slope, hipStream_t s);
-int wide_pn_bwdbwd(const float* h, const float* gy, const float* y, const float* rn, float* ggy, float* gy_out, float* gr_out, long npix, int C,
-                   float slope, hipStream_t s);
-int wide_channel_sum(const float* g, float* out, long npix, int C, float scale, hipStream_t s);
-int wide_to_image_fwd(const float* x, const float* w, float* t, long npix, int C, int Ncol, hipStream_t s);
-int wide_to_image_bwd(const float* g, const float* t, const float* x, const float* w, float* gx, float* gw, long npix, int C, int Ncol,
-                      const float* rn, float slope, hipStream_t s);
-int wide_from_image_dx(const float* g, const float* w, float* gx, int B, int H, int W, int Ncol, int C, int pool, hipStream_t s);
-int wide_from_image_dw(const float* x, const float* g, float* gw, float* gb, int B, int H, int W, int Ncol, int C, int pool, hipStream_t s);
+// wide.hip: the same operators for channel counts outside the lane-group kernels' range (C % 4 == 0, any size), over the activation
+// storage type T = float / __bf16 (instantiated for both in wide.hip)
+template <typename T> int wide_pn_fwd(const T* c, const float* bias, T* y, float* rn, long npix, int C, float slope, float eps, hipStream_t s);
+template <typename T> int wide_pn_bwd(const T* gy, const T* gy2, const float* gr, const T* y, const float* rn, T* gc, long npix, int C, float slope,
+                                      hipStream_t s);
+template <typename T> int wide_pn_bwdbwd(const T* h, const T* gy, const T* y, const float* rn, T* ggy, T* gy_out, float* gr_out, long npix, int C,
+                                         float slope, hipStream_t s);
+template <typename T> int wide_channel_sum(const T* g, float* out, long npix, int C, float scale, hipStream_t s);
+template <typename T> int wide_to_image_fwd(const T* x, const float* w, float* t, long npix, int C, int Ncol, hipStream_t s);
+template <typename T> int wide_to_image_bwd(const float* g, const float* t, const T* x, const float* w, T* gx, float* gw, long npix, int C, int Ncol,
+                                            const float* rn, float slope, hipStream_t s);
+template <typename T> int wide_from_image_dx(const T* g, const float* w, float* gx, int B, int H, int W, int Ncol, int C, int pool, hipStream_t s);
+template <typename T> int wide_from_image_dw(const float* x, const T* g, float* gw, float* gb, int B, int H, int W, int Ncol, int C, int pool,
+                                             hipStream_t s);
+// bilinear x2 adjoint + LeakyReLU -> PixelNorm backward in one pass, fp32 intermediate (bf16 storage; fp32 chains the two operators)
+template <typename T> int wide_up2_adjoint_pnbwd(const T* g, const T* yprev, const float* rn, T* o, int B, int h, int w, int C, float slope,
+                                                 hipStream_t s);
 
 }  // namespace ngan
 

@@ -153,13 +153,12 @@ bool lpp_ok(int C) {
         PN_LAUNCH(KERNEL, 1, __VA_ARGS__);                                                                        \
     } while (0)
 
-// T = float: the fp32 contract of include/ngan.h, with csrc/wide.hip behind it for channel counts outside the lane-group kernels'
-// range; T = __bf16: the bf16-storage entry points (no wide path)
+// T = float: the fp32 contract of include/ngan.h; T = __bf16: the bf16-storage entry points.  csrc/wide.hip is behind both for channel
+// counts outside the lane-group kernels' range
 template <typename T>
 int pn_fwd_impl(const T* c, const float* bias, T* y, float* rnorm, long npix, int C, float slope, float eps, void* stream) {
     NGAN_REQUIRE(c && y && rnorm, NGAN_ERR_ARG, "lrelu_pixelnorm_fwd: null pointer");
-    if constexpr (sizeof(T) == 4)
-        if (npix > 0 && C > 0 && C % 4 == 0 && !lpp_ok(C)) return ngan::wide_pn_fwd(c, bias, y, rnorm, npix, C, slope, eps, (hipStream_t)stream);
+    if (npix > 0 && C > 0 && C % 4 == 0 && !lpp_ok(C)) return ngan::wide_pn_fwd(c, bias, y, rnorm, npix, C, slope, eps, (hipStream_t)stream);
     NGAN_REQUIRE(npix > 0 && lpp_ok(C), NGAN_ERR_SHAPE, "lrelu_pixelnorm_fwd: npix=%ld C=%d unsupported", npix, C);
     PN_DISPATCH(pn_fwd_kernel, c, bias, y, rnorm, npix, C, slope, eps);
     return ngan::launch_status("ngan_lrelu_pixelnorm_fwd");
@@ -168,8 +167,7 @@ int pn_fwd_impl(const T* c, const float* bias, T* y, float* rnorm, long npix, in
 template <typename T>
 int pn_bwd2_impl(const T* gy, const T* gy2, const float* gr, const T* y, const float* rnorm, T* gc, long npix, int C, float slope, void* stream) {
     NGAN_REQUIRE(gy && y && rnorm && gc, NGAN_ERR_ARG, "lrelu_pixelnorm_bwd: null pointer");
-    if constexpr (sizeof(T) == 4)
-        if (npix > 0 && C > 0 && C % 4 == 0 && !lpp_ok(C)) return ngan::wide_pn_bwd(gy, gy2, gr, y, rnorm, gc, npix, C, slope, (hipStream_t)stream);
+    if (npix > 0 && C > 0 && C % 4 == 0 && !lpp_ok(C)) return ngan::wide_pn_bwd(gy, gy2, gr, y, rnorm, gc, npix, C, slope, (hipStream_t)stream);
     NGAN_REQUIRE(npix > 0 && lpp_ok(C), NGAN_ERR_SHAPE, "lrelu_pixelnorm_bwd: npix=%ld C=%d unsupported", npix, C);
     PN_DISPATCH(pn_bwd_kernel, gy, gr, y, rnorm, gc, npix, C, slope, gy2);
     return ngan::launch_status("ngan_lrelu_pixelnorm_bwd");
@@ -179,9 +177,8 @@ template <typename T>
 int pn_bwdbwd_impl(const T* h, const T* gy, const T* y, const float* rnorm, T* ggy, T* gy_out, float* gr_out, long npix, int C, float slope,
                    void* stream) {
     NGAN_REQUIRE(h && gy && y && rnorm && ggy && gy_out && gr_out, NGAN_ERR_ARG, "lrelu_pixelnorm_bwdbwd: null pointer");
-    if constexpr (sizeof(T) == 4)
-        if (npix > 0 && C > 0 && C % 4 == 0 && !lpp_ok(C))
-            return ngan::wide_pn_bwdbwd(h, gy, y, rnorm, ggy, gy_out, gr_out, npix, C, slope, (hipStream_t)stream);
+    if (npix > 0 && C > 0 && C % 4 == 0 && !lpp_ok(C))
+        return ngan::wide_pn_bwdbwd(h, gy, y, rnorm, ggy, gy_out, gr_out, npix, C, slope, (hipStream_t)stream);
     NGAN_REQUIRE(npix > 0 && lpp_ok(C), NGAN_ERR_SHAPE, "lrelu_pixelnorm_bwdbwd: npix=%ld C=%d unsupported", npix, C);
     PN_DISPATCH(pn_bwdbwd_kernel, h, gy, y, rnorm, ggy, gy_out, gr_out, npix, C, slope);
     return ngan::launch_status("ngan_lrelu_pixelnorm_bwdbwd");

@@ -706,7 +706,7 @@ extern "C" int ngan_gp_coef(const float* norms, int B, float lambda, const float
 
 
 // ---- entry points over the activation type: T = float is the fp32 contract of include/ngan.h (csrc/wide.hip behind it for channel counts
-// outside the lane-group kernels' range), T = __bf16 the "bf16 activation storage" section (no wide path: NGAN_ERR_SHAPE instead)
+// outside the lane-group kernels' range), T = __bf16 the "bf16 activation storage" section (the same wide.hip kernels, bf16 storage)
 #define BF(p) reinterpret_cast<const __bf16*>(p)
 #define BFM(p) reinterpret_cast<__bf16*>(p)
 template <typename T> constexpr bool is_f32() { return sizeof(T) == 4; }
@@ -714,11 +714,10 @@ template <typename T> constexpr bool is_f32() { return sizeof(T) == 4; }
 template <typename T>
 static int channel_sum_impl(const T* g, float* out, float* workspace, long npix, int C, float scale, int accumulate, void* stream) {
     NGAN_REQUIRE(g && out && workspace, NGAN_ERR_ARG, "channel_sum: null pointer");
-    if constexpr (is_f32<T>())
-        if (npix > 0 && C > 0 && !pow2_quads(C)) {                                                                                // wide.hip
-            NGAN_REQUIRE(!accumulate, NGAN_ERR_SHAPE, "channel_sum: accumulate is not available for C=%d", C);
-            return ngan::wide_channel_sum(g, out, npix, C, scale, (hipStream_t)stream);
-        }
+    if (npix > 0 && C > 0 && !pow2_quads(C)) {                                                                                // wide.hip
+        NGAN_REQUIRE(!accumulate, NGAN_ERR_SHAPE, "channel_sum: accumulate is not available for C=%d", C);
+        return ngan::wide_channel_sum(g, out, npix, C, scale, (hipStream_t)stream);
+    }
     NGAN_REQUIRE(npix > 0 && pow2_quads(C), NGAN_ERR_SHAPE, "channel_sum: npix=%ld C=%d unsupported", npix, C);
     hipStream_t s = (hipStream_t)stream;
     const int nblk = stream_blocks(npix, C / 4);
@@ -775,9 +774,8 @@ extern "C" int ngan_bf16_from_image_fwd(const float* x, const float* w, const fl
 template <typename T>
 static int from_image_dx_impl(const T* g, const float* w, float* gx, int B, int H, int W, int Ncol, int C, int pool, void* stream) {
     NGAN_REQUIRE(g && w && gx, NGAN_ERR_ARG, "from_image_dx: null pointer");
-    if constexpr (is_f32<T>())
-        if (B > 0 && H > 0 && W > 0 && Ncol >= 1 && Ncol <= 4 && C > 0 && !pow2_quads(C))
-            return ngan::wide_from_image_dx(g, w, gx, B, H, W, Ncol, C, pool, (hipStream_t)stream);                             // wide.hip
+    if (B > 0 && H > 0 && W > 0 && Ncol >= 1 && Ncol <= 4 && C > 0 && !pow2_quads(C))
+        return ngan::wide_from_image_dx(g, w, gx, B, H, W, Ncol, C, pool, (hipStream_t)stream);                             // wide.hip
     NGAN_REQUIRE(B > 0 && H > 0 && W > 0 && Ncol >= 1 && Ncol <= 4 && pow2_quads(C), NGAN_ERR_SHAPE,
                  "from_image_dx: B=%d H=%d W=%d Ncol=%d C=%d unsupported", B, H, W, Ncol, C);
     NGAN_REQUIRE((long)B * H * W * (C / 4) < (1L << 31), NGAN_ERR_SHAPE, "from_image_dx: B*H*W*C/4 must be below 2^31");
@@ -804,11 +802,10 @@ template <typename T>
 static int from_image_dw_impl(const float* x, const T* g, float* gw, float* gb, float* workspace, int B, int H, int W,
                               int Ncol, int C, int pool, int accumulate, void* stream) {
     NGAN_REQUIRE(x && g && gw && workspace, NGAN_ERR_ARG, "from_image_dw: null pointer");
-    if constexpr (is_f32<T>())
-        if (B > 0 && H > 0 && W > 0 && Ncol >= 1 && Ncol <= 4 && C > 0 && !pow2_quads(C)) {
-            NGAN_REQUIRE(!accumulate, NGAN_ERR_SHAPE, "from_image_dw: accumulate is not available for C=%d", C);
-            return ngan::wide_from_image_dw(x, g, gw, gb, B, H, W, Ncol, C, pool, (hipStream_t)stream);                         // wide.hip
-        }
+    if (B > 0 && H > 0 && W > 0 && Ncol >= 1 && Ncol <= 4 && C > 0 && !pow2_quads(C)) {
+        NGAN_REQUIRE(!accumulate, NGAN_ERR_SHAPE, "from_image_dw: accumulate is not available for C=%d", C);
+        return ngan::wide_from_image_dw(x, g, gw, gb, B, H, W, Ncol, C, pool, (hipStream_t)stream);                         // wide.hip
+    }
     NGAN_REQUIRE(B > 0 && H > 0 && W > 0 && Ncol >= 1 && Ncol <= 4 && pow2_quads(C), NGAN_ERR_SHAPE,
                  "from_image_dw: B=%d H=%d W=%d Ncol=%d C=%d unsupported", B, H, W, Ncol, C);
     NGAN_REQUIRE((long)B * H * W * (C / 4) < (1L << 31), NGAN_ERR_SHAPE, "from_image_dw: B*H*W*C/4 must be below 2^31");
@@ -848,9 +845,8 @@ extern "C" int ngan_bf16_from_image_dw(const float* x, const ngan_bf16* g, float
 template <typename T>
 static int to_image_fwd_impl(const T* x, const float* w, float* t, long npix, int C, int Ncol, void* stream) {
     NGAN_REQUIRE(x && w && t, NGAN_ERR_ARG, "to_image_fwd: null pointer");
-    if constexpr (is_f32<T>())
-        if (npix > 0 && Ncol >= 1 && Ncol <= 4 && C > 0 && C % 4 == 0 && !pow2_quads(C))
-            return ngan::wide_to_image_fwd(x, w, t, npix, C, Ncol, (hipStream_t)stream);                                        // wide.hip
+    if (npix > 0 && Ncol >= 1 && Ncol <= 4 && C > 0 && C % 4 == 0 && !pow2_quads(C))
+        return ngan::wide_to_image_fwd(x, w, t, npix, C, Ncol, (hipStream_t)stream);                                        // wide.hip
     NGAN_REQUIRE(npix > 0 && Ncol >= 1 && Ncol <= 4 && pow2_quads(C), NGAN_ERR_SHAPE, "to_image_fwd: npix=%ld C=%d Ncol=%d unsupported",
                  npix, C, Ncol);
     hipStream_t s = (hipStream_t)stream;
@@ -871,11 +867,10 @@ template <typename T>
 static int to_image_bwd_impl(const float* g, const float* t, const T* x, const float* w, T* gx, float* gw,
                              float* workspace, long npix, int C, int Ncol, const float* rn, float slope, int accumulate, void* stream) {
     NGAN_REQUIRE(g && t && x && w && gx && gw && workspace, NGAN_ERR_ARG, "to_image_bwd: null pointer");
-    if constexpr (is_f32<T>())
-        if (npix > 0 && Ncol >= 1 && Ncol <= 4 && C > 0 && C % 4 == 0 && !pow2_quads(C)) {
-            NGAN_REQUIRE(!accumulate, NGAN_ERR_SHAPE, "to_image_bwd: accumulate is not available for C=%d", C);
-            return ngan::wide_to_image_bwd(g, t, x, w, gx, gw, npix, C, Ncol, rn, slope, (hipStream_t)stream);                   // wide.hip
-        }
+    if (npix > 0 && Ncol >= 1 && Ncol <= 4 && C > 0 && C % 4 == 0 && !pow2_quads(C)) {
+        NGAN_REQUIRE(!accumulate, NGAN_ERR_SHAPE, "to_image_bwd: accumulate is not available for C=%d", C);
+        return ngan::wide_to_image_bwd(g, t, x, w, gx, gw, npix, C, Ncol, rn, slope, (hipStream_t)stream);                   // wide.hip
+    }
     NGAN_REQUIRE(npix > 0 && Ncol >= 1 && Ncol <= 4 && pow2_quads(C), NGAN_ERR_SHAPE, "to_image_bwd: npix=%ld C=%d Ncol=%d unsupported",
                  npix, C, Ncol);
     hipStream_t s = (hipStream_t)stream;
@@ -980,7 +975,7 @@ extern "C" int ngan_up2_adjoint_pnbwd(const float* g, const float* yprev, const 
     NGAN_REQUIRE(g && yprev && rnorm && o, NGAN_ERR_ARG, "ngan_up2_adjoint_pnbwd: null pointer");
     if (B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0 && !pow2_quads(C)) {      // wide layers: the two operators one after the other (wide.hip)
         const int st = ngan_up2_adjoint(g, o, B, h, w, C, stream);
-        return st ? st : ngan::wide_pn_bwd(o, nullptr, nullptr, yprev, rnorm, o, (long)B * h * w, C, slope, (hipStream_t)stream);
+        return st ? st : ngan::wide_pn_bwd<float>(o, nullptr, nullptr, yprev, rnorm, o, (long)B * h * w, C, slope, (hipStream_t)stream);
     }
     NGAN_REQUIRE(B > 0 && B < 65536 && h > 0 && w > 0 && pow2_quads(C), NGAN_ERR_SHAPE, "ngan_up2_adjoint_pnbwd: bad dims %d %d %d %d", B, h, w, C);
     return launch_up2_adjoint_strip<float>(g, yprev, rnorm, o, B, h, w, C, slope, (hipStream_t)stream);
@@ -988,6 +983,8 @@ extern "C" int ngan_up2_adjoint_pnbwd(const float* g, const float* yprev, const 
 extern "C" int ngan_bf16_up2_adjoint_pnbwd(const ngan_bf16* g, const ngan_bf16* yprev, const float* rnorm, ngan_bf16* o, int B, int h, int w,
                                            int C, float slope, void* stream) {
     NGAN_REQUIRE(g && yprev && rnorm && o, NGAN_ERR_ARG, "ngan_bf16_up2_adjoint_pnbwd: null pointer");
+    if (B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0 && !pow2_quads(C))      // wide layers: one fused pass, fp32 intermediate (wide.hip)
+        return ngan::wide_up2_adjoint_pnbwd(BF(g), BF(yprev), rnorm, BFM(o), B, h, w, C, slope, (hipStream_t)stream);
     NGAN_REQUIRE(B > 0 && B < 65536 && h > 0 && w > 0 && pow2_quads(C), NGAN_ERR_SHAPE, "ngan_bf16_up2_adjoint_pnbwd: bad dims %d %d %d %d", B, h, w, C);
     return launch_up2_adjoint_strip<__bf16>(BF(g), BF(yprev), rnorm, BFM(o), B, h, w, C, slope, (hipStream_t)stream);
 }

@@ -296,7 +296,8 @@ def _pooled(x):
 def _bf16_prec(b, h, w, k, n, resample):
     """precision code of a conv on bf16 activations: 5, or an error -- there is no fallback from bf16 storage to an fp32-storage kernel"""
     if _C.conv3x3_algorithm(b, h, w, k, n, resample, 5) != 5:
-        raise RuntimeError(f"conv3x3 on bf16 activations takes 16 / 32 / 64 / 128 channels per call, got K={k}, N={n}")
+        raise RuntimeError(f"conv3x3 on bf16 activations takes N = 16 / 32 / 64 / 128 and K a multiple of 16 up to 1024 per call, "
+                           f"got K={k}, N={n}")
     return 5
 
 
