@@ -281,6 +281,23 @@ int ngan_adam_step(float* p, const float* g, float* m, float* v, const long* seg
                    const int* seg_active, float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off,
                    int n_chunks, const float* hyper, int n_hyper, void* stream);
 
+/* ---- RMSprop: optim.RMSprop.step, train.py:220-222 (the reference's RMSprop switch: alpha 0.99, eps 1e-8, no momentum, not centred,
+ * no weight decay) --------------------------------------------------------------------------------------------------------------------
+ * The work list, seg_active and seg_step are those of ngan_adam_step (step counts advance for active tensors; the update reads none).
+ *   v                       square_avg, the one state buffer (fp32, laid out like p)
+ *   hyper                   5 device floats {lr, alpha, eps, grad_scale, 1 - alpha} (1 - alpha rounded from the host's double, as torch
+ *                           forms `value=1 - alpha`); per element  g *= grad_scale;  v = alpha*v + (1 - alpha)*g*g;  p -= lr*g/(sqrt(v) + eps)
+ *   n_hyper                 must equal NGAN_RMSPROP_HYPER_FLOATS
+ * ngan_linear_wgrad_rmsprop: the stem's weight-gradient contraction of ngan_linear_wgrad with this update in its epilogue instead of a
+ * stored gradient (K <= 512, a multiple of 16; any B); p and v are the stem weight's slices of the flat buffers.  Same bits as
+ * ngan_linear_wgrad followed by ngan_rmsprop_step on the stored gradient. */
+#define NGAN_RMSPROP_HYPER_FLOATS 5
+int ngan_rmsprop_step(float* p, const float* g, float* v, const long* seg_off, const long* seg_len, const int* seg_active,
+                      float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off, int n_chunks, const float* hyper,
+                      int n_hyper, void* stream);
+int ngan_linear_wgrad_rmsprop(const float* z, const float* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K, int S,
+                              int C, float scale, void* stream);
+
 /* ---- the critic's first layer pair as one operator (first-order passes): FromImage (ONE colour channel, models.py:161-165) folded
  * into the block's first 3x3 conv + LeakyReLU + PixelNorm (models.py:252-264).  f[c] = wf[c]*p + bf[c] is affine in one number per
  * pixel, so the conv over its C channels is a 3x3 conv over ONE channel with A[n][t] = scale*sum_c W[n][c][t]*wf[c] and a
@@ -320,7 +337,7 @@ int ngan_augment_batch(const float* src, const int* idx, const void* params, flo
  * convolutions multiply bf16 operands with ONE v_mfma_f32_16x16x32_bf16 per product group (the fp32 master weights are rounded to
  * bf16 by the packing kernel, scale folded in first).  What does not: accumulation, PixelNorm statistics and norms (rnorm), biases,
  * LeakyReLU / tanh, the scalar loss heads, images (C = colours: x, x_hat, G(z), dD/dx), latents, every parameter, every parameter
- * gradient and the Adam state are fp32, and those entry points are the ones above.
+ * gradient and the Adam / RMSprop state are fp32, and those entry points are the ones above.
  *
  * Each ngan_bf16_<op> below has the arguments and semantics of ngan_<op> above; the pointers typed ngan_bf16 are the activation
  * tensors.  Channel counts: the 3x3 conv takes N in {16, 32, 64, 128} and any K that is a multiple of 16 up to 1024 -- K in
@@ -390,6 +407,8 @@ int ngan_bf16_linear_wgrad_acc(const float* z, const ngan_bf16* gc, float* gW, i
                                void* stream);
 int ngan_bf16_linear_wgrad_adam(const float* z, const ngan_bf16* gc, float* p, float* m, float* v, const float* seg_step,
                                 const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, void* stream);
+int ngan_bf16_linear_wgrad_rmsprop(const float* z, const ngan_bf16* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K,
+                                   int S, int C, float scale, void* stream);
 int ngan_bf16_linear_dgrad(const ngan_bf16* gc, const float* Wt, float* gz, int B, int K, int S, int C, float scale, void* stream);
 int ngan_bf16_final_dot_fwd(const ngan_bf16* y, const float* W, const float* bias, float* out, int B, int S2, int C, float scale, void* stream);
 int ngan_bf16_final_dot_dx(const float* go, const float* W, ngan_bf16* gy, int B, int S2, int C, float scale, void* stream);

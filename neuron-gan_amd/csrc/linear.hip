@@ -136,14 +136,16 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float* __restri
 // stem exchange forms the full-batch gradient from world*B gathered samples): a wave owns 16 weight rows and all K columns,
 // A = z^T (16 k-columns x 4 samples), B = gc (4 samples x 16 rows), so a lane ends with 4 consecutive k of one row: one
 // 16-byte store.  z (B x K) and gc are tiny and stay in L1/L2; the 4*C*S*K-byte result is written exactly once.
-// ADAM: the gradient is never stored -- the lane applies Adam to its 4 * NT elements of the parameter and its moments (p, m, v are
-// the tensor's slices of the flat buffers; step / hyper as in ngan_adam_step).  The stem holds 16.8 M of the generator's 17.1 M
-// parameters: the stored form costs a 67 MB zero fill, a 67 MB read-modify-write here and a 67 MB read in the Adam kernel.
-struct StemAdam { float* p; float* m; float* v; const float* hyper; const float* step; };
-template <typename T, int NT, bool ADAM = false>
+// RULE: STEM_STORE writes the gradient.  STEM_ADAM / STEM_RMSPROP never store it -- the lane applies the update to its 4 * NT elements
+// of the parameter and its optimiser state (p, m, v are the tensor's slices of the flat buffers, m unused by RMSprop; step / hyper as in
+// ngan_adam_step / ngan_rmsprop_step).  The stem holds 16.8 M of the generator's 17.1 M parameters: the stored form costs a 67 MB zero
+// fill, a 67 MB read-modify-write here and a 67 MB read in the flat optimiser kernel.
+enum StemRule { STEM_STORE = 0, STEM_ADAM = 1, STEM_RMSPROP = 2 };
+struct StemUpdate { float* p; float* m; float* v; const float* hyper; const float* step; };
+template <typename T, int NT, int RULE = STEM_STORE>
 __global__ __launch_bounds__(256) void linear_wgrad_mfma_kernel(const float* __restrict__ z, const T* __restrict__ gc,
                                                                 float* __restrict__ gW, int B, int K, int S, int C, float scale,
-                                                                int accumulate, StemAdam ad = StemAdam{}) {
+                                                                int accumulate, StemUpdate ad = StemUpdate{}) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = lane & 15, kq = lane >> 4;
     const long rows = (long)C * S;
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_mfma_kernel(const float* __r
         for (int t = 0; t < NT; ++t)
             if (t < nt) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(zv[t], gv, acc[t], 0, 0, 0);
     }
-    if (ADAM) {
+    if (RULE == STEM_ADAM) {
         if (rok) {
             const AdamCoef k = adam_coef(ad.hyper, ad.step[0]);
             const long o = row * K + kq * 4;
@@ -179,6 +181,24 @@ __global__ __launch_bounds__(256) void linear_wgrad_mfma_kernel(const float* __r
                     adam_update(k, acc[t][2] * scale, pv.z, mv.z, vv.z);
                     adam_update(k, acc[t][3] * scale, pv.w, mv.w, vv.w);
                     st4(ad.m + o + t * 16, mv);
+                    st4(ad.v + o + t * 16, vv);
+                    st4(ad.p + o + t * 16, pv);
+                }
+        }
+        return;
+    }
+    if (RULE == STEM_RMSPROP) {
+        if (rok) {
+            const RmspropCoef k = rmsprop_coef(ad.hyper);
+            const long o = row * K + kq * 4;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                if (t < nt) {
+                    float4 pv = ld4(ad.p + o + t * 16), vv = ld4(ad.v + o + t * 16);
+                    rmsprop_update(k, acc[t][0] * scale, pv.x, vv.x);
+                    rmsprop_update(k, acc[t][1] * scale, pv.y, vv.y);
+                    rmsprop_update(k, acc[t][2] * scale, pv.z, vv.z);
+                    rmsprop_update(k, acc[t][3] * scale, pv.w, vv.w);
                     st4(ad.v + o + t * 16, vv);
                     st4(ad.p + o + t * 16, pv);
                 }
@@ -365,8 +385,8 @@ static int linear_wgrad_impl(const float* z, const T* gc, float* gW, int B, int 
     const long rows = (long)C * S;
     if (K % 16 == 0 && K <= 512) {
         const dim3 grid(ngan::ceil_div(rows, 64)), block(256);
-        if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, false>), grid, block, 0, (hipStream_t)stream, z, gc, gW, B, K, S, C, scale, accumulate, StemAdam{});
-        else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, false>), grid, block, 0, (hipStream_t)stream, z, gc, gW, B, K, S, C, scale, accumulate, StemAdam{});
+        if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, STEM_STORE>), grid, block, 0, (hipStream_t)stream, z, gc, gW, B, K, S, C, scale, accumulate, StemUpdate{});
+        else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, STEM_STORE>), grid, block, 0, (hipStream_t)stream, z, gc, gW, B, K, S, C, scale, accumulate, StemUpdate{});
         return ngan::launch_status("ngan_linear_wgrad(mfma)");
     }
     const int rpb = rows >= 4096 ? 16 : 4;
@@ -398,9 +418,9 @@ static int linear_wgrad_adam_impl(const float* z, const T* gc, float* p, float* 
     NGAN_REQUIRE(B > 0 && S > 0 && C > 0 && K > 0 && K % 16 == 0 && K <= 512, NGAN_ERR_SHAPE,
                  "linear_wgrad_adam: B=%d K=%d S=%d C=%d unsupported (K a multiple of 16, at most 512)", B, K, S, C);
     const dim3 grid(ngan::ceil_div((long)C * S, 64)), block(256);
-    const StemAdam ad{p, m, v, hyper, seg_step};
-    if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, true>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
-    else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, true>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
+    const StemUpdate ad{p, m, v, hyper, seg_step};
+    if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, STEM_ADAM>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
+    else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, STEM_ADAM>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
     return ngan::launch_status("ngan_linear_wgrad_adam");
 }
 extern "C" int ngan_linear_wgrad_adam(const float* z, const float* gc, float* p, float* m, float* v, const float* seg_step,
@@ -410,6 +430,29 @@ extern "C" int ngan_linear_wgrad_adam(const float* z, const float* gc, float* p,
 extern "C" int ngan_bf16_linear_wgrad_adam(const float* z, const ngan_bf16* gc, float* p, float* m, float* v, const float* seg_step,
                                            const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, void* stream) {
     return linear_wgrad_adam_impl<__bf16>(z, BF(gc), p, m, v, seg_step, hyper, n_hyper, B, K, S, C, scale, stream);
+}
+
+template <typename T>
+static int linear_wgrad_rmsprop_impl(const float* z, const T* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K, int S,
+                                     int C, float scale, void* stream) {
+    NGAN_REQUIRE(z && gc && p && v && hyper, NGAN_ERR_ARG, "linear_wgrad_rmsprop: null pointer");
+    NGAN_REQUIRE(n_hyper == NGAN_RMSPROP_HYPER_FLOATS, NGAN_ERR_ARG,
+                 "linear_wgrad_rmsprop: hyper holds %d floats, this library reads %d (include/ngan.h)", n_hyper, NGAN_RMSPROP_HYPER_FLOATS);
+    NGAN_REQUIRE(B > 0 && S > 0 && C > 0 && K > 0 && K % 16 == 0 && K <= 512, NGAN_ERR_SHAPE,
+                 "linear_wgrad_rmsprop: B=%d K=%d S=%d C=%d unsupported (K a multiple of 16, at most 512)", B, K, S, C);
+    const dim3 grid(ngan::ceil_div((long)C * S, 64)), block(256);
+    const StemUpdate ad{p, nullptr, v, hyper, nullptr};
+    if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, STEM_RMSPROP>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
+    else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, STEM_RMSPROP>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
+    return ngan::launch_status("ngan_linear_wgrad_rmsprop");
+}
+extern "C" int ngan_linear_wgrad_rmsprop(const float* z, const float* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K,
+                                         int S, int C, float scale, void* stream) {
+    return linear_wgrad_rmsprop_impl<float>(z, gc, p, v, hyper, n_hyper, B, K, S, C, scale, stream);
+}
+extern "C" int ngan_bf16_linear_wgrad_rmsprop(const float* z, const ngan_bf16* gc, float* p, float* v, const float* hyper, int n_hyper, int B,
+                                              int K, int S, int C, float scale, void* stream) {
+    return linear_wgrad_rmsprop_impl<__bf16>(z, BF(gc), p, v, hyper, n_hyper, B, K, S, C, scale, stream);
 }
 
 template <typename T>

@@ -82,6 +82,20 @@ __device__ __forceinline__ void adam_update(const AdamCoef& k, float g, float& p
     v = vv;
     p -= k.step_size * (mv / (sqrtf(vv) * k.inv_sqrt_bc2 + k.eps));   // p.addcdiv_(m, sqrt(v)/sqrt(bc2) + eps, -lr/bc1)
 }
+// One element of optim.RMSprop.step (train.py:220-222: alpha 0.99, eps 1e-8, no momentum, not centred, no weight decay), shared by
+// ngan_rmsprop_step (adam.hip) and the stem's RMSprop epilogue (linear.hip) in the same way.  hyper = {lr, alpha, eps, grad_scale,
+// 1 - alpha}, the last rounded from the host's double (torch passes the Python-side `1 - alpha` to addcmul_).  RMSprop keeps a step
+// count too, but its arithmetic does not read it.
+struct RmspropCoef { float lr, alpha, eps, gscale, oma; };
+__device__ __forceinline__ RmspropCoef rmsprop_coef(const float* __restrict__ hyper) {
+    return RmspropCoef{hyper[0], hyper[1], hyper[2], hyper[3], hyper[4]};
+}
+__device__ __forceinline__ void rmsprop_update(const RmspropCoef& k, float g, float& p, float& v) {
+    const float gv = g * k.gscale;                                 // 1/world_size after a SUM exchange, else 1
+    const float vv = fmaf(k.alpha, v, k.oma * gv * gv);           // v.mul_(alpha).addcmul_(g, g, 1 - alpha)
+    v = vv;
+    p -= k.lr * (gv / (sqrtf(vv) + k.eps));                        // p.addcdiv_(g, sqrt(v) + eps, -lr)
+}
 
 // ---- activation storage type (round 4: "bf16" mode, precision code 5 of include/ngan.h) -------------------------------------------
 // Every kernel that reads or writes an ACTIVATION tensor (a conv / stem / FromImage output, or the gradient w.r.t. one) is a template

@@ -25,14 +25,17 @@ from . import _C, ops
 from .loss_functions import D_W_loss, D_grad_pen_loss, G_W_loss
 from .utils import sample_latent_vec, sample_latent_vec_device
 
-ADAM_CHUNK = 4096  # elements per work item of ngan_adam_step (must match csrc/adam.hip)
+ADAM_CHUNK = 4096  # elements per work item of ngan_adam_step / ngan_rmsprop_step (must match csrc/adam.hip)
 SEG_ALIGN = 64     # parameters start on 256-byte boundaries inside the flat buffers
 
 
 class FlatParams:
-    """All parameters of a net as views into one flat buffer (plus flat grad / Adam state buffers)."""
+    """All parameters of a net as views into one flat buffer (plus flat grad / optimiser state buffers).
 
-    def __init__(self, net: torch.nn.Module):
+    state: the names of the optimiser's state buffers to allocate (`FusedAdam.STATE`, the default, or `FusedRMSprop.STATE`); the
+    others are None -- a RMSprop trainer holds no first-moment buffer (70 MB at the default widths)."""
+
+    def __init__(self, net: torch.nn.Module, state=("exp_avg", "exp_avg_sq")):
         self.params = list(net.parameters())
         self.names = [getattr(p, "_ngan_name", n) for n, p in net.named_parameters()]   # stable across growth stages
         assert self.params, "network has no parameters"
@@ -44,8 +47,11 @@ class FlatParams:
         self.offsets, self.total = offs, total
         self.flat = torch.zeros(total, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.exp_avg = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.exp_avg_sq = torch.zeros(total, device=dev, dtype=torch.float32)
+        self.exp_avg = self.exp_avg_sq = self.square_avg = None
+        self.state_names = tuple(state)
+        for name in self.state_names:
+            assert name in ("exp_avg", "exp_avg_sq", "square_avg"), name
+            setattr(self, name, torch.zeros(total, device=dev, dtype=torch.float32))
         for p, off in zip(self.params, offs):
             n = p.numel()
             self.flat[off:off + n].copy_(p.data.reshape(-1))
@@ -83,14 +89,17 @@ class FlatParams:
                 p.grad = self.grad[off:off + p.numel()].view(p.shape)
 
 
-class FusedAdam:
-    """optim.Adam(params, lr, betas=(beta1, 0.999)) semantics of train.py:224-225 in one kernel launch."""
+class _FlatOptimizer:
+    """What FusedAdam and FusedRMSprop share -- the interface the trainer, the epoch driver, the data-parallel path and capture call
+    (param_groups, set_lr, set_grad_scale, step(stem_factors), repack).  Hyper-parameters live in a device tensor, so a captured graph
+    replays with the learning rate of the moment."""
+    KIND = STATE = GRAD_SCALE = None      # set by the subclass: checkpoint kind, FlatParams buffers, index of grad_scale in `hyper`
 
-    def __init__(self, flat: FlatParams, lr=1e-4, betas=(0.5, 0.999), eps=1e-8):
+    def __init__(self, flat: FlatParams, lr, hyper_host):
+        missing = [b for b in self.STATE if getattr(flat, b) is None]
+        assert not missing, f"FlatParams(net, state={self.STATE}) is missing {missing}"
         self.flat = flat
-        # {lr, beta1, beta2, eps, grad_scale, 1 - beta1, 1 - beta2, ln beta1, ln beta2}: include/ngan.h, ngan_adam_step
-        self.hyper_host = [float(lr), float(betas[0]), float(betas[1]), float(eps), 1.0, 1.0 - float(betas[0]), 1.0 - float(betas[1]),
-                           *(math.log(float(b)) if float(b) > 0 else float("-inf") for b in betas)]     # (beta = 0: 1 - 0^t = 1)
+        self.hyper_host = hyper_host
         self.hyper = torch.tensor(self.hyper_host, dtype=torch.float32, device=flat.flat.device)
         self.param_groups = [{"lr": float(lr)}]  # same handle the reference's update_lr() writes to (train.py:253-265)
 
@@ -99,7 +108,7 @@ class FusedAdam:
         self._push()
 
     def set_grad_scale(self, s):
-        self.hyper_host[4] = float(s)
+        self.hyper_host[self.GRAD_SCALE] = float(s)
         self._push()
 
     def _push(self):
@@ -108,8 +117,8 @@ class FusedAdam:
 
     def step(self, stem_factors=None):
         """stem_factors: (z, gc, s2, c, scale) of the generator stem (tensor 0 of the flat buffer) when its gradient was NOT stored
-        (PGGANTrainer.fused_stem): its chunks are left out of the flat launch and `ngan_linear_wgrad_adam` forms the gradient from
-        the factors and applies the same update in its epilogue."""
+        (PGGANTrainer.fused_stem): its chunks are left out of the flat launch and the stem launch (`ngan_linear_wgrad_adam` /
+        `ngan_linear_wgrad_rmsprop`) forms the gradient from the factors and applies the same update in its epilogue."""
         f = self.flat
         if self.hyper_host[0] != self.param_groups[0]["lr"]:
             self._push()
@@ -118,19 +127,57 @@ class FusedAdam:
             assert f.active_host[0] == 1, "the stem is active at every stage"
             n0 = (f.params[0].numel() + ADAM_CHUNK - 1) // ADAM_CHUNK
         n_chunks = int(f.chunk_seg.numel()) - n0
-        _C.call("ngan_adam_step", f.flat, f.grad, f.exp_avg, f.exp_avg_sq, f.seg_off, f.seg_len, f.seg_active, f.seg_step,
-                len(f.params), f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel())      # also advances every active step count
+        self._flat_step(f, n0, n_chunks)                  # also advances every active step count
         if stem_factors is not None:
             z, gc, s2, c, scale = stem_factors
-            n = f.params[0].numel()
-            _C.call(ops._k("ngan_linear_wgrad_adam", gc), z, gc, f.flat[:n], f.exp_avg[:n], f.exp_avg_sq[:n], f.seg_step[:1], self.hyper, self.hyper.numel(),
-                    z.shape[0], z.shape[1], s2, c, float(scale))
+            self._stem_step(f, f.params[0].numel(), z, gc, s2, c, float(scale))
         self.repack()
 
     def repack(self):
         """this net's packed conv weights are stale after a step: re-pack them (and only them -- the other net's copies are still
         valid) with a single launch"""
         ops.refresh_packed(owner=id(self), params=self.flat.params)
+
+
+class FusedAdam(_FlatOptimizer):
+    """optim.Adam(params, lr, betas=(beta1, 0.999)) semantics of train.py:224-225 in one kernel launch."""
+    KIND, STATE, GRAD_SCALE = "adam", ("exp_avg", "exp_avg_sq"), 4
+
+    def __init__(self, flat: FlatParams, lr=1e-4, betas=(0.5, 0.999), eps=1e-8):
+        # {lr, beta1, beta2, eps, grad_scale, 1 - beta1, 1 - beta2, ln beta1, ln beta2}: include/ngan.h, ngan_adam_step
+        super().__init__(flat, lr, [float(lr), float(betas[0]), float(betas[1]), float(eps), 1.0, 1.0 - float(betas[0]),
+                                    1.0 - float(betas[1]),
+                                    *(math.log(float(b)) if float(b) > 0 else float("-inf") for b in betas)])   # (beta = 0: 1 - 0^t = 1)
+
+    def _flat_step(self, f, n0, n_chunks):
+        _C.call("ngan_adam_step", f.flat, f.grad, f.exp_avg, f.exp_avg_sq, f.seg_off, f.seg_len, f.seg_active, f.seg_step,
+                len(f.params), f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel())
+
+    def _stem_step(self, f, n, z, gc, s2, c, scale):
+        _C.call(ops._k("ngan_linear_wgrad_adam", gc), z, gc, f.flat[:n], f.exp_avg[:n], f.exp_avg_sq[:n], f.seg_step[:1], self.hyper,
+                self.hyper.numel(), z.shape[0], z.shape[1], s2, c, scale)
+
+
+class FusedRMSprop(_FlatOptimizer):
+    """optim.RMSprop(params, lr, alpha, eps) semantics of train.py:220-222 -- the reference's RMSprop switch, with torch's defaults
+    alpha 0.99, eps 1e-8, no momentum, not centred, no weight decay -- in one kernel launch (`ngan_rmsprop_step`).  One state buffer,
+    square_avg; per-tensor step counts are kept as torch keeps state['step'], though the update does not read them."""
+    KIND, STATE, GRAD_SCALE = "rmsprop", ("square_avg",), 3
+
+    def __init__(self, flat: FlatParams, lr=1e-4, alpha=0.99, eps=1e-8):
+        # {lr, alpha, eps, grad_scale, 1 - alpha}: include/ngan.h, ngan_rmsprop_step (1 - alpha rounded from the double, as torch)
+        super().__init__(flat, lr, [float(lr), float(alpha), float(eps), 1.0, 1.0 - float(alpha)])
+
+    def _flat_step(self, f, n0, n_chunks):
+        _C.call("ngan_rmsprop_step", f.flat, f.grad, f.square_avg, f.seg_off, f.seg_len, f.seg_active, f.seg_step, len(f.params),
+                f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel())
+
+    def _stem_step(self, f, n, z, gc, s2, c, scale):
+        _C.call(ops._k("ngan_linear_wgrad_rmsprop", gc), z, gc, f.flat[:n], f.square_avg[:n], self.hyper, self.hyper.numel(),
+                z.shape[0], z.shape[1], s2, c, scale)
+
+
+OPTIMIZERS = {"adam": FusedAdam, "rmsprop": FusedRMSprop}
 
 
 def exchange_gradients(flat: FlatParams, world: int, group=None, force: bool = False):
@@ -236,15 +283,27 @@ class PGGANTrainer:
     """One object per process (= per GPU).  `train_iteration(real)` is train.py:356-385 with sim_loss off."""
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
-                 n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None):
+                 n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
+                 rmsprop_alpha=0.99, rmsprop_eps=1e-8):
+        """optimizer: "adam" -- optim.Adam(params, lr, betas=(beta1, 0.999)), the reference's default -- or "rmsprop" --
+        optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps), what the reference's RMSprop switch selects (train.py:220-225);
+        beta1 only matters for Adam"""
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
         self.G, self.D = generator, discriminator
         self.device = next(generator.parameters()).device
         self.n_critic = n_critic
         self.alpha_step = alpha_step
         self.device_latents = device_latents
-        self.flat_g, self.flat_d = FlatParams(generator), FlatParams(discriminator)
-        self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999))
-        self.opt_d = FusedAdam(self.flat_d, learning_rate, (beta1, 0.999))
+        self.optimizer_kind = optimizer
+        opt_cls = OPTIMIZERS[optimizer]
+        self.flat_g, self.flat_d = FlatParams(generator, opt_cls.STATE), FlatParams(discriminator, opt_cls.STATE)
+        if optimizer == "adam":
+            self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999))
+            self.opt_d = FusedAdam(self.flat_d, learning_rate, (beta1, 0.999))
+        else:
+            self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps)
+            self.opt_d = FusedRMSprop(self.flat_d, learning_rate, rmsprop_alpha, rmsprop_eps)
         self.d_loss = D_W_loss(generator, discriminator, drift_epsilon=drift_epsilon, check_nan=False)
         self.gp_loss = D_grad_pen_loss(generator, discriminator, Lambda=grad_pen_lambda)
         self.g_loss = G_W_loss(generator, discriminator, check_nan=False)
@@ -474,35 +533,49 @@ class PGGANTrainer:
 
     # ---- optimiser state for checkpoints (optional extra key; the reference saves none) ---------------------------
     def optimizer_state(self):
-        out = {}
+        """{"kind": "adam" | "rmsprop", "G": ..., "D": ...}: per net the tensor names, lr, per-tensor step counts and, per state buffer of
+        the optimiser (exp_avg + exp_avg_sq, or square_avg), one tensor per name"""
+        out = {"kind": self.optimizer_kind}
         for tag, flat, opt in (("G", self.flat_g, self.opt_g), ("D", self.flat_d, self.opt_d)):
             out[tag] = {"names": list(flat.names), "lr": opt.param_groups[0]["lr"],
-                        "step": flat.seg_step.detach().cpu().clone(),
-                        "exp_avg": {n: flat.exp_avg[o:o + p.numel()].detach().cpu().clone().view(p.shape)
-                                    for n, p, o in zip(flat.names, flat.params, flat.offsets)},
-                        "exp_avg_sq": {n: flat.exp_avg_sq[o:o + p.numel()].detach().cpu().clone().view(p.shape)
-                                       for n, p, o in zip(flat.names, flat.params, flat.offsets)}}
+                        "step": flat.seg_step.detach().cpu().clone()}
+            for buf in opt.STATE:
+                out[tag][buf] = {n: getattr(flat, buf)[o:o + p.numel()].detach().cpu().clone().view(p.shape)
+                                 for n, p, o in zip(flat.names, flat.params, flat.offsets)}
         return out
 
+    def reset_optimizer_state(self):
+        """a fresh optimiser: state buffers and per-tensor step counts back to zero (learning rates stay)"""
+        for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
+            for buf in opt.STATE:
+                getattr(flat, buf).zero_()
+            flat.seg_step.zero_()
+
     def load_optimizer_state(self, state):
+        """state of optimizer_state(); one without "kind" (the checkpoints written before RMSprop existed) is an Adam state.  A state
+        of the other optimiser raises ValueError."""
+        kind = state.get("kind", "adam")
+        if kind != self.optimizer_kind:
+            raise ValueError(f"optimizer state of kind {kind!r} cannot be loaded into a {self.optimizer_kind!r} trainer")
         for tag, flat, opt in (("G", self.flat_g, self.opt_g), ("D", self.flat_d, self.opt_d)):
             st = state[tag]
             saved_step = dict(zip(st["names"], st["step"].tolist()))
             steps = flat.seg_step.detach().cpu().clone()
+            first = st[opt.STATE[0]]
             for i, (n, p, o) in enumerate(zip(flat.names, flat.params, flat.offsets)):
-                if n in st["exp_avg"] and tuple(st["exp_avg"][n].shape) == tuple(p.shape):
-                    flat.exp_avg[o:o + p.numel()].copy_(st["exp_avg"][n].reshape(-1))
-                    flat.exp_avg_sq[o:o + p.numel()].copy_(st["exp_avg_sq"][n].reshape(-1))
+                if n in first and tuple(first[n].shape) == tuple(p.shape):
+                    for buf in opt.STATE:
+                        getattr(flat, buf)[o:o + p.numel()].copy_(st[buf][n].reshape(-1))
                     steps[i] = saved_step.get(n, 0.0)
             flat.seg_step.copy_(steps)
             opt.set_lr(st["lr"])
 
     # ---- HIP-graph capture of a whole iteration ---------------------------------------------------------------
     def _training_state(self):
-        """everything a training iteration changes on the device (parameters, Adam moments and step counts, the device RNG)"""
+        """everything a training iteration changes on the device (parameters, optimiser state and step counts, the device RNG)"""
         bufs = []
-        for flat in (self.flat_g, self.flat_d):
-            bufs += [flat.flat, flat.exp_avg, flat.exp_avg_sq, flat.seg_step]
+        for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
+            bufs += [flat.flat] + [getattr(flat, buf) for buf in opt.STATE] + [flat.seg_step]
         return bufs
 
     def capture(self, real_example, warmup=1, draws=None):
@@ -839,6 +912,22 @@ def build_arg_parser():
     return p
 
 
+def cli_overrides(argv, options, names):
+    """{name: value} of the configuration names given literally on the command line (train.py:95-104): only those override the
+    configuration module or file"""
+    given = [a[2:] for a in argv if a.startswith('--') and a not in ('--configs', '--images')]   # train.py:95
+    return {a: getattr(options, a) for a in given if a in names}
+
+
+def make_trainer(config, G, D):
+    """The trainer `main()` trains with: RMSprop when config.RMSprop is set, else Adam with betas (beta1, 0.999) (train.py:220-225)."""
+    kw = dict(learning_rate=config.learning_rate, grad_pen_lambda=config.grad_pen_lambda, drift_epsilon=config.drift_epsilon,
+              n_critic=config.n_critic, alpha_step=config.alpha_step, device_latents=True)
+    if config.RMSprop:
+        return PGGANTrainer(G, D, optimizer="rmsprop", **kw)
+    return PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
+
+
 def main(argv=None):
     """`python -m neuron_gan_amd.train ...` -- bootstrap of the reference's train.py:94-296, 623-625 for the PGGAN path."""
     import sys
@@ -847,12 +936,11 @@ def main(argv=None):
     from .utils import Checkpointer
     argv = list(sys.argv[1:] if argv is None else argv)
     options = build_arg_parser().parse_args(argv)
-    given = [a[2:] for a in argv if a.startswith('--') and a not in ('--configs', '--images')]   # train.py:95
-    given = [g for g in given if g in config.configs_name]
+    overrides = cli_overrides(argv, options, config.configs_name)
     if options.configs:
-        config.import_configs(options.configs, {a: getattr(options, a) for a in given}, create_dirs=True)
+        config.import_configs(options.configs, overrides, create_dirs=True)
     else:
-        config.set_configs(**{a: getattr(options, a) for a in given})
+        config.set_configs(**overrides)
         config.validate_configs(create_dirs=True)
     if not config.pggan or config.wgan:
         raise NotImplementedError("only the PGGAN path (pggan=True, wgan=False) is implemented")
@@ -880,10 +968,9 @@ def main(argv=None):
     D = models.Discriminator_PG(config.N_dis_features, image_size_init=size_init).to(device)
     filename = os.path.join(config.weights_dir, 'GenDisc_{}.pth'.format(config.ID))         # train.py:196-197
     # the trainer exists before the checkpoint is read, so that `--resume` also restores the optimiser state this implementation
-    # adds to its checkpoints (Adam moments and per-tensor step counts; the reference saves none, utils.py:160-169)
-    trainer = PGGANTrainer(G, D, learning_rate=config.learning_rate, beta1=config.beta1, grad_pen_lambda=config.grad_pen_lambda,
-                           drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, alpha_step=config.alpha_step,
-                           device_latents=True)
+    # adds to its checkpoints (Adam moments or RMSprop square averages, per-tensor step counts; the reference saves none,
+    # utils.py:160-169)
+    trainer = make_trainer(config, G, D)
     checkpoint = Checkpointer(G, D, config.learning_rate, filename, N_epochs=config.N_epochs, device=device, extra_checkpoint_period=1e3,
                               trainer=trainer)
     if config.resume and os.path.exists(filename):

@@ -150,7 +150,13 @@ class Checkpointer:
         if self.trainer is not None:
             self.trainer.refresh_stage()
             if filename is None and 'optimizer_state' in checkpoint_dict:
-                self.trainer.load_optimizer_state(checkpoint_dict['optimizer_state'])
+                saved_kind = checkpoint_dict['optimizer_state'].get('kind', 'adam')     # (checkpoints without a kind are Adam's)
+                if saved_kind == self.trainer.optimizer_kind:
+                    self.trainer.load_optimizer_state(checkpoint_dict['optimizer_state'])
+                else:
+                    # the reference never restores an optimiser (utils.py:213-215): start this one fresh, as it would
+                    self.trainer.reset_optimizer_state()
+                    print('{} holds {} state; the {} optimiser starts fresh'.format(source, saved_kind, self.trainer.optimizer_kind))
         if self.verbose:
             print(('Loaded training state from {}' if filename is None else 'Loaded weights from {}').format(source))
 
