@@ -416,6 +416,65 @@ int ngan_bf16_final_dot_dw(const ngan_bf16* y, const float* go, float* gW, float
 int ngan_bf16_final_dot_dw_acc(const ngan_bf16* y, const float* go, float* gW, float* gb, int B, int S2, int C, float scale, int accumulate,
                                void* stream);
 
+/* ---- weight clipping fused into the optimiser step (the WGAN critic, reference train.py:489-490) ---------------------------------
+ * Arguments as ngan_adam_step / ngan_rmsprop_step, plus clip >= 0: each updated parameter is stored as min(max(p, -clip), clip) --
+ * the same bits as the unclipped step followed by p.clamp_(-clip, clip) (NaN passes through, as with clamp_). */
+int ngan_adam_step_clip(float* p, const float* g, float* m, float* v, const long* seg_off, const long* seg_len,
+                        const int* seg_active, float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off,
+                        int n_chunks, const float* hyper, int n_hyper, float clip, void* stream);
+int ngan_rmsprop_step_clip(float* p, const float* g, float* v, const long* seg_off, const long* seg_len, const int* seg_active,
+                           float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off, int n_chunks, const float* hyper,
+                           int n_hyper, float clip, void* stream);
+
+/* ---- WGAN nets (reference models.py:728-790): 4x4 stride-2 pad-1 convolutions and training-mode BatchNorm2d, exact fp32 ----------
+ * Channels-last fp32 tensors.  W is a torch conv weight [d0][d1][4][4].
+ * ngan_s2_pack: Wp (ngan_s2_packed_floats(M, C) floats) = W in the kernels' order for an M-output, C-input pass:
+ *     up == 0 (down pass): W is [M][C] (a Conv2d weight, or a ConvTranspose2d weight in its input-gradient pass)
+ *     up == 1 (up pass):   W is [C][M] (a ConvTranspose2d weight, or a Conv2d weight in its input-gradient pass)
+ * ngan_s2_conv: up == 0: Conv2d(k4, s2, p1): x (B, Hin, Win, C) -> y (B, Hin/2, Win/2, M); Hin, Win even
+ *               up == 1: ConvTranspose2d(k4, s2, p1): x (B, Hin, Win, C) -> y (B, 2Hin, 2Win, M)
+ *     each input element is read as act(in_scale[c]*x + in_shift[c]) (no affine part when both are null; act = LeakyReLU(slope) when
+ *     in_act != 0) -- BatchNorm -> LeakyReLU on load; zero padding applies after it.  y = conv + bias[m] (bias may be null), then
+ *     tanh when tanh_out != 0.
+ * ngan_s2_wgrad: dW[h][f][ky][kx] = sum_{b,i,j} H(half[b,i,j,h]) * F(full[b, 2i-1+ky, 2j-1+kx, f]), half (B, Hh, Wh, CH),
+ *     full (B, 2Hh, 2Wh, CF), H / F the on-load transforms (scale, shift, act) of each operand; work holds
+ *     ngan_s2_wgrad_workspace_floats(...) floats.  Conv2d: half = output gradient, full = input.  ConvTranspose2d: the reverse.
+ * ngan_bn_stats: batch statistics of y (npix, C): mean, rstd = 1/sqrt(biased var + eps), the on-load transform scale = gamma*rstd,
+ *     shift = beta - mean*scale; run_mean / run_var (may both be null) get the momentum update with the unbiased variance; *nbt += 1
+ *     (nbt may be null).  work: ngan_chan_reduce_workspace_floats(npix, C) floats.
+ * ngan_bn_fold_eval: eval-mode BatchNorm as the on-load transform: scale = gamma/sqrt(run_var + eps), shift = beta - run_mean*scale.
+ * ngan_bn_act_bwd: g is the gradient w.r.t. act(scale*y + shift); writes gy w.r.t. y.  gamma non-null: training-mode BatchNorm
+ *     backward with its batch statistics (mean, rstd); dgamma / dbeta (each may be null) = sum gz*xhat, sum gz.  gamma null: only the
+ *     activation (and the affine part, if scale is given, is treated as constant -- the D's first LeakyReLU passes null).
+ *     work: ngan_bn_act_bwd_workspace_floats(npix, C) floats.
+ * ngan_bn_act_apply: out = act(scale*y + shift) (the critic head's input).  ngan_chan_sum: out[c] = sum over pixels (bias gradients).
+ * ngan_tanh_bwd: out = g * (1 - t*t).
+ * ngan_wgan_stem_fwd: Linear(K -> C*S) with bias, output permuted from NCHW to NHWC: y[b][p][c] = bias[c*S+p] + sum_k z[b][k]*W[c*S+p][k]
+ * ngan_wgan_stem_grad: gW[c*S+p][k] = sum_b g[b][p][c]*z[b][k], gb[c*S+p] = sum_b g[b][p][c] (either may be null).
+ * Every reduction is two-stage in a fixed order (no float atomics): results are bit-reproducible. */
+long ngan_s2_packed_floats(int M, int C);
+int ngan_s2_pack(const float* W, float* Wp, int M, int C, int up, void* stream);
+int ngan_s2_conv(const float* x, const float* Wp, const float* bias, const float* in_scale, const float* in_shift, int in_act, float slope,
+                 float* y, int B, int Hin, int Win, int C, int M, int up, int tanh_out, void* stream);
+long ngan_s2_wgrad_workspace_floats(int B, int Hh, int Wh, int CH, int CF);
+int ngan_s2_wgrad(const float* half, const float* full, const float* h_scale, const float* h_shift, int h_act, const float* f_scale,
+                  const float* f_shift, int f_act, float slope, float* dW, float* work, int B, int Hh, int Wh, int CH, int CF, void* stream);
+long ngan_chan_reduce_workspace_floats(long npix, int C);
+long ngan_bn_act_bwd_workspace_floats(long npix, int C);
+int ngan_bn_stats(const float* y, long npix, int C, const float* gamma, const float* beta, float* mean, float* rstd, float* scale,
+                  float* shift, float* run_mean, float* run_var, long long* nbt, float momentum, float eps, float* work, void* stream);
+int ngan_bn_fold_eval(const float* gamma, const float* beta, const float* run_mean, const float* run_var, float eps, float* scale,
+                      float* shift, int C, void* stream);
+int ngan_bn_act_bwd(const float* y, const float* g, const float* scale, const float* shift, const float* mean, const float* rstd,
+                    const float* gamma, int act, float slope, long npix, int C, float* gy, float* dgamma, float* dbeta, float* work,
+                    void* stream);
+int ngan_bn_act_apply(const float* y, const float* scale, const float* shift, int act, float slope, long npix, int C, float* out,
+                      void* stream);
+int ngan_chan_sum(const float* g, long npix, int C, float* out, float* work, void* stream);
+int ngan_tanh_bwd(const float* t, const float* g, float* out, long n, void* stream);
+int ngan_wgan_stem_fwd(const float* z, const float* W, const float* bias, float* y, int B, int K, int S, int C, void* stream);
+int ngan_wgan_stem_grad(const float* z, const float* g, float* gW, float* gb, int B, int K, int S, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,20 @@ SIGNATURES = {
     "ngan_first_block_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P],
     "ngan_first_block_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "ngan_first_block_dx": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    # the WGAN nets (include/ngan.h, last section)
+    "ngan_adam_step_clip": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _F, _P],
+    "ngan_rmsprop_step_clip": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _F, _P],
+    "ngan_s2_pack": [_P, _P, _I, _I, _I, _P],
+    "ngan_s2_conv": [_P, _P, _P, _P, _P, _I, _F, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "ngan_s2_wgrad": [_P, _P, _P, _P, _I, _P, _P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _P],
+    "ngan_bn_stats": [_P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P],
+    "ngan_bn_fold_eval": [_P, _P, _P, _P, _F, _P, _P, _I, _P],
+    "ngan_bn_act_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _F, _L, _I, _P, _P, _P, _P, _P],
+    "ngan_bn_act_apply": [_P, _P, _P, _I, _F, _L, _I, _P, _P],
+    "ngan_chan_sum": [_P, _L, _I, _P, _P, _P],
+    "ngan_tanh_bwd": [_P, _P, _P, _L, _P],
+    "ngan_wgan_stem_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ngan_wgan_stem_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -96,6 +110,10 @@ NON_STATUS = {
     "ngan_conv3x3_packed_floats": ([_I, _I, _I], _L),
     "ngan_conv3x3_pack_elements": ([_I, _I, _I, _I], _L),
     "ngan_conv3x3_wgrad_plan": ([_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)], _I),
+    "ngan_s2_packed_floats": ([_I, _I], _L),
+    "ngan_s2_wgrad_workspace_floats": ([_I, _I, _I, _I, _I], _L),
+    "ngan_chan_reduce_workspace_floats": ([_L, _I], _L),
+    "ngan_bn_act_bwd_workspace_floats": ([_L, _I], _L),
 }
 
 _lib = None

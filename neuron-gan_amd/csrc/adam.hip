@@ -4,6 +4,8 @@
 // Per-tensor step counts are kept because a progressively grown net activates tensors at different times:
 // torch skips parameters whose .grad is None, so their bias correction starts when they first receive one.
 // Hyper-parameters and step counts live in device memory so a captured graph replays with fresh values.
+// ngan_adam_step_clip / ngan_rmsprop_step_clip (the WGAN critic's weight clipping, reference train.py:489-490) clamp each updated
+// parameter to [-clip, clip] before it is stored: the same bits as the unclipped step followed by p.clamp_(-clip, clip).
 // ngan_rmsprop_step is the same launch pair for optim.RMSprop.step (train.py:220-222, the reference's --RMSprop switch): one state
 // buffer (square_avg) instead of two, same work list, same per-tensor step counts (torch keeps state['step'] for RMSprop too).
 #include "ngan_common.h"
@@ -17,11 +19,15 @@ __global__ void adam_advance_kernel(const int* __restrict__ active, float* __res
 
 constexpr int CHUNK = 4096;
 
+// clamp_(-c, c) as torch forms it: min(max(p, -c), c) with NaN passed through
+__device__ __forceinline__ float clamp_sym(float p, float c) { return p < -c ? -c : (p > c ? c : p); }
+
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, const long* __restrict__ seg_off,
                                                    const long* __restrict__ seg_len, const int* __restrict__ seg_active,
                                                    const float* __restrict__ seg_step, const int* __restrict__ chunk_seg,
-                                                   const long* __restrict__ chunk_off, const float* __restrict__ hyper) {
+                                                   const long* __restrict__ chunk_off, const float* __restrict__ hyper, float clip) {
     const int seg = chunk_seg[blockIdx.x];
     if (!seg_active[seg]) return;
     const AdamCoef k = adam_coef(hyper, seg_step[seg]);
@@ -34,14 +40,15 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         adam_update(k, g[j], pv, mv, vv);
         m[j] = mv;
         v[j] = vv;
-        p[j] = pv;
+        p[j] = CLIP ? clamp_sym(pv, clip) : pv;
     }
 }
 
+template <bool CLIP>
 __global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v,
                                                       const long* __restrict__ seg_off, const long* __restrict__ seg_len,
                                                       const int* __restrict__ seg_active, const int* __restrict__ chunk_seg,
-                                                      const long* __restrict__ chunk_off, const float* __restrict__ hyper) {
+                                                      const long* __restrict__ chunk_off, const float* __restrict__ hyper, float clip) {
     const int seg = chunk_seg[blockIdx.x];
     if (!seg_active[seg]) return;
     const RmspropCoef k = rmsprop_coef(hyper);
@@ -53,7 +60,7 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ p, con
         float pv = p[j], vv = v[j];
         rmsprop_update(k, g[j], pv, vv);
         v[j] = vv;
-        p[j] = pv;
+        p[j] = CLIP ? clamp_sym(pv, clip) : pv;
     }
 }
 
@@ -71,8 +78,8 @@ extern "C" int ngan_adam_step(float* p, const float* g, float* m, float* v, cons
     hipLaunchKernelGGL(adam_advance_kernel, dim3(ngan::ceil_div(n_seg, 256)), dim3(256), 0, s, seg_active, seg_step, n_seg);
     int st = ngan::launch_status("ngan_adam_step(advance)");
     if (st) return st;
-    hipLaunchKernelGGL(adam_kernel, dim3(n_chunks), dim3(256), 0, s, p, g, m, v, seg_off, seg_len, seg_active, seg_step,
-                       chunk_seg, chunk_off, hyper);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(n_chunks), dim3(256), 0, s, p, g, m, v, seg_off, seg_len, seg_active, seg_step,
+                       chunk_seg, chunk_off, hyper, 0.f);
     return ngan::launch_status("ngan_adam_step");
 }
 
@@ -88,7 +95,43 @@ extern "C" int ngan_rmsprop_step(float* p, const float* g, float* v, const long*
     hipLaunchKernelGGL(adam_advance_kernel, dim3(ngan::ceil_div(n_seg, 256)), dim3(256), 0, s, seg_active, seg_step, n_seg);
     int st = ngan::launch_status("ngan_rmsprop_step(advance)");
     if (st) return st;
-    hipLaunchKernelGGL(rmsprop_kernel, dim3(n_chunks), dim3(256), 0, s, p, g, v, seg_off, seg_len, seg_active, chunk_seg, chunk_off,
-                       hyper);
+    hipLaunchKernelGGL(rmsprop_kernel<false>, dim3(n_chunks), dim3(256), 0, s, p, g, v, seg_off, seg_len, seg_active, chunk_seg, chunk_off,
+                       hyper, 0.f);
     return ngan::launch_status("ngan_rmsprop_step");
+}
+
+extern "C" int ngan_adam_step_clip(float* p, const float* g, float* m, float* v, const long* seg_off, const long* seg_len,
+                                   const int* seg_active, float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off,
+                                   int n_chunks, const float* hyper, int n_hyper, float clip, void* stream) {
+    NGAN_REQUIRE(p && g && m && v && seg_off && seg_len && seg_active && seg_step && chunk_seg && chunk_off && hyper,
+                 NGAN_ERR_ARG, "adam_step_clip: null pointer");
+    NGAN_REQUIRE(n_hyper == NGAN_ADAM_HYPER_FLOATS, NGAN_ERR_ARG, "adam_step_clip: hyper holds %d floats, this library reads %d (include/ngan.h)",
+                 n_hyper, NGAN_ADAM_HYPER_FLOATS);
+    NGAN_REQUIRE(n_seg > 0 && n_chunks > 0, NGAN_ERR_SHAPE, "adam_step_clip: n_seg=%d n_chunks=%d", n_seg, n_chunks);
+    NGAN_REQUIRE(clip >= 0.f, NGAN_ERR_ARG, "adam_step_clip: clip=%g", clip);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(ngan::ceil_div(n_seg, 256)), dim3(256), 0, s, seg_active, seg_step, n_seg);
+    int st = ngan::launch_status("ngan_adam_step_clip(advance)");
+    if (st) return st;
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(n_chunks), dim3(256), 0, s, p, g, m, v, seg_off, seg_len, seg_active, seg_step,
+                       chunk_seg, chunk_off, hyper, clip);
+    return ngan::launch_status("ngan_adam_step_clip");
+}
+
+extern "C" int ngan_rmsprop_step_clip(float* p, const float* g, float* v, const long* seg_off, const long* seg_len, const int* seg_active,
+                                      float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off, int n_chunks,
+                                      const float* hyper, int n_hyper, float clip, void* stream) {
+    NGAN_REQUIRE(p && g && v && seg_off && seg_len && seg_active && seg_step && chunk_seg && chunk_off && hyper,
+                 NGAN_ERR_ARG, "rmsprop_step_clip: null pointer");
+    NGAN_REQUIRE(n_hyper == NGAN_RMSPROP_HYPER_FLOATS, NGAN_ERR_ARG,
+                 "rmsprop_step_clip: hyper holds %d floats, this library reads %d (include/ngan.h)", n_hyper, NGAN_RMSPROP_HYPER_FLOATS);
+    NGAN_REQUIRE(n_seg > 0 && n_chunks > 0, NGAN_ERR_SHAPE, "rmsprop_step_clip: n_seg=%d n_chunks=%d", n_seg, n_chunks);
+    NGAN_REQUIRE(clip >= 0.f, NGAN_ERR_ARG, "rmsprop_step_clip: clip=%g", clip);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(ngan::ceil_div(n_seg, 256)), dim3(256), 0, s, seg_active, seg_step, n_seg);
+    int st = ngan::launch_status("ngan_rmsprop_step_clip(advance)");
+    if (st) return st;
+    hipLaunchKernelGGL(rmsprop_kernel<true>, dim3(n_chunks), dim3(256), 0, s, p, g, v, seg_off, seg_len, seg_active, chunk_seg, chunk_off,
+                       hyper, clip);
+    return ngan::launch_status("ngan_rmsprop_step_clip");
 }

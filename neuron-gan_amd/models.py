@@ -21,7 +21,7 @@ import torch.nn as nn
 from . import ops
 from .configs import config
 
-__all__ = ['Generator_PG', 'Discriminator_PG']
+__all__ = ['Generator_PG', 'Discriminator_PG', 'Generator_wgan', 'Discriminator_wgan']
 
 latent_dim_default = config.latent_dim
 image_size_default = config.image_size
@@ -678,3 +678,91 @@ class Discriminator_PG(_ProgressiveNet):
         if verbose:
             print('Loaded training state from {}'.format(filename))
         return obj
+
+
+# =====================================================================================================================
+# Wasserstein GAN nets (reference models.py:728-790): 4x4 stride-2 convolutions with BatchNorm2d, run on wgan_ops.
+# `self.layers` is the reference's nn.Sequential of stock torch modules, so state_dict keys, shapes, buffers and the RNG draws of
+# construction are the reference's; forward walks it and issues the stride-2 kernels on channels-last tensors instead.
+# =====================================================================================================================
+WGAN_SLOPE = 0.2    # the reference's literal LeakyReLU slope in both nets (not config.LeakyReLU_leak)
+
+
+class Generator_wgan(nn.Module):
+
+    def __init__(self, N_features, latent_dim=latent_dim_default, image_size=image_size_default,
+                 N_colors=N_colors_default):
+        super(Generator_wgan, self).__init__()
+        self.latent_dim = latent_dim
+        N_layers = len(N_features)
+        Image_size_init = image_size // (2 ** N_layers)
+        self.image_size_init, self.N_colors = Image_size_init, N_colors
+        layers = list()
+        layers.append(nn.Linear(latent_dim, N_features[0] * Image_size_init ** 2))
+        layers.append(nn.Unflatten(dim=1, unflattened_size=(N_features[0], Image_size_init, Image_size_init)))
+        layers.append(nn.BatchNorm2d(N_features[0]))
+        layers.append(nn.LeakyReLU(negative_slope=0.2, inplace=True))
+        for i in range(N_layers - 1):
+            layers.append(nn.ConvTranspose2d(N_features[i], N_features[i + 1], kernel_size=4, stride=2, padding=1))
+            layers.append(nn.BatchNorm2d(N_features[i + 1]))
+            layers.append(nn.LeakyReLU(negative_slope=0.2, inplace=True))
+        layers.append(nn.ConvTranspose2d(N_features[-1], N_colors, kernel_size=4, stride=2, padding=1))
+        layers.append(nn.Tanh())
+        self.layers = nn.Sequential(*layers)
+
+    def forward_nhwc(self, z):
+        """latents (B, latent_dim) -> images (B, H, W, N_colors), channels-last"""
+        from . import wgan_ops as W
+        L = list(self.layers)
+        lin, bn = L[0], L[2]
+        y = W.Stem.apply(z, lin.weight, lin.bias, self.image_size_init, bn.num_features)
+        i = 4
+        while i < len(L):
+            ct = L[i]
+            last = i + 1 < len(L) and isinstance(L[i + 1], nn.Tanh)
+            y = W.S2Conv.apply(y, bn.weight, bn.bias, ct.weight, ct.bias, W.BNSpec(bn), True, WGAN_SLOPE, True, last)
+            if last:
+                break
+            bn = L[i + 1]
+            i += 3
+        return y
+
+    def forward(self, x):
+        return self.forward_nhwc(x).permute(0, 3, 1, 2)       # NCHW view of the channels-last images
+
+
+class Discriminator_wgan(nn.Module):
+    def __init__(self, N_features, image_size=image_size_default, N_colors=N_colors_default):
+        super(Discriminator_wgan, self).__init__()
+        Layers = list()
+        N_layers = len(N_features)
+        Layers.append(nn.Conv2d(N_colors, N_features[0], kernel_size=4, stride=2, padding=1))
+        Layers.append(nn.LeakyReLU(negative_slope=0.2, inplace=True))
+        for i in range(N_layers - 1):
+            Layers.append(nn.Conv2d(N_features[i], N_features[i + 1], kernel_size=4, stride=2, padding=1))
+            Layers.append(nn.BatchNorm2d(N_features[i + 1]))
+            Layers.append(nn.LeakyReLU(negative_slope=0.2, inplace=True))
+        Image_size_final = image_size // (2 ** N_layers)
+        Layers.append(nn.Flatten())
+        Layers.append(nn.Linear(N_features[-1] * Image_size_final ** 2, 1))
+        self.layers = nn.Sequential(*Layers)
+
+    def forward_nhwc(self, x):
+        """images (B, H, W, N_colors), channels-last -> scores (B, 1)"""
+        from . import wgan_ops as W
+        L = list(self.layers)
+        y = W.S2Conv.apply(x, None, None, L[0].weight, L[0].bias, None, False, WGAN_SLOPE, False, False)
+        bn = None                      # what sits between y and its consumer: LeakyReLU only after the first conv
+        i = 2
+        while isinstance(L[i], nn.Conv2d):
+            gamma, beta = (bn.weight, bn.bias) if bn is not None else (None, None)
+            y = W.S2Conv.apply(y, gamma, beta, L[i].weight, L[i].bias, W.BNSpec(bn) if bn is not None else None, True, WGAN_SLOPE,
+                               False, False)
+            bn = L[i + 1]
+            i += 3
+        head = L[i + 1]
+        gamma, beta = (bn.weight, bn.bias) if bn is not None else (None, None)
+        return W.BNActHead.apply(y, gamma, beta, head.weight, head.bias, W.BNSpec(bn) if bn is not None else None, WGAN_SLOPE)
+
+    def forward(self, x):
+        return self.forward_nhwc(to_nhwc(x).contiguous())

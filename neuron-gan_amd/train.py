@@ -732,6 +732,210 @@ class PGGANTrainer:
         return self.train_iteration(real)
 
 
+class _ClipMixin:
+    """weight clipping fused into the flat optimiser launch (ngan_adam_step_clip / ngan_rmsprop_step_clip): the same bits as the
+    unclipped step followed by p.clamp_(-clip, clip) on every parameter (reference train.py:489-490)"""
+    clip = 0.01
+
+
+class ClippedFusedAdam(_ClipMixin, FusedAdam):
+    def _flat_step(self, f, n0, n_chunks):
+        _C.call("ngan_adam_step_clip", f.flat, f.grad, f.exp_avg, f.exp_avg_sq, f.seg_off, f.seg_len, f.seg_active, f.seg_step,
+                len(f.params), f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel(), float(self.clip))
+
+
+class ClippedFusedRMSprop(_ClipMixin, FusedRMSprop):
+    def _flat_step(self, f, n0, n_chunks):
+        _C.call("ngan_rmsprop_step_clip", f.flat, f.grad, f.square_avg, f.seg_off, f.seg_len, f.seg_active, f.seg_step, len(f.params),
+                f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel(), float(self.clip))
+
+
+class WGANTrainer:
+    """The reference's WGAN loop (train.py:470-506) for Generator_wgan / Discriminator_wgan: n_critic x [D(real), D(G(z).detach()),
+    -mean + mean + drift * mean(real^2), backward, optimiser step, clamp every critic parameter to +-clip], then one generator step
+    -mean(D(G(z))).  Both nets stay in train mode, so every forward uses batch statistics and updates the BatchNorm running buffers,
+    as in the reference.  The critic's parameter gradients of the generator step are not computed.  The clamp is fused into the
+    critic's optimiser launch.  Same interface as PGGANTrainer: step / train_iteration / capture / replay, opt_d / opt_g, last_z_g."""
+
+    def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, drift_epsilon=0.001, n_critic=1, clip=0.01,
+                 optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None):
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
+        world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
+        if world > 1:
+            raise NotImplementedError("WGANTrainer runs on one GPU: BatchNorm batch statistics per rank would differ from the reference's "
+                                      "(synchronised BatchNorm is not implemented)")
+        if ops.get_conv_precision() != "f32":
+            raise NotImplementedError(f"the WGAN nets run in exact fp32 only; conv precision is {ops.get_conv_precision()!r} "
+                                      f"(ops.set_conv_precision('f32'))")
+        self.G, self.D = generator, discriminator
+        self.device = next(generator.parameters()).device
+        self.n_critic = int(n_critic)
+        self.drift_epsilon = float(drift_epsilon)
+        self.device_latents = device_latents
+        self.optimizer_kind = optimizer
+        self.world = 1
+        opt_cls = OPTIMIZERS[optimizer]
+        self.flat_g, self.flat_d = FlatParams(generator, opt_cls.STATE), FlatParams(discriminator, opt_cls.STATE)
+        self.flat_g.set_active(self.flat_g.params)
+        self.flat_d.set_active(self.flat_d.params)
+        if optimizer == "adam":
+            self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999))
+            self.opt_d = ClippedFusedAdam(self.flat_d, learning_rate, (beta1, 0.999))
+        else:
+            self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps)
+            self.opt_d = ClippedFusedRMSprop(self.flat_d, learning_rate, rmsprop_alpha, rmsprop_eps)
+        self.opt_d.clip = float(clip)
+        self.last_z_g = None
+        self._one = torch.ones((), device=self.device)
+        self._graphs = {}
+        self._graph = self._entry = None
+
+    def _latent(self, batch, z):
+        if z is not None:
+            return z
+        if self.device_latents:
+            return sample_latent_vec_device((batch, self.G.latent_dim), self.device)
+        return sample_latent_vec((batch, self.G.latent_dim), device=self.device)
+
+    def _bn_buffers(self):
+        return [b for net in (self.G, self.D) for b in net.buffers()]
+
+    def d_compute(self, real, z=None):
+        """D_W_loss (loss_functions.py:14-45) and its backward: gradients end up in flat_d.grad"""
+        b = real.size(0)
+        self.flat_d.ensure_grad_views()
+        self.flat_d.zero_grad()
+        s_real_all = self.D(real)                                    # D(real), then the latent draw, G(z).detach(), D(fake)
+        z = self._latent(b, z)
+        with torch.no_grad():
+            fake = self.G.forward_nhwc(z)
+        s_fake_all = self.D.forward_nhwc(fake)
+        loss, s_real, s_fake = ops.WLossHead.apply(torch.cat([s_real_all, s_fake_all], dim=0), b, self.drift_epsilon)
+        loss.backward(gradient=self._one)
+        return {"D_loss": loss.detach(), "score_real": s_real.detach(), "score_fake": s_fake.detach()}
+
+    def d_step(self, real, z=None):
+        stats = self.d_compute(real, z)
+        self.opt_d.step()                                            # + clamp_(-clip, clip) in the same launch
+        return stats
+
+    def g_compute(self, real, z=None):
+        b = real.size(0)
+        self.flat_g.ensure_grad_views()
+        self.flat_g.zero_grad()
+        d_params = self.flat_d.params
+        for p in d_params:
+            p.requires_grad_(False)
+        try:
+            z = self._latent(b, z)
+            self.last_z_g = z
+            loss = ops.WLossHead.apply(self.D.forward_nhwc(self.G.forward_nhwc(z)), b, 0.0)[0]
+            loss.backward(gradient=self._one)
+        finally:
+            for p in d_params:
+                p.requires_grad_(True)
+        return {"G_loss": loss.detach()}
+
+    def g_step(self, real, z=None):
+        stats = self.g_compute(real, z)
+        self.opt_g.step()
+        return stats
+
+    def train_iteration(self, real, z_d=None, z_g=None):
+        """z_d: None, one latent batch (used by every critic step) or a sequence of n_critic batches"""
+        stats = {}
+        for i in range(self.n_critic):
+            z = z_d[i] if isinstance(z_d, (list, tuple)) else z_d
+            stats.update(self.d_step(real, z))
+        if self.n_critic == 0:
+            stats.update(self.d_compute(real, z_d[0] if isinstance(z_d, (list, tuple)) else z_d))
+        stats.update(self.g_step(real, z_g))
+        return stats
+
+    def set_lr(self, lr):
+        self.opt_d.set_lr(lr)
+        self.opt_g.set_lr(lr)
+
+    def refresh_stage(self):
+        """after parameters were loaded (Checkpointer): captured graphs are kept (they read the same buffers), nothing to re-mark"""
+        self.flat_g.set_active(self.flat_g.params)
+        self.flat_d.set_active(self.flat_d.params)
+
+    # ---- optimiser state for checkpoints: the same layout as PGGANTrainer's ----------------------------------------
+    optimizer_state = PGGANTrainer.optimizer_state
+    reset_optimizer_state = PGGANTrainer.reset_optimizer_state
+    load_optimizer_state = PGGANTrainer.load_optimizer_state
+
+    def _training_state(self):
+        bufs = []
+        for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
+            bufs += [flat.flat] + [getattr(flat, buf) for buf in opt.STATE] + [flat.seg_step]
+        return bufs + self._bn_buffers()
+
+    def capture(self, real_example, warmup=1, draws=None):
+        """Capture one train_iteration for this batch shape into a graph (PGGANTrainer.capture without the data-parallel segments).
+        The warm-up runs on a snapshot (parameters, optimiser state, BatchNorm buffers, the device RNG are restored).
+        draws: optional {"z_d": [n_critic static tensors] or one, "z_g": static tensor}, refilled by the caller before each replay."""
+        if draws is None and not self.device_latents:
+            raise RuntimeError("graph capture needs device_latents=True or static draws (CPU-drawn latents cannot be replayed)")
+        dr = draws or {}
+        z_d, z_g = dr.get("z_d"), dr.get("z_g")
+        static_real = real_example.clone()
+        state = self._training_state()
+        saved = [t.clone() for t in state]
+        rng = torch.cuda.get_rng_state(self.device)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                self.train_iteration(static_real, z_d, z_g)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        del saved
+        torch.cuda.set_rng_state(rng, self.device)
+        torch.cuda.synchronize()
+        import gc
+        gc.collect()
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                stats = self.train_iteration(static_real, z_d, z_g)
+        finally:
+            if gc_was_enabled:
+                gc.enable()
+        self._graph, self._entry = graph, (graph, static_real, stats)
+        self._graphs[tuple(real_example.shape)] = self._entry
+        return graph
+
+    def has_graph(self, shape):
+        return tuple(shape) in self._graphs
+
+    def replay(self, real=None):
+        if real is not None:
+            entry = self._graphs.get(tuple(real.shape))
+            if entry is None:
+                raise RuntimeError(f"no graph captured for input shape {tuple(real.shape)}: call capture() first")
+            entry[1].copy_(real, non_blocking=True)
+        else:
+            if self._graph is None:
+                raise RuntimeError("call capture() first")
+            entry = self._entry
+        entry[0].replay()
+        return entry[2]
+
+    def step(self, real, use_graph=True):
+        if use_graph and self.device_latents:
+            if not self.has_graph(real.shape):
+                self.capture(real)
+            return self.replay(real)
+        return self.train_iteration(real)
+
+
 # =====================================================================================================================
 # Epoch-level driver and command line (SURVEY.md 8f-2): the reference's train.py as functions instead of module-level code.
 # Out of scope and therefore absent: the PNG dataset with PIL/skimage augmentations (data/NeuronDataset.py), score plots,
@@ -871,6 +1075,84 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     return series
 
 
+def wgan_critic_steps(score_real, score_fake, n_critic, period=10):
+    """adapt_critic on the WGAN path: Calculate_D_steps(Score_real_series, Score_fake_series, 1, n_critic, 10) (reference train.py:466)
+    over the per-epoch series so far.  (The reference passes its preallocated numpy series and raises there, utils.py:110.)  Fewer than
+    two epochs, or no gap between the series (the ratio is then undefined), give n_critic."""
+    from .utils import Calculate_D_steps
+    real, fake = list(score_real)[-period:], list(score_fake)[-period:]
+    if len(real) < 2 or len(fake) < 2:
+        return n_critic
+    gap = float(np.mean(np.abs(np.subtract(fake, real))))
+    if not math.isfinite(gap) or gap == 0.0:
+        return n_critic
+    return Calculate_D_steps(real, fake, 1, n_critic, period)
+
+
+def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print, samples_dir=None,
+               eval_noise=None):
+    """The reference's WGAN epoch loop (train.py:454-536): per epoch the SUMS over its batches of score_real, score_fake, D_loss and
+    G_loss (printed every epoch, stored in the checkpoint's series); at the checkpoint period `save_state` and a 16-image grid from G in
+    eval mode on `eval_noise` (drawn once at start-up, train.py:269).  adapt_critic: `wgan_critic_steps` over the series so far.
+    sim_loss_lambda > 0: similarity_loss(images, latents) is added to the monitored G_loss (train.py:493-496; it depends on neither
+    network, so it changes no gradient).  Returns the per-epoch sums."""
+    from .utils import plot_gen_samples, similarity_loss
+    G = trainer.G
+    device = trainer.device
+    if epoch_final is None:
+        epoch_final = cfg.N_epochs + 1
+    if eval_noise is None:
+        eval_noise = sample_latent_vec((16, G.latent_dim), device=device)
+    sim_lambda = float(getattr(cfg, 'sim_loss_lambda', 0.0) or 0.0)
+    n_images = len(dataset)
+    n_critic_max = trainer.n_critic
+    names = ("score_real", "score_fake", "D_loss", "G_loss")
+    history = []
+    if checkpoint is not None and epoch_init > 1:       # a resumed run continues the series it saved
+        past = [dict(zip(names, v)) for v in zip(checkpoint.Loss_real[:epoch_init - 1], checkpoint.Loss_fake[:epoch_init - 1],
+                                                 checkpoint.Loss_D[:epoch_init - 1], checkpoint.Loss_G[:epoch_init - 1])]
+    else:
+        past = []
+    try:
+        for epoch in range(epoch_init, epoch_final):
+            if getattr(cfg, 'adapt_critic', False):
+                seen = past + history
+                trainer.n_critic = wgan_critic_steps([h["score_real"] for h in seen], [h["score_fake"] for h in seen], n_critic_max)
+            acc = torch.zeros(len(names), device=device)
+            order = torch.randperm(n_images).tolist()                 # DataLoader(shuffle=True), train.py:153
+            for i in range(0, n_images, cfg.batch_size):
+                if hasattr(dataset, "batch"):                      # device dataset: one augmentation launch per batch (data.py)
+                    images = dataset.batch(order[i:i + cfg.batch_size])
+                else:
+                    images = torch.stack([dataset[j] for j in order[i:i + cfg.batch_size]]).to(device)
+                images = images.float()
+                stats = trainer.step(images, use_graph=use_graph and trainer.n_critic == n_critic_max)
+                g_loss = stats["G_loss"]
+                if sim_lambda > 0:
+                    g_loss = g_loss + similarity_loss(images, trainer.last_z_g, sim_lambda)
+                acc += torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss])   # sums, one read per epoch
+            vals = acc.tolist()
+            if any(math.isnan(v) for v in vals):
+                raise ValueError('loss is nan at epoch {}'.format(epoch))
+            sums = dict(zip(names, vals))
+            history.append(sums)
+            if checkpoint is not None and epoch - 1 < len(checkpoint.Loss_real):
+                i = epoch - 1
+                checkpoint.Loss_real[i], checkpoint.Loss_fake[i] = sums["score_real"], sums["score_fake"]
+                checkpoint.Loss_D[i], checkpoint.Loss_G[i] = sums["D_loss"], sums["G_loss"]
+            log('Epoch {}: score_real {:.5f} score_fake {:.5f} D_loss {:.5f} G_loss {:.5f} (n_critic {})'.format(
+                epoch, sums["score_real"], sums["score_fake"], sums["D_loss"], sums["G_loss"], trainer.n_critic))
+            if checkpoint is not None and epoch % cfg.checkpointing_period == 0:
+                checkpoint.lr = trainer.opt_g.param_groups[0]["lr"]
+                checkpoint.save_state(epoch)
+                if samples_dir is not None:
+                    plot_gen_samples(G, eval_noise=eval_noise,
+                                     filename=os.path.join(samples_dir, 'Test_images_{}_{}.png'.format(cfg.ID, epoch)))
+    finally:
+        trainer.n_critic = n_critic_max
+    return history
+
+
 def build_arg_parser():
     """The reference's flags (train.py:39-91), same names, types and help; defaults are irrelevant because -- as in the
     reference (train.py:95-104) -- only flags literally present on the command line override the configuration module."""
@@ -920,7 +1202,16 @@ def cli_overrides(argv, options, names):
 
 
 def make_trainer(config, G, D):
-    """The trainer `main()` trains with: RMSprop when config.RMSprop is set, else Adam with betas (beta1, 0.999) (train.py:220-225)."""
+    """The trainer `main()` trains with: RMSprop when config.RMSprop is set, else Adam with betas (beta1, 0.999) (train.py:220-225).
+    wgan without pggan: a WGANTrainer (weight clipping at 0.01, reference train.py:489-490); wgan with pggan is refused."""
+    if config.wgan and config.pggan:
+        raise ValueError("wgan=True together with pggan=True is not a configuration the reference can train (it fails at "
+                         "Generator_net.image_size); choose one")
+    if config.wgan:
+        kw = dict(learning_rate=config.learning_rate, drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, device_latents=True)
+        if config.RMSprop:
+            return WGANTrainer(G, D, optimizer="rmsprop", **kw)
+        return WGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
     kw = dict(learning_rate=config.learning_rate, grad_pen_lambda=config.grad_pen_lambda, drift_epsilon=config.drift_epsilon,
               n_critic=config.n_critic, alpha_step=config.alpha_step, device_latents=True)
     if config.RMSprop:
@@ -942,8 +1233,11 @@ def main(argv=None):
     else:
         config.set_configs(**overrides)
         config.validate_configs(create_dirs=True)
-    if not config.pggan or config.wgan:
-        raise NotImplementedError("only the PGGAN path (pggan=True, wgan=False) is implemented")
+    if config.wgan and config.pggan:
+        raise ValueError("wgan=True together with pggan=True is not a configuration the reference can train (it fails at "
+                         "Generator_net.image_size); choose one")
+    if not config.pggan and not config.wgan:
+        raise NotImplementedError("the DCGAN path is disabled in the reference itself (train.py:629); choose pggan or wgan")
     if config.device != 'cuda':
         raise RuntimeError("the HIP path needs device='cuda' (there is no CPU fallback)")
     config.print_configs()
@@ -963,6 +1257,8 @@ def main(argv=None):
             dataset = TensorImageDataset(data.to(device))
     else:
         dataset = TensorImageDataset.synthetic(16, config.image_size, config.N_colors, device=device)
+    if config.wgan:
+        return _wgan_main(config, dataset, device, Checkpointer)
     size_init = dataset.image_size_max // (2 ** n_up)                                       # train.py:162-165
     G = models.Generator_PG(config.N_gen_features, image_size_init=size_init).to(device)    # train.py:172-175
     D = models.Discriminator_PG(config.N_dis_features, image_size_init=size_init).to(device)
@@ -986,6 +1282,32 @@ def main(argv=None):
     epoch_final = epoch_init + config.N_epochs_session if config.N_epochs_session else config.N_epochs + 1
     return pggan_train(trainer, dataset, config, checkpoint=checkpoint, epoch_init=epoch_init, epoch_final=epoch_final,
                        samples_dir=config.samples_sub_dir)
+
+
+def _wgan_main(config, dataset, device, Checkpointer):
+    """main() for wgan=True, pggan=False (train.py:172-180, 204-210, 269, 454-536)"""
+    from . import models
+    from .utils import init_weights
+    G = models.Generator_wgan(config.N_gen_features, latent_dim=config.latent_dim, image_size=config.image_size,
+                              N_colors=config.N_colors).to(device)
+    D = models.Discriminator_wgan(config.N_dis_features, image_size=config.image_size, N_colors=config.N_colors).to(device)
+    filename = os.path.join(config.weights_dir, 'GenDisc_{}.pth'.format(config.ID))
+    resume = config.resume and os.path.exists(filename)
+    if not resume and not config.weights_init:
+        G.apply(init_weights)
+        D.apply(init_weights)
+    trainer = make_trainer(config, G, D)
+    checkpoint = Checkpointer(G, D, config.learning_rate, filename, N_epochs=config.N_epochs, device=device, extra_checkpoint_period=1e3,
+                              trainer=trainer)
+    if resume:
+        checkpoint.load_state()
+    elif config.weights_init:
+        checkpoint.load_state(os.path.join(config.weights_dir, config.weights_init))
+    eval_noise = sample_latent_vec((16, G.latent_dim), device=device)
+    epoch_init = checkpoint.epoch + 1
+    epoch_final = epoch_init + config.N_epochs_session if config.N_epochs_session else config.N_epochs + 1
+    return wgan_train(trainer, dataset, config, checkpoint=checkpoint, epoch_init=epoch_init, epoch_final=epoch_final,
+                      samples_dir=config.samples_sub_dir, eval_noise=eval_noise)
 
 
 if __name__ == '__main__':

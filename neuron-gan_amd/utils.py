@@ -134,8 +134,10 @@ class Checkpointer:
             self.Loss_G[:self.epoch] = checkpoint_dict['Loss_G']
             self.Loss_D[:self.epoch] = checkpoint_dict['Loss_D']
         if 'Generator_attrs' in checkpoint_dict and 'Discriminator_attrs' in checkpoint_dict:
-            gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in self.Generator_net.saved_attrs}
-            dis_attrs = {k: v for k, v in checkpoint_dict['Discriminator_attrs'].items() if k in self.Discriminator_net.saved_attrs}
+            # (the WGAN nets list no saved_attrs: the reference fails there, utils.py:194-198; here they count as empty)
+            gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in getattr(self.Generator_net, 'saved_attrs', [])}
+            dis_attrs = {k: v for k, v in checkpoint_dict['Discriminator_attrs'].items()
+                         if k in getattr(self.Discriminator_net, 'saved_attrs', [])}
             if hasattr(self.Generator_net, 'set_resolution'):
                 res, alpha = gen_attrs['image_size'], float(gen_attrs['alpha'])
                 if self.Generator_net.image_size != res:
@@ -143,8 +145,11 @@ class Checkpointer:
                     self.Discriminator_net.set_resolution(res, alpha)
             set_saved_attrs(self.Generator_net, gen_attrs)
             set_saved_attrs(self.Discriminator_net, dis_attrs)
-        gen_state = type(self.Generator_net).from_state_dict(source, verbose=False).state_dict()
-        dis_state = type(self.Discriminator_net).from_state_dict(source, verbose=False).state_dict()
+        if hasattr(type(self.Generator_net), 'from_state_dict'):
+            gen_state = type(self.Generator_net).from_state_dict(source, verbose=False).state_dict()
+            dis_state = type(self.Discriminator_net).from_state_dict(source, verbose=False).state_dict()
+        else:       # fixed-architecture nets (WGAN): the saved state dicts, BatchNorm buffers included
+            gen_state, dis_state = checkpoint_dict['Generator_state'], checkpoint_dict['Discriminator_state']
         self.Generator_net.load_state_dict(gen_state, strict=False)
         self.Discriminator_net.load_state_dict(dis_state, strict=False)
         if self.trainer is not None:
@@ -202,8 +207,9 @@ def plot_gen_samples(Generator, eval_noise=None, N_images=16, seed=None, filenam
         N_images = images.size(0)
     Generator.train(was_training)
     images = images.cpu()
-    if images.size(-1) != Generator.image_size_max:
-        images = torch.nn.functional.interpolate(images, size=(Generator.image_size_max, Generator.image_size_max))
+    size = getattr(Generator, 'image_size_max', images.size(-1))      # (fixed-size nets: the WGAN generator)
+    if images.size(-1) != size:
+        images = torch.nn.functional.interpolate(images, size=(size, size))
     grid = make_image_grid(images, nrow=int(np.round(np.sqrt(N_images))))
     if filename is not None:
         from PIL import Image
@@ -235,3 +241,14 @@ def similarity_loss(images_batch, Z_batch, Lambda=1.0):
     im = im / im.norm(2, dim=1, keepdim=True)
     z = z / z.norm(2, dim=1, keepdim=True)
     return Lambda * torch.pow(z @ z.t() - im @ im.t(), 2).sum() / (b * (b - 1))
+
+
+def init_weights(m: torch.nn.Module):
+    """The reference's init for the WGAN / DCGAN nets (utils.py:96-101), applied with `net.apply(init_weights)`: normal(0, 0.02)
+    conv weights, normal(1, 0.02) BatchNorm weights, zero BatchNorm biases; exact type match, so Linear layers and conv biases keep
+    torch's default init."""
+    if type(m) in [torch.nn.Conv2d, torch.nn.ConvTranspose2d]:
+        m.weight.data.normal_(0.0, 0.02)
+    elif type(m) == torch.nn.BatchNorm2d:
+        m.weight.data.normal_(1.0, 0.02)
+        m.bias.data.fill_(0.0)
