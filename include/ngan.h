@@ -65,8 +65,7 @@ int ngan_conv3x3_pack_weights(const float* w_oihw, float* packed, int Cout, int 
  *     lane and spends 16 instead of 36 v_mfma_f32_16x16x4_f32 per 16 pixels and 16 x 16 channel pair.  fp32 arithmetic throughout;
  *     its error against an fp64 evaluation of the fused operator is below 1e-6 relative L2 (tests/test_gpu_ops.py::
  *     test_winograd_kernels_against_fp64; the direct form: 2.6e-7 against 1.5e-7 on the same operands).
- * The answer depends on the shape only: the library reads no environment variable (the measurement switches that select the
- * direct forms exist in the diagnostic build, `make diag`, only). */
+ * The answer depends on the shape only: the library reads no environment variable. */
 int ngan_conv3x3_algorithm(int B, int H, int W, int K, int N, int resample, int precision);
 long ngan_conv3x3_packed_floats(int Cout, int Cin, int precision);   /* size of `packed` in floats */
 

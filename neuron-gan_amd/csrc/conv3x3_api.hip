@@ -6,9 +6,8 @@
 // Exact-fp32 layers on large images in Winograd F(2x2, 3x3) form: 16 -> 16 with plain or bilinear input (conv3x3_tile_kernel /
 // conv3x3_persist_kernel), and the shapes with a 32-channel side with plain input on whole 32-pixel tiles (conv3x3_wino.hip)
 static bool wino_eligible(int B, int H, int W, int K, int N, int resample) {
-    if (!NGAN_DIAG_FLAG("NGAN_WINOGRAD", true) || resample == NGAN_RESAMPLE_POOL2 || !persist_eligible(B, H, W, K, N, resample)) return false;
-    if (K == 16 && N == 16) return true;
-    return NGAN_DIAG_FLAG("NGAN_WINOGRAD32", true) && W % 32 == 0;
+    if (resample == NGAN_RESAMPLE_POOL2 || !persist_eligible(B, H, W, K, N, resample)) return false;
+    return (K == 16 && N == 16) || W % 32 == 0;
 }
 
 extern "C" int ngan_conv3x3_algorithm(int B, int H, int W, int K, int N, int resample, int precision) {
@@ -26,14 +25,10 @@ extern "C" int ngan_conv3x3_algorithm(int B, int H, int W, int K, int N, int res
     return (K == 16 && ngan::conv3x3_mid_eligible(B, H, W, 32, N)) ? 2 : 0;
 }
 
-// exact-fp32 layers with 32..128 channels on small images run in the fp32 variant of the mid kernel
-static bool mid_f32_enabled() { return NGAN_DIAG_FLAG("NGAN_MID_F32", true); }
-
 // epilogue 1 can also write y averaged over 2x2 blocks (aux_out of ngan_conv3x3_fwd_ex): the Winograd kernels on whole tiles, whose
 // lanes own exactly one pooling window each
 extern "C" int ngan_conv3x3_pooled_output(int B, int H, int W, int K, int N, int resample, int precision) {
     if (precision != 4 || B <= 0 || H <= 0 || W <= 0 || (H & 1) || W % 32) return 0;
-    if (resample == NGAN_RESAMPLE_UP2 && !NGAN_DIAG_FLAG("NGAN_WINOGRAD_UP2", true) && K == 16 && N == 16) return 0;   // (conv3x3_persist_kernel)
     return ngan_conv3x3_algorithm(B, H, W, K, N, resample, 0) == 4 ? 1 : 0;
 }
 
@@ -45,8 +40,7 @@ extern "C" int ngan_conv3x3_epilogue_fused(int B, int H, int W, int K, int N, in
     const bool persist = persist_eligible(B, H, W, K, N, resample);
     if (epilogue == EPI_TO_IMAGE) return persist && resample == 0 && out_mode == 0 ? 1 : 0;
     if (epilogue == EPI_PN_BWD)
-        return (persist && resample == 0) ||
-               ((precision >= 1 || mid_f32_enabled()) && resample == 0 && ngan::conv3x3_mid_fuses_epilogue(B, H, W, precision == 2 ? 32 : K, N)) ? 1 : 0;
+        return resample == 0 && (persist || ngan::conv3x3_mid_fuses_epilogue(B, H, W, precision == 2 ? 32 : K, N)) ? 1 : 0;
     return 0;
 }
 
@@ -92,15 +86,15 @@ extern "C" int ngan_conv3x3_fwd_ex(const float* x, const float* packed, const fl
         // precision code 4 = the Winograd form (16 -> 16: checked by the precision test above) = the kernels' PREC parameter 2
         const int tprec = precision == 4 ? 2 : precision;
         // Winograd form in conv3x3_wino.hip: the shapes with a 32-channel side, and every bilinear-input shape on whole tiles
-        if (tprec == 2 && W % 32 == 0 && (K == 32 || N == 32 || (resample == NGAN_RESAMPLE_UP2 && NGAN_DIAG_FLAG("NGAN_WINOGRAD_UP2", true))))
+        if (tprec == 2 && W % 32 == 0 && (K == 32 || N == 32 || resample == NGAN_RESAMPLE_UP2))
             return ngan::conv3x3_wino_launch(a, N / 16, K / 16, resample, epilogue, out_mode, s);
-        if (resample == 0 && NGAN_DIAG_FLAG("NGAN_TILE_KERNEL", true) && W % 32 == 0)      // plain input, whole tiles along x
+        if (resample == 0 && W % 32 == 0)      // plain input, whole tiles along x
             return ngan::conv3x3_tile_launch(a, N / 16, K / 16, epilogue, out_mode, tprec, s);
         return ngan::conv3x3_persist_launch(a, N / 16, K / 16, resample, epilogue, out_mode, tprec, s);
     }
     // many channels, small image: the kernel of conv3x3_mid.hip, split-bf16 (precision 2: K = 16 padded to 32) or exact fp32
     // (fp32 with a pooled input stays on the generic kernel, which measured 10 % faster there)
-    if (precision >= 1 || (mid_f32_enabled() && resample != NGAN_RESAMPLE_POOL2 && ngan::conv3x3_mid_eligible(B, H, W, K, N)))
+    if (precision >= 1 || (resample != NGAN_RESAMPLE_POOL2 && ngan::conv3x3_mid_eligible(B, H, W, K, N)))
         return ngan::conv3x3_mid_launch(x, packed, bias, y, rnorm, aux_in, aux_rn, B, H, W, K, N, resample, epilogue, out_mode, slope, eps, precision, s);
     // generic exact-fp32 kernel: it has epilogues 0 and 1; the PixelNorm backward runs as a second launch, in place
     const int epi = epilogue == EPI_PN_BWD ? EPI_NONE : epilogue;
@@ -136,18 +130,18 @@ extern "C" int ngan_conv3x3_kernel_name(int B, int H, int W, int K, int N, int r
     if (precision == 5) return ngan::conv3x3_bf16_kernel_name(B, H, W, K, N, buf, len);
     if (precision == 3)
         snprintf(buf, len, "conv3x3_up2f_kernel<%d, %d>", K / 16, epilogue);
-    else if (precision == 4 && W % 32 == 0 && (K == 32 || N == 32 || (resample == NGAN_RESAMPLE_UP2 && NGAN_DIAG_FLAG("NGAN_WINOGRAD_UP2", true))))
+    else if (precision == 4 && W % 32 == 0 && (K == 32 || N == 32 || resample == NGAN_RESAMPLE_UP2))
         snprintf(buf, len, "conv3x3_wino_kernel<%d, %d, %d, %d, %d, %d, %d>", K / 16, N / 16, ngan::conv3x3_wino_tile_rows(N / 16, K / 16),
                  (K == 16) ? 4 : 8, resample, (out_mode && epilogue != EPI_PN_BWD) ? 0 : epilogue, out_mode);
     else if (N <= 32 && K <= 32 && resample != NGAN_RESAMPLE_POOL2 && ci == 0) {
-        if ((out_mode || resample == 0) && NGAN_DIAG_FLAG("NGAN_TILE_KERNEL", true) && W % 32 == 0)
+        if ((out_mode || resample == 0) && W % 32 == 0)
             snprintf(buf, len, "conv3x3_tile_kernel<%d, %d, %d, %d, %d>", N / 16, K / 16, (out_mode && epilogue != EPI_PN_BWD) ? 0 : epilogue,
                      out_mode, precision == 4 ? 2 : precision);
         else
             snprintf(buf, len, "conv3x3_persist_kernel<%d, %d, %d, %d, %d, %d>", N / 16, K / 16, out_mode ? 0 : resample,
                      (out_mode && epilogue != EPI_PN_BWD) ? 0 : epilogue, out_mode, precision == 4 ? 2 : precision);
     }
-    else if ((precision >= 1 || (mid_f32_enabled() && resample != NGAN_RESAMPLE_POOL2)) && ngan::conv3x3_mid_eligible(B, H, W, precision == 2 ? 32 : K, N))
+    else if ((precision >= 1 || resample != NGAN_RESAMPLE_POOL2) && ngan::conv3x3_mid_eligible(B, H, W, precision == 2 ? 32 : K, N))
         return ngan::conv3x3_mid_kernel_name(B, H, W, precision == 2 ? 32 : K, N, resample, epilogue, out_mode, precision, buf, len);
     else {
         const TileCfg c = kCfg[mti][ci];

@@ -9,26 +9,6 @@
 #include <cstdlib>
 #include "conv3x3_shared.h"
 
-// A/B switches for measurements exist in the DIAGNOSTIC build only (`make diag`: -DNGAN_DIAG, written to build/diag/, never into
-// the package directory).  In the product library every switch is the compile-time constant of its default: no environment
-// variable changes which kernel a call runs.
-#ifdef NGAN_DIAG
-namespace ngan {
-inline bool diag_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] != '0' : dflt; }
-inline int diag_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-}
-#define NGAN_DIAG_FLAG(name, dflt) ([] { static const bool v = ::ngan::diag_flag(name, dflt); return v; }())
-#define NGAN_DIAG_INT(name, dflt) ([] { static const int v = ::ngan::diag_int(name, dflt); return v; }())
-#else
-#define NGAN_DIAG_FLAG(name, dflt) (dflt)
-#define NGAN_DIAG_INT(name, dflt) (dflt)
-#endif
-
-// workgroups of the 16 -> 16 Winograd instances the register allocation makes room for per CU (waves per SIMD; build-time knob)
-#ifndef NGAN_WINO16_WPE
-#define NGAN_WINO16_WPE 2
-#endif
-
 namespace ngan {
 // launchers exported by the kernel files (template instance chosen at run time from the arguments)
 int conv3x3_tile_launch(const ConvArgs& a, int mtw, int kg, int epilogue, int out_mode, int tprec, hipStream_t s);                  // conv3x3_tile.hip
@@ -87,9 +67,6 @@ struct TileWalk {
 };
 
 inline int persistent_grid(int n_tiles, int resident) {
-    const int per_cu = NGAN_DIAG_INT("NGAN_PERSIST_WG_PER_CU", 0);
-    const int cap = per_cu > 0 ? per_cu * 256 : 1 << 30;
-    if (resident > cap) resident = cap;
     int grid = resident < n_tiles ? resident : n_tiles;
     grid &= ~7;
     return grid < 8 ? 8 : grid;
@@ -155,25 +132,6 @@ __device__ __forceinline__ void st_split(float* tile, int idx, float4 v) {
     *reinterpret_cast<bf16x4*>(&tile[KG == 1 ? (idx ^ 8) : (idx + PLANE)]) = lo;
 }
 
-// three-way split (conv3x3_tile_kernel PREC = 3, diagnostic build): hi and mid where the two-way split keeps hi and lo, lo in the same
-// slot of a second plane
-template <int PLANE>
-__device__ __forceinline__ void st_split3(float* tile, int idx, float4 v) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-    bf16x4 hi, mid, lo;
-    const float x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        hi[i] = (__bf16)x[i];
-        const float r1 = x[i] - (float)hi[i];
-        mid[i] = (__bf16)r1;
-        lo[i] = (__bf16)(r1 - (float)mid[i]);
-    }
-    *reinterpret_cast<bf16x4*>(&tile[idx]) = hi;
-    *reinterpret_cast<bf16x4*>(&tile[idx ^ 8]) = mid;
-    *reinterpret_cast<bf16x4*>(&tile[idx + PLANE]) = lo;
-}
-
 // LDS image of a tile: rows of LP = 40 pixels (>= 34 used), 16 floats per pixel, one plane per 16-channel group.
 // The 16-byte quad c of pixel column X is stored at quad (c ^ 2*((X >> 2) & 1)): with that rotation the 16-lane groups of
 // a ds_read_b128 (lanes = 16 consecutive pixels x 4 quads) touch 16 distinct 16-byte slots of a 256-byte bank row
@@ -235,7 +193,7 @@ inline bool persist_eligible(int B, int H, int W, int K, int N, int resample) {
 
 // bilinear x2 folded into the weights (precision code 3): the persistent kernel's shapes with 16 outputs, and an interior to speak of
 inline bool up2f_eligible(int B, int H, int W, int K, int N, int resample) {
-    return NGAN_DIAG_FLAG("NGAN_UP2_FOLDED", true) && resample == NGAN_RESAMPLE_UP2 && N == 16 && (K == 16 || K == 32) && H % 2 == 0 && W % 2 == 0 && H >= 16 && W >= 32 &&
+    return resample == NGAN_RESAMPLE_UP2 && N == 16 && (K == 16 || K == 32) && H % 2 == 0 && W % 2 == 0 && H >= 16 && W >= 32 &&
            persist_eligible(B, H, W, K, N, resample);
 }
 

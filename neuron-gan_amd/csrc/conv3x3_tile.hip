@@ -19,58 +19,27 @@ namespace {
 // Same LDS image and MFMA order as conv3x3_persist_kernel; bit-identical to it without a bias (with one, the bias is added first
 // instead of last).
 // ---------------------------------------------------------------------------------------------------------
-#ifndef NGAN_TILE_PRE
-#define NGAN_TILE_PRE 1
-#endif
-#ifndef NGAN_TILE_PRE_WINO
-#define NGAN_TILE_PRE_WINO 1
-#endif
-#ifndef NGAN_TILE_DOUBLE_BUFFER
-#define NGAN_TILE_DOUBLE_BUFFER 0      // measured, round 3: slower (below)
-#endif
-
-// Phase-timer build only (`make phases`; tools/wgrad_phases.py --op fwd): shader-clock stamps, summed over the sampled waves (one workgroup in
-// eight).  0 = the tile's first barrier, 1 = waiting for the tile's loads + LDS writes, 2 = second barrier, 3 = issuing the next tile's loads +
-// the epilogue's scalars / operand requests, 4 = transforms + MFMAs, 5 = epilogue arithmetic + stores, 6 = number of waves
-#ifdef NGAN_DIAG_PHASES
-__device__ unsigned long long tile_phase_ctr[11];      // 7 = earliest loop entry, 8 = latest exit, 9 = sum of entries, 10 = sum of exits (s_memrealtime, 100 MHz)
-#define TPH_INIT unsigned long long ph_[6] = {0, 0, 0, 0, 0, 0}, last_ = __builtin_readcyclecounter(), t0_ = __builtin_amdgcn_s_memrealtime()
-#define TPH(i) { const unsigned long long now_ = __builtin_readcyclecounter(); ph_[i] += now_ - last_; last_ = now_; }
-#define TPH_FLUSH if (lane == 0 && (blockIdx.x & 7) == 0) { const unsigned long long t1_ = __builtin_amdgcn_s_memrealtime(); \
-    for (int i_ = 0; i_ < 6; ++i_) atomicAdd(&tile_phase_ctr[i_], ph_[i_]); atomicAdd(&tile_phase_ctr[6], 1ull); \
-    atomicMin(&tile_phase_ctr[7], t0_); atomicMax(&tile_phase_ctr[8], t1_); atomicAdd(&tile_phase_ctr[9], t0_); atomicAdd(&tile_phase_ctr[10], t1_); }
-#else
-#define TPH_INIT
-#define TPH(i)
-#define TPH_FLUSH
-#endif
-
 template <int MTW, int KG, int EPI, int OUTMODE, int PREC>
-__global__ __launch_bounds__(256, PREC == 2 ? NGAN_WINO16_WPE : (MTW * KG == 1) ? (PREC ? 3 : 4) : 2) void conv3x3_tile_kernel(ConvArgs a, int n_tiles) {
-    // PREC: 0 exact fp32 (direct), 1 split bf16, 2 exact fp32 by Winograd F(2x2, 3x3) (16 -> 16 only; see the MFMA section),
-    // 3 (diagnostic build only: ngan_diag_conv3x3_bf16x6 below) THREE-way split bf16: x = hi + mid + lo covers fp32's 24 significand bits, six of
-    // the nine cross products per fp32 product (hh, hm, mh, hl, lh, mm; the dropped three are <= 2^-24 relative), fp32 accumulation
-    constexpr bool BF = PREC == 1 || PREC == 3, BF6 = PREC == 3, WINO = PREC == 2;
-    constexpr int NPART = BF6 ? 3 : 2;
+__global__ __launch_bounds__(256, (MTW * KG == 1 && PREC != 2) ? (PREC ? 3 : 4) : 2) void conv3x3_tile_kernel(ConvArgs a, int n_tiles) {
+    // PREC: 0 exact fp32 (direct), 1 split bf16, 2 exact fp32 by Winograd F(2x2, 3x3) (16 -> 16 only; see the MFMA section)
+    constexpr bool BF = PREC == 1, WINO = PREC == 2;
     static_assert(!WINO || (MTW == 1 && KG == 1), "the Winograd form is built for the 16 -> 16 layers");
-    static_assert(!BF6 || (MTW == 1 && KG == 1), "the three-way split is an experiment on the 16 -> 16 layers");
     constexpr int THc = persist_tile_h(MTW, KG, 0), PGW = THc / 2, RPW = THc / 4;
     constexpr int HH_ = THc + 2, LP = 40;
     constexpr int NSTEP = KG == 1 ? 5 : 9;
-    constexpr int W_ELEMS = BF ? NSTEP * MTW * NPART * 256 : (WINO ? 16 * 256 : 9 * KG * MTW * 256), PLANE = HH_ * LP * 16, TILE_ELEMS = (BF6 ? 2 : KG) * PLANE;
+    constexpr int W_ELEMS = BF ? NSTEP * MTW * 2 * 256 : (WINO ? 16 * 256 : 9 * KG * MTW * 256), PLANE = HH_ * LP * 16, TILE_ELEMS = KG * PLANE;
     constexpr int LPG = HH_ / 2;                 // interior loads per 16-channel group: HH_ rows x 32 columns x 4 quads / 256 threads
     constexpr int NL = KG * LPG, NST = NL + 1;   // + one load for the two halo columns
     constexpr int N_HALO = KG * 2 * HH_ * 4;     // its active lanes: (group, side, row, quad)
     constexpr int K = KG * 16, N = MTW * 16;
     constexpr unsigned OOB = 0xFFFFFFF0u;
     static_assert(HH_ % 2 == 0 && N_HALO <= 256, "staging layout");
-    // Build-time option for the Winograd instances: TWO tile buffers.  The next tile is staged into the other buffer while this one
-    // is being read, so a tile costs one workgroup barrier instead of two and no wave waits for the others' staging before its MFMAs
-    // (16 + 2 x 25.6 KB: still two workgroups per CU).  Correct (the whole op suite passes with it) and NOT faster: 16 -> 16 at
+    // Measured and not kept (round 3): TWO tile buffers for the Winograd instances, the next tile staged into the other buffer while
+    // this one is being read -- one workgroup barrier per tile instead of two, no wave waiting for the others' staging before its MFMAs
+    // (16 + 2 x 25.6 KB: still two workgroups per CU).  Correct (the whole op suite passed with it) and NOT faster: 16 -> 16 at
     // 512 x 512, batch 16: 145 -> 154 us plain, 165 -> 167 us with LeakyReLU -> PixelNorm, 75.9 -> 80.4 us with the pool-adjoint store;
-    // iteration 7.17 -> 7.22 ms.  The second barrier was not what the waves wait for; off.
-    constexpr bool DB = WINO && NGAN_TILE_DOUBLE_BUFFER;
-    __shared__ __attribute__((aligned(16))) float smem[W_ELEMS + (DB ? 2 : 1) * TILE_ELEMS];
+    // iteration 7.17 -> 7.22 ms.  The second barrier was not what the waves wait for.
+    __shared__ __attribute__((aligned(16))) float smem[W_ELEMS + TILE_ELEMS];
     float* wl = smem;
     float* tile = smem + W_ELEMS;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -193,48 +162,28 @@ __global__ __launch_bounds__(256, PREC == 2 ? NGAN_WINO16_WPE : (MTW * KG == 1) 
     auto stage = [&](float* buf) {                 // the loaded tile (stg) -> LDS image
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
-            if (BF6) st_split3<PLANE>(buf, s_lds[i], stg[i]);
-            else if (BF) st_split<KG, PLANE>(buf, s_lds[i], stg[i]);
+            if (BF) st_split<KG, PLANE>(buf, s_lds[i], stg[i]);
             else st4(&buf[s_lds[i]], stg[i]);
         }
         pin_registers(stg[NL]);     // every wave awaits the halo load here (the waves that store nothing would carry it, un-awaited, into the next issue)
         if (tid < N_HALO) {
-            if (BF6) st_split3<PLANE>(buf, s_lds[NL], stg[NL]);
-            else if (BF) st_split<KG, PLANE>(buf, s_lds[NL], stg[NL]);
+            if (BF) st_split<KG, PLANE>(buf, s_lds[NL], stg[NL]);
             else st4(&buf[s_lds[NL]], stg[NL]);
         }
     };
-    if (DB && t < t_end) {                         // double-buffered: the first tile is staged here, the second one's loads go out
-        stage(tile);
-        __syncthreads();
-        if (t + run.step < t_end) issue(next_tile);
-    }
-    float* const tile0 = tile;
-    int cur = 0;
-    TPH_INIT;
     while (t < t_end) {
         const int b = cur_tile.b, y0 = cur_tile.ty * THc, x0 = cur_tile.tx * 32;
         const int tn = t + run.step;
-        if (DB) {
-            // stg holds tile tn (loaded during the previous tile): into the buffer nobody reads now; then the loads of the tile after it
-            tile = tile0 + cur * TILE_ELEMS;
-            if (tn < t_end) stage(tile0 + (cur ^ 1) * TILE_ELEMS);
-            if (tn + run.step < t_end) issue(walk.next(next_tile));
-        } else {
-            __syncthreads();   // previous tile's MFMAs have finished reading `tile`
-            TPH(0);
-            stage(tile);
-            TPH(1);
-            __syncthreads();
-            TPH(2);
-            if (tn < t_end) issue(next_tile);   // in flight while this tile is computed
-        }
+        __syncthreads();   // previous tile's MFMAs have finished reading `tile`
+        stage(tile);
+        __syncthreads();
+        if (tn < t_end) issue(next_tile);   // in flight while this tile is computed
 
         // ---- per-tile scalars of the epilogue.  The tile's byte offset is ADDED to the per-lane constants (one v_add per access)
         // instead of riding in the buffer instructions' soffset field: a buffer_store_dwordx4 with an SGPR soffset reads its data
         // registers late, the compiler (whose hazard table exempts exactly that form) puts no wait state behind it, and the next
         // VALU write into those registers reached memory instead -- single components of the last four lanes of a pixel group,
-        // in a fraction of a percent of the tiles (tools/dbg_tile.py; found the same way: bit-comparison with the old kernel) ----
+        // in a fraction of a percent of the tiles (found by bit-comparison with the old kernel) ----
         const long img = (long)b * a.H * a.W;
         const int pix0 = (OS * y0) * Wo + OS * x0;                       // first output pixel of the tile inside its image
         const unsigned y_soff = (unsigned)pix0 * (N * 4), p_soff = (unsigned)(y0 * a.W + x0) * 4u;
@@ -253,7 +202,7 @@ __global__ __launch_bounds__(256, PREC == 2 ? NGAN_WINO16_WPE : (MTW * KG == 1) 
         constexpr bool PNB = EPI == EPI_PN_BWD && OUTMODE == 0;
         // (the 16 -> 16 direct / split-bf16 instances run 3 - 4 workgroups per CU and have no registers for it; the Winograd instance
         // has 2 per CU and ~170 of 256 registers in use)
-        constexpr bool PRE = PNB && (MTW * KG > 1 || (WINO && NGAN_TILE_PRE_WINO)) && NGAN_TILE_PRE;
+        constexpr bool PRE = PNB && (MTW * KG > 1 || WINO);
         float4 yy[PNB ? PGW : 1][MTW];
         float rr[PNB ? PGW : 1];
         auto load_pn_operands = [&]() {
@@ -267,7 +216,6 @@ __global__ __launch_bounds__(256, PREC == 2 ? NGAN_WINO16_WPE : (MTW * KG == 1) 
         };
         if (PRE) load_pn_operands();
 
-        TPH(3);
         f32x4 acc[PGW][MTW];
 #pragma unroll
         for (int pg = 0; pg < PGW; ++pg)
@@ -320,36 +268,6 @@ __global__ __launch_bounds__(256, PREC == 2 ? NGAN_WINO16_WPE : (MTW * KG == 1) 
                 acc[ar * 2 + 0][0] = unpk2(ta[ar][0] + ta[ar][1] + ta[ar][2]);
                 acc[ar * 2 + 1][0] = unpk2(psub(psub(ta[ar][1], ta[ar][2], m1), ta[ar][3], m1));
             }
-        } else if (BF6) {
-            // weights [step][part hi / mid / lo][lane][8]; tile: hi and mid share the pixel's 64-byte slot (the two-way split's layout), lo
-            // is the same slot of a second plane.  Smallest products first.
-#pragma unroll
-            for (int st = 0; st < NSTEP; ++st) {
-                bf16x8 xh[PGW], xm[PGW], xl[PGW];
-#pragma unroll
-                for (int pg = 0; pg < PGW; ++pg) {
-                    const int row = wave * RPW + (pg >> 1);
-                    const int base = (row * LP + (pg & 1) * 16) * 16 + rs[st];
-                    xh[pg] = *reinterpret_cast<const bf16x8*>(&tile[base]);
-                    xm[pg] = *reinterpret_cast<const bf16x8*>(&tile[base ^ 8]);
-                    xl[pg] = *reinterpret_cast<const bf16x8*>(&tile[base + PLANE]);
-                }
-                const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&wl[(st * 3 + 0) * 256 + lane * 4]);
-                const bf16x8 wm = *reinterpret_cast<const bf16x8*>(&wl[(st * 3 + 1) * 256 + lane * 4]);
-                const bf16x8 wlo = *reinterpret_cast<const bf16x8*>(&wl[(st * 3 + 2) * 256 + lane * 4]);
-#pragma unroll
-                for (int pg = 0; pg < PGW; ++pg) acc[pg][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xh[pg], acc[pg][0], 0, 0, 0);
-#pragma unroll
-                for (int pg = 0; pg < PGW; ++pg) acc[pg][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[pg], acc[pg][0], 0, 0, 0);
-#pragma unroll
-                for (int pg = 0; pg < PGW; ++pg) acc[pg][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, xm[pg], acc[pg][0], 0, 0, 0);
-#pragma unroll
-                for (int pg = 0; pg < PGW; ++pg) acc[pg][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, xh[pg], acc[pg][0], 0, 0, 0);
-#pragma unroll
-                for (int pg = 0; pg < PGW; ++pg) acc[pg][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xm[pg], acc[pg][0], 0, 0, 0);
-#pragma unroll
-                for (int pg = 0; pg < PGW; ++pg) acc[pg][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[pg], acc[pg][0], 0, 0, 0);
-            }
         } else if (BF) {
 #pragma unroll
             for (int st = 0; st < NSTEP; ++st) {
@@ -399,13 +317,12 @@ __global__ __launch_bounds__(256, PREC == 2 ? NGAN_WINO16_WPE : (MTW * KG == 1) 
                 }
             }
         }
-        TPH(4);
         // ---- epilogue ----
         if (PNB && !PRE) load_pn_operands();
         // PixelNorm-backward operands: wait for everything in flight (the operand loads and the next tile, issued a tile's worth of
         // MFMAs ago) BEFORE the first store goes out.  Once stores are in flight, loads and stores of gfx9 retire out of order with each other
         // under one counter, and the counted waits the compiler emits for the older loads returned early: wrong last dwords in the
-        // last lanes of a pixel group (tools/dbg_epi2.py; without the prefetch the kernel is bit-identical to conv3x3_persist_kernel)
+        // last lanes of a pixel group (found by bit-comparison: without the prefetch the kernel is bit-identical to conv3x3_persist_kernel)
         if (PNB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         float timg = 0.f;
         // pooled side output (Winograd form, epilogue 1, a.aout given): the lane's four pixel groups ARE one 2x2 pooling window
@@ -459,17 +376,6 @@ __global__ __launch_bounds__(256, PREC == 2 ? NGAN_WINO16_WPE : (MTW * KG == 1) 
                 if (q == pg) timg = d;          // all four q-lanes hold pixel group pg's sum; lane group q keeps the one it will finish
             }
             if (PNB) {
-#ifdef NGAN_DIAG
-                // Timing experiment (tools/gp_fusion_probe.py, diagnostic build only): what a create_graph pass would need from a fused
-                // input-gradient + PixelNorm-backward kernel -- the gradient BEFORE the PixelNorm backward as a second output (aux_out)
-                if (OUTMODE == 0 && a.aout) {
-                    const __amdgpu_buffer_rsrc_t pre_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.aout + img * N, 0, out_bytes, 0x00020000);
-#pragma unroll
-                    for (int mt = 0; mt < MTW; ++mt)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, make_float4(lo[mt].x, lo[mt].y, hi[mt].x, hi[mt].y)), pre_rsrc,
-                                                               e_voff[pg] + y_soff + mt * 64, 0, 0);
-                }
-#endif
                 // backward of the LeakyReLU -> PixelNorm that produced this layer's input, applied to the gradient just computed
                 float s = 0.f;
 #pragma unroll
@@ -557,16 +463,10 @@ __global__ __launch_bounds__(256, PREC == 2 ? NGAN_WINO16_WPE : (MTW * KG == 1) 
             const __amdgpu_buffer_rsrc_t t_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.aout + img, 0, px_bytes, 0x00020000);
             if (q < PGW) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, tv), t_rsrc, t_voff + p_soff, 0, 0);
         }
-        if (DB) {
-            __syncthreads();   // every wave has finished reading this tile's buffer and writing the next tile's
-            cur ^= 1;
-        }
-        TPH(5);
         t = tn;
         cur_tile = next_tile;
         next_tile = walk.next(next_tile);
     }
-    TPH_FLUSH;
 }
 
 template <int MTW, int KG, int EPI, int OUTMODE, int PREC>
@@ -609,43 +509,3 @@ int ngan::conv3x3_tile_launch(const ConvArgs& a, int mtw, int kg, int epilogue, 
     if (mtw == 1) return kg == 1 ? dispatch_tile_prec<1, 1>(a, epilogue, out_mode, tprec, s) : dispatch_tile_prec<1, 2>(a, epilogue, out_mode, tprec, s);
     return kg == 1 ? dispatch_tile_prec<2, 1>(a, epilogue, out_mode, tprec, s) : dispatch_tile_prec<2, 2>(a, epilogue, out_mode, tprec, s);
 }
-
-#ifdef NGAN_DIAG
-// Diagnostic build only (not in include/ngan.h; tools/bf16x6_probe.py): the three-way split-bf16 form of the 16 -> 16 layer on plain input,
-// whole 32-pixel tiles -- the experiment behind the round-2 review's ruling on a "bf16x6" mode.  Packs w (OIHW fp32, 16 x 16 x 3 x 3) * scale
-// into `packed` (5 steps x 3 parts x 512 bf16 = 15 KB) and runs conv3x3_tile_kernel<1, 1, epilogue, 0, 3>; epilogue 0 or 1.
-namespace {
-__global__ void pack_weights_bf16x6_kernel(const float* __restrict__ w, __bf16* __restrict__ packed, float scale) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;                 // [step 5][part 3][lane 64][8]
-    if (idx >= 5 * 3 * 512) return;
-    const int j = idx & 7, lane = (idx >> 3) & 63, part = (idx >> 9) % 3, step = idx / (3 * 512);
-    const int n = lane & 15, kk = 8 * (lane >> 4) + j, tap = 2 * step + (kk >> 4), k = kk & 15;
-    float v = tap < 9 ? w[((long)n * 16 + k) * 9 + tap] * scale : 0.f;
-    const __bf16 hi = (__bf16)v;
-    const float r1 = v - (float)hi;
-    const __bf16 mid = (__bf16)r1;
-    packed[idx] = part == 0 ? hi : part == 1 ? mid : (__bf16)(r1 - (float)mid);
-}
-}  // namespace
-extern "C" int ngan_diag_conv3x3_bf16x6(const float* x, const float* w, const float* bias, float* y, float* rnorm, float* packed,
-                                        int B, int H, int W, float scale, int epilogue, float slope, float eps, void* stream) {
-    if (!x || !w || !y || !packed || B <= 0 || H <= 0 || W <= 0 || W % 32 || (epilogue != 0 && epilogue != 1) || (epilogue == 1 && !rnorm)) return NGAN_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pack_weights_bf16x6_kernel, dim3(30), dim3(256), 0, s, w, reinterpret_cast<__bf16*>(packed), scale);
-    ConvArgs a{x, packed, bias, y, rnorm, B, H, W, 16, 16, 0, 0, slope, eps, nullptr, nullptr, nullptr};
-    return epilogue ? launch_tile<1, 1, 1, 0, 3>(a, s) : launch_tile<1, 1, 0, 0, 3>(a, s);
-}
-#endif
-
-#ifdef NGAN_DIAG_PHASES
-// phase-timer build only (not declared in include/ngan.h): copies the phase counters of conv3x3_tile_kernel out and optionally zeroes them
-extern "C" int ngan_diag_tile_phases(unsigned long long* out11, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (hipMemcpyFromSymbol(out11, HIP_SYMBOL(tile_phase_ctr), 11 * sizeof(unsigned long long)) != hipSuccess) return 1;
-    if (reset) {
-        const unsigned long long z[11] = {0, 0, 0, 0, 0, 0, 0, ~0ull, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(tile_phase_ctr), z, sizeof(z)) != hipSuccess) return 1;
-    }
-    return 0;
-}
-#endif

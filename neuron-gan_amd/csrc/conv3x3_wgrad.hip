@@ -16,59 +16,28 @@ struct WgradArgs {
 };
 
 // ---------------------------------------------------------------------------------------------------------
-// fp32 weight gradient, second version (wgrad_kernel above: one ds_read_b32 + its address arithmetic per MFMA, 50-55 % of the
-// fp32 MFMA peak).  The contraction index is the pixel, 4 per v_mfma_f32_16x16x4_f32, so an operand register must hold ONE channel
-// of 4 pixels.  The tile is therefore staged channel-major -- gT[co][row][col], xT[ci][row][col + 1 halo] -- with scalar LDS
-// stores (global loads stay 16 B per lane along the channels), and k-lane q of MFMA j takes pixel 16 blk + 4 q + j: the A operands
-// of j = 0..3 are ONE ds_read_b128 of gT, the B operands of all three dx taps of a row are x columns 4q .. 4q + 5 of that row, i.e.
-// one ds_read_b128 + one ds_read_b64, picked by register index j + dx.  36 MFMAs (a 16-pixel block, all 9 taps) need 7 LDS
-// reads and no address arithmetic instead of 40 reads.  Plane pitches are = 4 (mod 64) dwords, which spreads the 16 channel
+// fp32 weight gradient.  The contraction index is the pixel, 4 per v_mfma_f32_16x16x4_f32, so an operand register must hold ONE
+// channel of 4 pixels.  The tile is therefore staged channel-major -- gT[co][row][col], xT[ci][row][col + 1 halo] -- with scalar LDS
+// stores (global loads stay 16 B per lane along the channels).  Plane pitches are = 4 (mod 64) dwords, which spreads the 16 channel
 // lanes of a read over the banks (one 2-way slot per b128 group) and makes the scalar stores 2-way at worst (free, LDS section of
-// MI355X_MICROARCH.md).  Tile order, per-block slabs and the fixed-order reduction are those of wgrad_kernel: bit-reproducible.
-// NW waves: a 16 x 16 (cout, cin) sub-slice per wave group, the tile's rows split over the groups' waves.
+// MI355X_MICROARCH.md).  Tile order, per-block slabs and the fixed-order reduction make it bit-reproducible.
+// (History: the first kernel read one ds_read_b32 + its address arithmetic per MFMA, 50-55 % of the fp32 MFMA peak; the direct
+// form that followed took k-lane q of MFMA j on pixel 16 blk + 4 q + j, 36 MFMAs of a 16-pixel block from 7 LDS reads -- 98
+// algorithmic TF against the Winograd form's 131 for 16 -> 16 at 512^2, batch 16 -- and was retired once the Winograd form below
+// covered every tile shape.)
 // ---------------------------------------------------------------------------------------------------------
-#ifndef NGAN_WGRAD_W22
-#define NGAN_WGRAD_W22 8
-#endif
-#ifndef NGAN_WGRAD_WINO16
-#define NGAN_WGRAD_WINO16 1
-#endif
-#ifndef NGAN_WGRAD_SMALL
-#define NGAN_WGRAD_SMALL (1 << 30)
-#endif
 // smallest m >= n with m = 4 (mod 64).  (Round 3 tried the smaller "any pitch whose quarter is odd" -- 364 instead of 388 dwords for
 // the 10 x 36 halo plane: the Winograd form's reads add 8 q to the lane address, and with a pitch of 44 (mod 64) six of the sixteen
 // lanes of a ds_read_b128 group collide instead of two: the 16 -> 16 kernel went from 51 to 106 us per launch.  Reverted.)
 constexpr int pad_plane(int n) { return n + ((4 - n % 64) + 64) % 64; }
 
-// WINO = 1 (16 x 16 slices, 8 x 32 tiles): the contraction in Winograd form, dW = G^T [ sum over 2x2 output tiles of (A dY A^T) . (B^T d B) ] G
+// The contraction in Winograd form, dW = G^T [ sum over 2x2 output tiles of (A dY A^T) . (B^T d B) ] G
 // -- the backward-filter counterpart of conv3x3_tile_kernel's F(2x2, 3x3).  A wave takes one row of 16 tiles; an MFMA contracts over
 // 4 tiles: lane (p, q) holds, for tile 4 q + ks, the transformed 2x2 output-gradient patch of output channel p (A operand) and the
 // transformed 4x4 input patch of input channel p (B operand), both computed by itself from its channel plane (2 + 8 ds_read_b64).
 // 16 accumulators (one per position of the 4x4 transformed tile) instead of 9 taps; 64 instead of 144 MFMAs per wave and tile.
-// The G^T . G back-transform is linear, so every workgroup applies it to its own partial sum before writing the slab: slab
-// format, slab reduction and bit-reproducibility are those of the direct form.
-// Phase-timer build only (`make phases`: -DNGAN_DIAG -DNGAN_DIAG_PHASES, build/phases/): where a wave's time goes, phase by phase
-// (shader clock, summed over the waves of a launch; read back through ngan_diag_wgrad_phases -- tools/wgrad_phases.py).  0 = waiting at the
-// tile's first barrier (the other waves still computing), 1 = waiting for this tile's global loads, 2 = LDS writes, 3 = second barrier,
-// 4 = issuing the next tile's loads, 5 = operand reads + transforms + MFMAs, 6 = the tail's first barrier (the waves' skew at the end of the
-// loop), 7 = the wave's own back-transform + its nine taps written to LDS + barrier (first output group), 8 = fixed-order sum over the row-group
-// waves + slab store (and the further output groups' rounds), 9 = unused, 10 = number of waves sampled (one workgroup in eight reports: with
-// every wave reporting, the atomics of the early finishers stood in the way of the others' tails and tripled the tail's apparent cost).
-#ifdef NGAN_DIAG_PHASES
-__device__ unsigned long long wgrad_phase_ctr[15];      // 11 = earliest loop entry, 12 = latest exit, 13 / 14 = sums of entries / exits (s_memrealtime, 100 MHz)
-#define PHASE_INIT unsigned long long ph_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_readcyclecounter(), t0_ = __builtin_amdgcn_s_memrealtime()
-#define PHASE_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); ph_[i] += now_ - last_; last_ = now_; }
-#define PHASE_WAIT_LOADS asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define PHASE_FLUSH if (lane == 0 && (blockIdx.x & 7) == 0) { const unsigned long long t1_ = __builtin_amdgcn_s_memrealtime(); \
-    for (int i_ = 0; i_ < 10; ++i_) atomicAdd(&wgrad_phase_ctr[i_], ph_[i_]); atomicAdd(&wgrad_phase_ctr[10], 1ull); \
-    atomicMin(&wgrad_phase_ctr[11], t0_); atomicMax(&wgrad_phase_ctr[12], t1_); atomicAdd(&wgrad_phase_ctr[13], t0_); atomicAdd(&wgrad_phase_ctr[14], t1_); }
-#else
-#define PHASE_INIT
-#define PHASE_STAMP(i)
-#define PHASE_WAIT_LOADS
-#define PHASE_FLUSH
-#endif
+// The G^T . G back-transform is linear, so every workgroup applies it to its own partial sum before writing the slab: the slabs hold
+// the 9 taps, as the retired direct form's did, and go through the same fixed-order reduction.
 
 // Round 4, measured and NOT kept (profiles/r04_wgrad_phases.txt, r04_micro_mfma_valu.txt, experiments/r04_wgrad_wave_private.diff):
 //  * the lane's ten input columns read once per halo row (two 16-byte + one 8-byte read instead of 16 + 8 per tile pair): 190 VGPRs, two
@@ -85,38 +54,36 @@ __device__ unsigned long long wgrad_phase_ctr[15];      // 11 = earliest loop en
 //  * 768 / 1024 instead of 512 workgroups (three per CU): 42.1 -> 43.0 / 46.7 us.
 //  * pairs of adjacent pixels per thread so that the transposing store of g is one ds_write_b64 per channel instead of two ds_write_b32
 //    (8 instead of 16 LDS instructions per thread and tile; conflict-free): 707 -> 713 us per iteration for the dominant instance: nothing.
-template <int COT, int CIT, int RES, int TW, int NW, int XF, int WINO = 0>
-__global__ __launch_bounds__(NW * 64, (WINO && !XF && COT * CIT == 1) ? 2 : (COT * CIT == 1) ? 3 : (COT * CIT == 2 || NW == 4 ? 2 : 1)) void wgrad_f32_kernel(WgradArgs a) {
+template <int COT, int CIT, int RES, int TW, int NW, int XF, int WINO>
+__global__ __launch_bounds__(NW * 64, (!XF && COT * CIT == 1) ? 2 : (COT * CIT == 1) ? 3 : (COT * CIT == 2 || NW == 4 ? 2 : 1)) void wgrad_f32_kernel(WgradArgs a) {
+    static_assert(WINO == 1, "Winograd form only; WINO stays in the instance names that profiles and bench.py's roofline accounting match");
     // Winograd form: a wave step covers 16 Winograd tiles -- one row of an 8 x 32 tile, or (TW = 16: images at most 16 pixels wide)
     // two rows of 8 of a 16 x 16 tile, lane quarters q = 0, 1 on the upper and q = 2, 3 on the lower row
     constexpr int WSTEP_ROWS = TW == 32 ? 2 : 4;                 // output rows a wave step covers
     constexpr int NT = NW * 64;
-    constexpr int TH = 256 / TW, HALO_H = TH + 2, NBLK = TW / 16;
+    constexpr int TH = 256 / TW, HALO_H = TH + 2;
     constexpr int CO_S = COT * 16, CI_S = CIT * 16;
-    constexpr int WO = COT * CIT, WR = NW / WO, RPW = TH / WR;                   // wave groups over sub-slices / over rows (direct form)
     constexpr int XP = TW + 4;                                                   // x row pitch (TW + 2 used), a multiple of 4
     constexpr int PLANE_G = pad_plane(TH * TW), PLANE_X = pad_plane(HALO_H * XP);
     constexpr int G_ELEMS = CO_S * PLANE_G, X_ELEMS = CI_S * PLANE_X;
-    constexpr int NACC = WINO ? 16 : 9;
     // Winograd form: a wave owns ONE 16-channel input group and ALL the slice's output groups (COT accumulator sets): the 4x4 input
     // patch transform B^T d B -- two thirds of the form's VALU work -- is then done once per (tile, input group), not once per
     // (cout, cin) wave pair as in the direct form's mapping (round 3: 2.75 -> 1.75 VALU instructions per MFMA on 32 x 32 slices).
     // (where the registers allow: the 8-wave 32 x 32 slices with plain / pooled input; 4-wave workgroups stage twice the tile per
     // thread and spilled 70 - 160 registers with two accumulator sets, the bilinear instance 56)
-    constexpr bool SHARE = WINO && NW == 8 && RES != NGAN_RESAMPLE_UP2;
+    constexpr bool SHARE = NW == 8 && RES != NGAN_RESAMPLE_UP2;
     constexpr int CW = SHARE ? COT : 1;                          // output groups per wave
     constexpr int WQ = (COT / CW) * CIT;                         // wave groups over (output group sets, input groups)
-    constexpr int WRW = NW / WQ, RPWW = TH / WRW;                // Winograd: row groups, rows per wave
-    static_assert(!WINO || (NW % WQ == 0 && TH % WRW == 0 && RPWW % WSTEP_ROWS == 0), "Winograd wave split");
-    constexpr int RED_WINO = NW * 9 * 64 * 4;                    // every wave's 9 back-transformed taps of one output group
-    constexpr int RED_ELEMS = WINO ? RED_WINO : NW * 9 * 64 * 4;
+    constexpr int WRW = NW / WQ, RPWW = TH / WRW;                // row groups, rows per wave
+    static_assert(NW % WQ == 0 && TH % WRW == 0 && RPWW % WSTEP_ROWS == 0, "Winograd wave split");
+    constexpr int RED_ELEMS = NW * 9 * 64 * 4;                   // every wave's 9 back-transformed taps of one output group
     // bilinear input: the low-resolution source patch of the halo tile is loaded once (fp32, [py][px][CI_S]) and expanded LDS -> LDS,
     // as in wgrad_bf16x3_kernel: 2 global loads per thread instead of 24, and the tap / weight arithmetic is tile-invariant
     constexpr int PH = TH / 2 + 2, PW = TW / 2 + 2, NPP = PH * PW;
     constexpr int PATCH_ELEMS = RES == NGAN_RESAMPLE_UP2 ? NPP * CI_S : 0;
     constexpr int SMEM = (G_ELEMS + X_ELEMS + PATCH_ELEMS) > RED_ELEMS ? (G_ELEMS + X_ELEMS + PATCH_ELEMS) : RED_ELEMS;
     constexpr int NG = TH * TW * (CO_S / 4) / NT, NXI = HALO_H * (TW + 2) * (CI_S / 4), NX = (NXI + NT - 1) / NT;
-    static_assert(TH * TW * (CO_S / 4) % NT == 0 && TH % WR == 0 && NW % WO == 0, "tile split");
+    static_assert(TH * TW * (CO_S / 4) % NT == 0, "tile split");
     // XF: plain input on an image whose width is a multiple of the 32-pixel tile -- the x tile is staged like conv3x3_tile_kernel's
     // (interior columns by whole loads at constant per-lane offsets, the descriptor base moved per tile, the top halo row behind a
     // zero-record descriptor, the two halo columns in one extra load): ~50 fewer VALU instructions per wave and tile
@@ -130,8 +97,6 @@ __global__ __launch_bounds__(NW * 64, (WINO && !XF && COT * CIT == 1) ? 2 : (COT
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int p = lane & 15, q = lane >> 4;
-    const int wo = wave % WO, wr = wave / WO;
-    const int cot = wo / CIT, cit = wo % CIT;        // this wave's 16x16 (cout, cin) sub-slice, all 9 taps
     const int slice = blockIdx.y;
     const int co0 = (slice / a.n_ci_slices) * CO_S, ci0 = (slice % a.n_ci_slices) * CI_S;
 
@@ -170,15 +135,12 @@ __global__ __launch_bounds__(NW * 64, (WINO && !XF && COT * CIT == 1) ? 2 : (COT
         xf_bits = used ? ((side ? 2 : 1) | (r == 0 ? 4 : 0)) : 8;
     }
 
-    f32x4 acc[WINO ? 1 : NACC];                      // direct form: one (cout, cin) sub-slice per wave
-    f32x4 accw[WINO ? CW : 1][16];                   // Winograd form: CW output groups of the slice, one input group
+    f32x4 accw[CW][16];                              // CW output groups of the slice, one input group
 #pragma unroll
-    for (int t = 0; t < (WINO ? 1 : NACC); ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < (WINO ? CW : 1); ++c)
+    for (int c = 0; c < CW; ++c)
 #pragma unroll
         for (int t = 0; t < 16; ++t) accw[c][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int wqw = wave % WQ, wrw = wave / WQ;      // Winograd: this wave's (output group set, input group) and row group
+    const int wqw = wave % WQ, wrw = wave / WQ;      // this wave's (output group set, input group) and row group
     const int citw = wqw % CIT, cot0w = (wqw / CIT) * CW;
 
     float4 gst[NG], xst[XF ? NXF : (RES == NGAN_RESAMPLE_UP2 ? NXP : NX)];
@@ -240,20 +202,12 @@ __global__ __launch_bounds__(NW * 64, (WINO && !XF && COT * CIT == 1) ? 2 : (COT
         }
     };
 
-    // this lane's operand addresses inside a (row, 16-pixel block): channel plane p of its sub-slice, pixels 4q ..
-    const float* ga = g_lds + (cot * 16 + p) * PLANE_G + 4 * q;
-    const float* xa = x_lds + (cit * 16 + p) * PLANE_X + 4 * q;
-
     int tile = blockIdx.x;
     const TileWalk walk(a.tiles_x, a.tiles_y, gridDim.x);       // tiles blockIdx.x, + gridDim.x, ...: decoded once, then advanced (conv3x3_internal.h)
     TileCursor cur_tile = walk.at(tile), next_tile = walk.next(cur_tile);
     if (tile < a.n_tiles) issue(cur_tile);
-    PHASE_INIT;
     while (tile < a.n_tiles) {
         __syncthreads();
-        PHASE_STAMP(0);
-        PHASE_WAIT_LOADS;
-        PHASE_STAMP(1);
 #pragma unroll
         for (int i = 0; i < NG; ++i) {
             float* d = g_lds + g_l[i];
@@ -298,20 +252,16 @@ __global__ __launch_bounds__(NW * 64, (WINO && !XF && COT * CIT == 1) ? 2 : (COT
                     d[0] = xst[i].x; d[PLANE_X] = xst[i].y; d[2 * PLANE_X] = xst[i].z; d[3 * PLANE_X] = xst[i].w;
                 }
         }
-        PHASE_STAMP(2);
         __syncthreads();
-        PHASE_STAMP(3);
         const int tn = tile + gridDim.x;
         if (tn < a.n_tiles) issue(next_tile);   // next tile's loads are in flight during the MFMAs
-        PHASE_STAMP(4);
-        if (WINO) {
-            // this wave's tile rows: output rows row0, row0 + 1 = halo rows row0 .. row0 + 3.  Signs: A = [1 0; 1 1; 1 -1; 0 -1] is used
-            // without the minus signs of its last row (one negation per element saved); the back-transform flips the sign of every
-            // position with u = 3 xor v = 3 instead.
-            // lane (p, q) owns the four consecutive tiles 4 q .. 4 q + 3 of the row (K-step ks contracts tiles 4 q + ks over q): two tiles
-            // at a time are one 16-byte + one 8-byte read per input row and one 16-byte read per gradient row and output group
+        // this wave's tile rows: output rows row0, row0 + 1 = halo rows row0 .. row0 + 3.  Signs: A = [1 0; 1 1; 1 -1; 0 -1] is used
+        // without the minus signs of its last row (one negation per element saved); the back-transform flips the sign of every
+        // position with u = 3 xor v = 3 instead.
+        // lane (p, q) owns the four consecutive tiles 4 q .. 4 q + 3 of the row (K-step ks contracts tiles 4 q + ks over q): two tiles
+        // at a time are one 16-byte + one 8-byte read per input row and one 16-byte read per gradient row and output group
 #pragma unroll
-            for (int tr = 0; tr < RPWW / WSTEP_ROWS; ++tr) {
+        for (int tr = 0; tr < RPWW / WSTEP_ROWS; ++tr) {
             const int row0 = wrw * RPWW + WSTEP_ROWS * tr + (TW == 32 ? 0 : 2 * (q >> 1)), col0 = 8 * (TW == 32 ? q : (q & 1));
             const float* gp = g_lds + (cot0w * 16 + p) * PLANE_G + row0 * TW + col0;       // + c * 16 * PLANE_G per output group
             const float* xp = x_lds + (citw * 16 + p) * PLANE_X + row0 * XP + col0;
@@ -355,107 +305,61 @@ __global__ __launch_bounds__(NW * 64, (WINO && !XF && COT * CIT == 1) ? 2 : (COT
                         for (int u = 0; u < 4; ++u)
 #pragma unroll
                             for (int v = 0; v < 4; ++v)
-                                accw[WINO ? co : 0][u * 4 + v] = __builtin_amdgcn_mfma_f32_16x16x4f32(M[u][v], V[u][v], accw[WINO ? co : 0][u * 4 + v], 0, 0, 0);
+                                accw[co][u * 4 + v] = __builtin_amdgcn_mfma_f32_16x16x4f32(M[u][v], V[u][v], accw[co][u * 4 + v], 0, 0, 0);
                     }
                 }
             }
-            }
-        } else
-#pragma unroll
-        for (int rr = 0; rr < RPW; ++rr) {
-            const int r = wr * RPW + rr;
-#pragma unroll
-            for (int blk = 0; blk < NBLK; ++blk) {
-                const float4 av4 = ld4(ga + r * TW + blk * 16);
-                const float av[4] = {av4.x, av4.y, av4.z, av4.w};
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy) {
-                    const float* xr = xa + (r + dy) * XP + blk * 16;
-                    const float4 b0 = ld4(xr);
-                    const float2 b1 = *reinterpret_cast<const float2*>(xr + 4);
-                    const float bv[6] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y};
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            acc[dy * 3 + dx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[j + dx], acc[dy * 3 + dx], 0, 0, 0);
-                }
-            }
         }
-        PHASE_STAMP(5);
         tile = tn;
         cur_tile = next_tile;
         next_tile = walk.next(next_tile);
     }
 
-    // ---- sum the WR row-waves of each sub-slice through LDS (fixed order), then write this block's slab ----
+    // ---- back-transform, sum the row-group waves through LDS (fixed order), then write this block's slab ----
     __syncthreads();
-    PHASE_STAMP(6);
     float4* red = reinterpret_cast<float4*>(smem);
     float* slab = a.partial + ((long)blockIdx.x * gridDim.y + slice) * (9 * CO_S * CI_S);
-    if (!WINO) {
+    // The back-transform  dW = G^T [ s . dU ] G  (G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]; s = -1 where u = 3 xor v = 3, MFMA section) is linear
+    // and lane-local -- a lane holds all 16 positions of its (cout quad, cin) entries -- so every wave applies it to its OWN partial sums
+    // first (once per launch: ~35 float4 operations per output group) and the waves then exchange 9 taps instead of 16 positions, in ONE
+    // round per output group: two barriers per group instead of eleven in all.  (Round 4: the phase timer showed the old tail -- four
+    // position passes, row transform and column transform each through LDS -- at 30 % of a wave's life on the 64 -> 64 layers, two
+    // tiles per workgroup.)  The summation order changes (transform, then the fixed-order sum over the row-group waves), the bits of a
+    // run stay reproducible.
 #pragma unroll
-        for (int t = 0; t < NACC; ++t)
-            red[(wave * NACC + t) * 64 + lane] = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
-        __syncthreads();
-    }
-    if (WINO) {
-        // The back-transform  dW = G^T [ s . dU ] G  (G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]; s = -1 where u = 3 xor v = 3, MFMA section) is linear
-        // and lane-local -- a lane holds all 16 positions of its (cout quad, cin) entries -- so every wave applies it to its OWN partial sums
-        // first (once per launch: ~35 float4 operations per output group) and the waves then exchange 9 taps instead of 16 positions, in ONE
-        // round per output group: two barriers per group instead of eleven in all.  (Round 4: the phase timer showed the old tail -- four
-        // position passes, row transform and column transform each through LDS -- at 30 % of a wave's life on the 64 -> 64 layers, two
-        // tiles per workgroup.)  The summation order changes (transform, then the fixed-order sum over the row-group waves), the bits of a
-        // run stay reproducible.
+    for (int c = 0; c < CW; ++c) {
+        if (c) __syncthreads();                              // the previous group's readers are done with `red`
+        // one column j of the 3 x 3 result at a time (Z[.][j] needs the whole row of positions, dW[.][j] the four Z[.][j]): seven live
+        // float4s beside the accumulators, written to LDS as they are finished -- all nine at once cost 45 spilled registers in the
+        // dominant instance
 #pragma unroll
-        for (int c = 0; c < CW; ++c) {
-            if (c) __syncthreads();                              // the previous group's readers are done with `red`
-            // one column j of the 3 x 3 result at a time (Z[.][j] needs the whole row of positions, dW[.][j] the four Z[.][j]): seven live
-            // float4s beside the accumulators, written to LDS as they are finished -- all nine at once cost 45 spilled registers in the
-            // dominant instance
+        for (int j = 0; j < 3; ++j) {
+            f32x4 Zj[4];
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                f32x4 Zj[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const f32x4 d1 = accw[WINO ? c : 0][u * 4 + 1], d2 = accw[WINO ? c : 0][u * 4 + 2];
-                    const float su = u == 3 ? -1.f : 1.f;
-                    Zj[u] = j == 0 ? (accw[WINO ? c : 0][u * 4 + 0] + (d1 + d2) * 0.5f) * su
-                          : j == 1 ? ((d1 - d2) * 0.5f) * su
-                                   : ((d1 + d2) * 0.5f - accw[WINO ? c : 0][u * 4 + 3]) * su;
-                }
-                const f32x4 p12 = (Zj[1] + Zj[2]) * 0.5f, m12 = (Zj[1] - Zj[2]) * 0.5f;
-                const f32x4 w0 = Zj[0] + p12, w2 = p12 + Zj[3];
-                red[(wave * 9 + 0 * 3 + j) * 64 + lane] = make_float4(w0[0], w0[1], w0[2], w0[3]);      // wave = wrw * WQ + wqw
-                red[(wave * 9 + 1 * 3 + j) * 64 + lane] = make_float4(m12[0], m12[1], m12[2], m12[3]);
-                red[(wave * 9 + 2 * 3 + j) * 64 + lane] = make_float4(w2[0], w2[1], w2[2], w2[3]);
+            for (int u = 0; u < 4; ++u) {
+                const f32x4 d1 = accw[c][u * 4 + 1], d2 = accw[c][u * 4 + 2];
+                const float su = u == 3 ? -1.f : 1.f;
+                Zj[u] = j == 0 ? (accw[c][u * 4 + 0] + (d1 + d2) * 0.5f) * su
+                      : j == 1 ? ((d1 - d2) * 0.5f) * su
+                               : ((d1 + d2) * 0.5f - accw[c][u * 4 + 3]) * su;
             }
-            __syncthreads();
-            if (c == 0) PHASE_STAMP(7);
-            // item (l, tap t, oi): wave group oi = (output group set, input group) of this pass, summed over its WRW row-group waves in fixed order
-            for (int item = tid; item < WQ * 9 * 64; item += NT) {
-                const int l = item & 63, t = (item >> 6) % 9, oi = (item >> 6) / 9;
-                float4 v = red[(oi * 9 + t) * 64 + l];
-#pragma unroll
-                for (int w = 1; w < WRW; ++w) v = f4add(v, red[((w * WQ + oi) * 9 + t) * 64 + l]);
-                const int ci_l = (oi % CIT) * 16 + (l & 15), co_l = ((oi / CIT) * CW + c) * 16 + 4 * (l >> 4);
-                float* op = slab + ((long)t * CO_S + co_l) * CI_S + ci_l;
-                op[0] = v.x; op[CI_S] = v.y; op[2 * CI_S] = v.z; op[3 * CI_S] = v.w;
-            }
+            const f32x4 p12 = (Zj[1] + Zj[2]) * 0.5f, m12 = (Zj[1] - Zj[2]) * 0.5f;
+            const f32x4 w0 = Zj[0] + p12, w2 = p12 + Zj[3];
+            red[(wave * 9 + 0 * 3 + j) * 64 + lane] = make_float4(w0[0], w0[1], w0[2], w0[3]);      // wave = wrw * WQ + wqw
+            red[(wave * 9 + 1 * 3 + j) * 64 + lane] = make_float4(m12[0], m12[1], m12[2], m12[3]);
+            red[(wave * 9 + 2 * 3 + j) * 64 + lane] = make_float4(w2[0], w2[1], w2[2], w2[3]);
         }
-        PHASE_STAMP(8);
-        PHASE_STAMP(9);
-        PHASE_FLUSH;
-        return;
-    }
-    for (int e = tid; e < WO * 9 * 64; e += NT) {
-        const int l = e & 63, t = (e >> 6) % 9, o = (e >> 6) / 9;
-        float4 v = red[(o * 9 + t) * 64 + l];               // wave index = wr*WO + wo
+        __syncthreads();
+        // item (l, tap t, oi): wave group oi = (output group set, input group) of this pass, summed over its WRW row-group waves in fixed order
+        for (int item = tid; item < WQ * 9 * 64; item += NT) {
+            const int l = item & 63, t = (item >> 6) % 9, oi = (item >> 6) / 9;
+            float4 v = red[(oi * 9 + t) * 64 + l];
 #pragma unroll
-        for (int k = 1; k < WR; ++k) v = f4add(v, red[((k * WO + o) * 9 + t) * 64 + l]);
-        const int ci_l = (o % CIT) * 16 + (l & 15), co_l = (o / CIT) * 16 + 4 * (l >> 4);
-        float* op = slab + ((long)t * CO_S + co_l) * CI_S + ci_l;
-        op[0] = v.x; op[CI_S] = v.y; op[2 * CI_S] = v.z; op[3 * CI_S] = v.w;
+            for (int w = 1; w < WRW; ++w) v = f4add(v, red[((w * WQ + oi) * 9 + t) * 64 + l]);
+            const int ci_l = (oi % CIT) * 16 + (l & 15), co_l = ((oi / CIT) * CW + c) * 16 + 4 * (l >> 4);
+            float* op = slab + ((long)t * CO_S + co_l) * CI_S + ci_l;
+            op[0] = v.x; op[CI_S] = v.y; op[2 * CI_S] = v.z; op[3 * CI_S] = v.w;
+        }
     }
 }
 
@@ -808,7 +712,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 }
 
 struct WgradPlan { int co_s, ci_s, nslices, n_ci_slices, tiles_x, tiles_y, n_tiles, nwx, tw; };
-constexpr int wgrad_f32_waves(int cot, int cit) { return cot * cit == 4 ? NGAN_WGRAD_W22 : 4; }    // a 32 x 32 slice: one wave (round 2: two) per 16 x 16 sub-slice
+constexpr int wgrad_f32_waves(int cot, int cit) { return cot * cit == 4 ? 8 : 4; }    // a 32 x 32 slice: one wave (round 2: two) per 16 x 16 sub-slice
 
 WgradPlan plan_wgrad(int B, int H, int W, int Cin, int Cout, int precision = 1) {
     WgradPlan p;
@@ -817,26 +721,23 @@ WgradPlan plan_wgrad(int B, int H, int W, int Cin, int Cout, int precision = 1) 
     p.tiles_y = ngan::ceil_div(H, 256 / p.tw);
     p.n_tiles = B * p.tiles_x * p.tiles_y;
     // fp32 layers with at most 32 channels on either side: 16 x 16 slices -- four times the workgroups of a 32 x 32 slicing, three
-    // resident per CU instead of one 8-wave workgroup.  Measured per tile count (NGAN_WGRAD_SMALL = threshold, round 3): 32 -> 32 at
+    // resident per CU instead of one 8-wave workgroup.  Measured per tile-count threshold (round 3): 32 -> 32 at
     // 64x64, batch 16 / 32: 23.6 -> 18.5 / 29.3 -> 25.6 us; at 128x128, batch 16: 43.6 -> 41.0; batch 32: 71.0 -> 71.4; 32 -> 16 at 256x256:
     // 77.5 -> 74.1; whole iteration 7.29 -> 7.25 ms with no threshold at all, which is what stays.
-    const bool small = precision == 0 && Cin <= 32 && Cout <= 32 && p.tw == 32 && p.n_tiles <= NGAN_WGRAD_SMALL;
+    const bool small = precision == 0 && Cin <= 32 && Cout <= 32 && p.tw == 32;
     p.co_s = (Cout % 32 == 0 && !small) ? 32 : 16;
     p.ci_s = (Cin % 32 == 0 && !small) ? 32 : 16;
     p.n_ci_slices = Cin / p.ci_s;
     p.nslices = (Cout / p.co_s) * p.n_ci_slices;
-    const int forced = NGAN_DIAG_INT("NGAN_WGRAD_SLABS", 0);
     // about two resident workgroups per CU: few slabs to reduce afterwards (256 / 768 measured slower).  The fp32 kernel's 32 x 32
     // slices are 8-wave workgroups with 83 KB of LDS, one per CU: 256 of them (fp32 32 -> 32 at 128x128: 100 vs 106 us, 64 -> 64 at
     // 32x32: 33 vs 39 us)
-    const int total = forced > 0 ? forced : ((precision == 0 && p.co_s == 32 && p.ci_s == 32 && NGAN_WGRAD_W22 == 8) ? 256 : 512);
+    const int total = (precision == 0 && p.co_s == 32 && p.ci_s == 32) ? 256 : 512;
     int cap = total / p.nslices;
     if (cap < 1) cap = 1;
     p.nwx = p.n_tiles < cap ? p.n_tiles : cap;
     return p;
 }
-
-inline bool wgrad_wino_on() { return NGAN_DIAG_FLAG("NGAN_WINOGRAD_WGRAD", true); }   // (one latch for the launch and its label)
 
 template <int COT, int CIT>
 int launch_wgrad(const WgradArgs& a, const WgradPlan& p, int res, int precision, hipStream_t s) {
@@ -868,32 +769,17 @@ int launch_wgrad(const WgradArgs& a, const WgradPlan& p, int res, int precision,
         return ngan::launch_status("ngan_conv3x3_wgrad(bf16x3, 16x16 tiles)");
     }
     constexpr int NW = wgrad_f32_waves(COT, CIT);
-    if (wgrad_wino_on() && p.tw == 16 && NGAN_WGRAD_WINO16) {
+    if (p.tw == 16) {
         if (res == 0) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 0, 16, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
         else if (res == 1) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 1, 16, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
         else hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 2, 16, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
         return ngan::launch_status("ngan_conv3x3_wgrad(f32, winograd, 16 x 16 tiles)");
     }
-    if (wgrad_wino_on() && p.tw == 32) {
-        if (res == 0 && a.W % 32 == 0) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 0, 32, NW, 1, 1>), grid, dim3(NW * 64), 0, s, a);
-        else if (res == 0) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 0, 32, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
-        else if (res == 1) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 1, 32, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
-        else hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 2, 32, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
-        return ngan::launch_status("ngan_conv3x3_wgrad(f32, winograd)");
-    }
-    if (p.tw == 32) {
-#ifdef NGAN_DIAG                                   // the direct form on 8 x 32 tiles: reachable with NGAN_WINOGRAD_WGRAD=0 only
-        if (res == 0 && a.W % 32 == 0) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 0, 32, NW, 1>), grid, dim3(NW * 64), 0, s, a);
-        else if (res == 0) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 0, 32, NW, 0>), grid, dim3(NW * 64), 0, s, a);
-        else if (res == 1) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 1, 32, NW, 0>), grid, dim3(NW * 64), 0, s, a);
-        else hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 2, 32, NW, 0>), grid, dim3(NW * 64), 0, s, a);
-#endif
-    } else {
-        if (res == 0) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 0, 16, NW, 0>), grid, dim3(NW * 64), 0, s, a);
-        else if (res == 1) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 1, 16, NW, 0>), grid, dim3(NW * 64), 0, s, a);
-        else hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 2, 16, NW, 0>), grid, dim3(NW * 64), 0, s, a);
-    }
-    return ngan::launch_status("ngan_conv3x3_wgrad(f32)");
+    if (res == 0 && a.W % 32 == 0) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 0, 32, NW, 1, 1>), grid, dim3(NW * 64), 0, s, a);
+    else if (res == 0) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 0, 32, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
+    else if (res == 1) hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 1, 32, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
+    else hipLaunchKernelGGL((wgrad_f32_kernel<COT, CIT, 2, 32, NW, 0, 1>), grid, dim3(NW * 64), 0, s, a);
+    return ngan::launch_status("ngan_conv3x3_wgrad(f32, winograd)");
 }
 
 }  // namespace
@@ -906,11 +792,8 @@ extern "C" int ngan_conv3x3_wgrad_kernel_name(int B, int H, int W, int Cin, int 
     const char* xf = (resample == 0 && p.tw == 32 && W % 32 == 0) ? "true" : "false";
     if (precision == 1) snprintf(buf, len, "wgrad_bf16x3_kernel<%d, %d, %d, %d, false, %s>", p.co_s / 16, p.ci_s / 16, resample, p.tw, xf);
     else if (precision == 5) snprintf(buf, len, "wgrad_bf16x3_kernel<%d, %d, %d, %d, true, %s>", p.co_s / 16, p.ci_s / 16, resample, p.tw, xf);
-    else {
-        const bool wino = wgrad_wino_on() && (p.tw == 32 || NGAN_WGRAD_WINO16);
-        snprintf(buf, len, "wgrad_f32_kernel<%d, %d, %d, %d, %d, %d, %d>", p.co_s / 16, p.ci_s / 16, resample, p.tw,
-                 wgrad_f32_waves(p.co_s / 16, p.ci_s / 16), (resample == 0 && p.tw == 32 && W % 32 == 0) ? 1 : 0, wino ? 1 : 0);
-    }
+    else snprintf(buf, len, "wgrad_f32_kernel<%d, %d, %d, %d, %d, %d, 1>", p.co_s / 16, p.ci_s / 16, resample, p.tw,
+                  wgrad_f32_waves(p.co_s / 16, p.ci_s / 16), (resample == 0 && p.tw == 32 && W % 32 == 0) ? 1 : 0);
     return NGAN_OK;
 }
 
@@ -1079,16 +962,3 @@ extern "C" int ngan_bf16_conv3x3_wgrad(const ngan_bf16* x, const ngan_bf16* g, f
     return wgrad_entry(reinterpret_cast<const float*>(x), reinterpret_cast<const float*>(g), gw, workspace, B, H, W, Cin, Cout, resample, scale,
                        accumulate, 5, stream);
 }
-
-#ifdef NGAN_DIAG_PHASES
-// phase-timer build only (not declared in include/ngan.h): copies the phase counters of wgrad_f32_kernel out and optionally zeroes them
-extern "C" int ngan_diag_wgrad_phases(unsigned long long* out11, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (hipMemcpyFromSymbol(out11, HIP_SYMBOL(wgrad_phase_ctr), 15 * sizeof(unsigned long long)) != hipSuccess) return 1;
-    if (reset) {
-        const unsigned long long z[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, ~0ull, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(wgrad_phase_ctr), z, sizeof(z)) != hipSuccess) return 1;
-    }
-    return 0;
-}
-#endif

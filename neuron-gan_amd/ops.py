@@ -36,15 +36,8 @@ EPI_NONE, EPI_LRELU_PN, EPI_PN_BWD, EPI_TO_IMAGE = 0, 1, 2, 3      # epilogues o
 # then lets the consumer's input-gradient kernel apply the producer's LeakyReLU->PixelNorm backward in its epilogue: the gradient
 # w.r.t. the producer's output is never written and re-read, and the producer's own PixelNorm-backward launch disappears.
 # ---------------------------------------------------------------------------------------------------------
-def _diag_env(name, default):
-    """Measurement A/B switches are honoured only with NGAN_DIAG=1 in the environment (tools/ab_env.sh sets it): a stray variable must
-    not change which kernels a training run or a parity test exercises.  (The documented user knobs are NGAN_CONV_PRECISION and
-    NGAN_LIB_PATH; the kernel library itself reads no environment variable.)"""
-    return os.environ.get(name, default) if os.environ.get("NGAN_DIAG") == "1" else default
-
-
 _first_order = 0
-_first_order_allowed = _diag_env("NGAN_FIRST_ORDER_FUSION", "1") != "0"     # A/B switch for measurements and tests
+_first_order_allowed = True     # off only for a sensitivity run (tools/c2_sensitivity.py)
 
 
 def allow_first_order_fusion(flag):
@@ -266,11 +259,10 @@ def _pool_first(resample):
     quarter-size tensor with plain input (the Winograd / tile / mid kernels at 0.6 - 0.9 of the fp32 MFMA peak) instead of pooling
     inside the generic kernel's staging (four dependent loads per staged element: 0.3 - 0.35).  The pooled copy also serves the
     weight gradient of the same layer.  (nn.AvgPool2d in front of a block's first conv, reference models.py:252-254.)"""
-    return resample == RES_POOL2 and _conv_precision == 0 and _pool_first_allowed
+    return resample == RES_POOL2 and _conv_precision == 0
 
 
-_pool_first_allowed = _diag_env("NGAN_POOL_FIRST", "1") != "0"     # A/B switch for measurements and tests
-_pool_out_allowed = _diag_env("NGAN_POOL_OUT", "1") != "0"         # A/B switch: pooled side output of the producing conv
+_pool_out_allowed = True     # pooled side output of the producing conv (off: the bit-equality reference of the tests)
 
 
 def _pooled_side(x):
@@ -528,7 +520,7 @@ def _accumulates_in_place(weight):
 # Small parameter gradients (biases, FromImage / ToImage / head weights) are added into the parameter's existing .grad buffer by the
 # kernel that computes them -- like the conv weight gradients -- instead of being handed to autograd, whose AccumulateGrad adds each
 # with an elementwise launch of its own (13 such launches per iteration in the round-3 kernel trace)
-_small_grads_in_place = _diag_env("NGAN_SMALL_GRADS_IN_PLACE", "1") != "0"
+_small_grads_in_place = True     # (off: the bit-equality reference of the tests)
 
 
 def _channel_sum(g, into=None):
@@ -906,7 +898,7 @@ class FromImage(Function):
         return gx, gw, gb, None
 
 
-_first_block_allowed = _diag_env("NGAN_FIRST_BLOCK", "1") != "0"      # A/B switch for measurements
+_first_block_allowed = True      # off only for a sensitivity run (tools/first_block_sensitivity.py)
 
 
 def first_block_fusable(x, w_from, w_conv):

@@ -318,7 +318,7 @@ class PGGANTrainer:
         # The generator stem's weight gradient is not stored when the stem qualifies (GPU, latent_dim a multiple of 16, at most 512):
         # g_step hands its factors to the Adam launch (FusedAdam.step).  g_compute on its own still stores it.  fused_stem=False: never.
         self.fused_stem = False
-        if fused_stem or (fused_stem is None and self.device.type == "cuda" and ops._diag_env("NGAN_FUSED_STEM_ADAM", "1") != "0"):
+        if fused_stem or (fused_stem is None and self.device.type == "cuda"):
             self.enable_fused_stem()
         self.force_exchange = False
         self.last_z_g = None
@@ -635,7 +635,7 @@ class PGGANTrainer:
         # capture mode refuses such a call from ANY thread while a capture is active (hipErrorStreamCaptureUnsupported -> the
         # watchdog terminates the process); thread_local polices the capturing thread only.  The second rule (an event whose stream
         # is part of the capture) is what _on_comm_stream takes care of.  Both reproduced case by case: tools/capture_event_probe.py.
-        mode = ops._diag_env("NGAN_CAPTURE_MODE", "") or ("thread_local" if self._comm_stream is not None else "global")
+        mode = "thread_local" if self._comm_stream is not None else "global"
         # No cyclic garbage collection while a capture is active: a collection that happens to start inside the captured region runs
         # the finalizers of whatever cyclic garbage earlier code left behind on the capturing thread.  The one that must not run there
         # is torch.cuda.CUDAGraph's: destroying an EARLIER captured graph (hipGraphExecDestroy / hipGraphDestroy and the release of its

@@ -1,5 +1,5 @@
 // Does s_memtime (the shader clock counter) keep counting while a CU has nothing to issue?  Calibration of the in-kernel clock probe
-// (s_memtime / s_memrealtime) of tools/wgrad_phases.py:   hipcc --offload-arch=gfx950 -O3 tools/micro/clock_gate.hip -o tools/micro/clock_gate && tools/micro/clock_gate
+// (s_memtime / s_memrealtime) behind the round-4 phase-timer records (profiles/r04_*_phases.txt):   hipcc --offload-arch=gfx950 -O3 tools/micro/clock_gate.hip -o tools/micro/clock_gate && tools/micro/clock_gate
 // One wave per CU (256 blocks of 64 threads): kind 0 = a dependent pointer chase through 64 MB (the wave waits for memory almost all the
 // time, the CU is idle), 1 = s_sleep loops (parked), 2 = a dependent v_fma chain (always issuing).  Prints shader cycles per ns.
 #include <hip/hip_runtime.h>
