@@ -474,6 +474,30 @@ int ngan_tanh_bwd(const float* t, const float* g, float* out, long n, void* stre
 int ngan_wgan_stem_fwd(const float* z, const float* W, const float* bias, float* y, int B, int K, int S, int C, void* stream);
 int ngan_wgan_stem_grad(const float* z, const float* g, float* gW, float* gb, int B, int K, int S, int C, void* stream);
 
+/* ---- synchronised BatchNorm2d for the data-parallel WGAN trainer (WGANTrainer(sync_batchnorm=True)) ----------------------------------
+ * Each rank reduces its own pixels into an fp64 record, the caller all-gathers the records (rank order 0 .. world-1 in `recs`), and
+ * every rank merges the same bytes in the same order: bit-identical statistics on every rank.  The single-GPU entry points above are
+ * unchanged; no float atomics here either.
+ * ngan_bn_moments: rec (1 + 2C doubles) = [count, mean[C], M2[C]] of y (npix, C), M2 = sum (y - mean)^2 (from sums shifted by the
+ *     channel's first pixel: no cancellation).  work: ngan_chan_reduce_workspace_floats(npix, C) floats.
+ * ngan_bn_merge_fold: merges world records (world x (1 + 2C) doubles) in rank order, pairwise (Chan et al.): n = na + nb,
+ *     d = mean_b - mean_a, mean = mean_a + d*nb/n, M2 = M2_a + M2_b + d^2*na*nb/n.  Then writes what ngan_bn_stats writes from the
+ *     global N and M2: mean, rstd = 1/sqrt(M2/N + eps), scale, shift, running statistics (variance M2/(N-1)), *nbt += 1 -- and
+ *     n_total[0] = N (one double on the device, for the backward).
+ * ngan_bn_act_bwd_partial: rec (2C doubles) = [S0[C], S1[C]] = sum gz, sum gz*xhat over this rank's pixels, gz = g * act'(scale*y +
+ *     shift), xhat = (y - mean)*rstd with the merged statistics.  work: ngan_chan_reduce_workspace_floats(npix, C) floats.
+ * ngan_bn_act_bwd_merged: sums the world gathered backward records (world x 2C doubles) in rank order and writes
+ *     gy = gamma*rstd*(gz - S0/N - xhat*S1/N), N = n_total[0]; dgamma / dbeta (each may be null) = S1 / S0 of record `rank` only --
+ *     this rank's share, which the data-parallel gradient all-reduce adds up.  work: 3C floats. */
+int ngan_bn_moments(const float* y, long npix, int C, double* rec, float* work, void* stream);
+int ngan_bn_merge_fold(const double* recs, int world, int C, const float* gamma, const float* beta, float* mean, float* rstd, float* scale,
+                       float* shift, float* run_mean, float* run_var, long long* nbt, float momentum, float eps, double* n_total, void* stream);
+int ngan_bn_act_bwd_partial(const float* y, const float* g, const float* scale, const float* shift, const float* mean, const float* rstd,
+                            int act, float slope, long npix, int C, double* rec, float* work, void* stream);
+int ngan_bn_act_bwd_merged(const float* y, const float* g, const float* scale, const float* shift, const float* mean, const float* rstd,
+                           const float* gamma, int act, float slope, long npix, int C, const double* recs, int world, int rank,
+                           const double* n_total, float* gy, float* dgamma, float* dbeta, float* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

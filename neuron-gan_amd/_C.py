@@ -83,6 +83,11 @@ SIGNATURES = {
     "ngan_tanh_bwd": [_P, _P, _P, _L, _P],
     "ngan_wgan_stem_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "ngan_wgan_stem_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    # synchronised BatchNorm of the data-parallel WGAN trainer (include/ngan.h, after the WGAN section)
+    "ngan_bn_moments": [_P, _L, _I, _P, _P, _P],
+    "ngan_bn_merge_fold": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P],
+    "ngan_bn_act_bwd_partial": [_P, _P, _P, _P, _P, _P, _I, _F, _L, _I, _P, _P, _P],
+    "ngan_bn_act_bwd_merged": [_P, _P, _P, _P, _P, _P, _P, _I, _F, _L, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments

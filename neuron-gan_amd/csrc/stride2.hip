@@ -469,6 +469,119 @@ __global__ __launch_bounds__(256) void stem_grad_kernel(const float* __restrict_
     if (gb && k == 0) gb[row] = sb;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// synchronised BatchNorm (data parallel): per-rank records in fp64 that are all-gathered and merged in rank order.
+//   moments record  [count, mean[C], M2[C]]     (M2 = sum of squared deviations from the record's own mean)
+//   backward record [S0[C], S1[C]]               (S0 = sum gz, S1 = sum gz * xhat, xhat from the GLOBAL statistics)
+// The stage-1 partials come from chan_reduce_stage1 as on the single-GPU path; sum_parts_f64 adds them in fp64 with a block of
+// 16 channels x 16 lanes (lane l takes the partials l, l + 16, ... in order, then the channel's thread adds the 16 lane sums in order).
+// ---------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool sum_parts_f64(const float* __restrict__ part, int nparts, int C, double& s0, double& s1, int& c) {
+    __shared__ double sm[2][256];
+    const int t = threadIdx.x;
+    const int cc = blockIdx.x * 16 + (t & 15), lane = t >> 4;
+    double a0 = 0.0, a1 = 0.0;
+    if (cc < C) {
+        for (int k = lane; k < nparts; k += 16) {
+            a0 += (double)part[((long)k * 2 + 0) * C + cc];
+            a1 += (double)part[((long)k * 2 + 1) * C + cc];
+        }
+    }
+    sm[0][t] = a0;
+    sm[1][t] = a1;
+    __syncthreads();
+    c = cc;
+    if (t >= 16 || cc >= C) return false;
+    s0 = 0.0;
+    s1 = 0.0;
+    for (int l = 0; l < 16; ++l) {
+        s0 += sm[0][l * 16 + t];
+        s1 += sm[1][l * 16 + t];
+    }
+    return true;
+}
+
+// shifted sums (pivot y[0, c]) -> this rank's moments record
+__global__ __launch_bounds__(256) void bn_moments_finish(const float* __restrict__ part, int nparts, const float* __restrict__ y, long npix,
+                                                         int C, double* __restrict__ rec) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) rec[0] = (double)npix;
+    double s0, s1;
+    int c;
+    if (!sum_parts_f64(part, nparts, C, s0, s1, c)) return;
+    const double d = s0 / (double)npix;
+    rec[1 + c] = (double)y[c] + d;
+    rec[1 + C + c] = fmax(s1 - s0 * d, 0.0);
+}
+
+// merge of the gathered moments records in rank order (Chan et al.), then what bn_stats_finish writes, plus the global count
+__global__ __launch_bounds__(256) void bn_merge_fold_kernel(const double* __restrict__ recs, int world, int C, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float* __restrict__ mean, float* __restrict__ rstd,
+                                                            float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ run_mean,
+                                                            float* __restrict__ run_var, long long* __restrict__ nbt, float momentum, float eps,
+                                                            double* __restrict__ n_total) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const long R = 1 + 2L * C;
+    double n = recs[0], mu = recs[1 + c], m2 = recs[1 + C + c];
+    for (int r = 1; r < world; ++r) {
+        const double* q = recs + r * R;
+        const double nb = q[0];
+        const double nn = n + nb;
+        const double d = q[1 + c] - mu;
+        mu += d * (nb / nn);
+        m2 += q[1 + C + c] + d * d * (n * nb / nn);
+        n = nn;
+    }
+    const double var = m2 / n;
+    const float r = (float)(1.0 / sqrt(var + (double)eps));
+    const float muf = (float)mu;
+    mean[c] = muf;
+    rstd[c] = r;
+    const float gs = gamma[c] * r;
+    scale[c] = gs;
+    shift[c] = beta[c] - muf * gs;
+    if (run_mean) {
+        const double unb = n > 1.0 ? m2 / (n - 1.0) : var;
+        run_mean[c] = (float)((1.0 - (double)momentum) * run_mean[c] + (double)momentum * mu);
+        run_var[c] = (float)((1.0 - (double)momentum) * run_var[c] + (double)momentum * unb);
+    }
+    if (c == 0) {
+        n_total[0] = n;
+        if (nbt) nbt[0] += 1;
+    }
+}
+
+// sum gz, sum gz * xhat over this rank's pixels -> its backward record
+__global__ __launch_bounds__(256) void bn_bwd_partial_finish(const float* __restrict__ part, int nparts, int C, double* __restrict__ rec) {
+    double s0, s1;
+    int c;
+    if (!sum_parts_f64(part, nparts, C, s0, s1, c)) return;
+    rec[c] = s0;
+    rec[C + c] = s1;
+}
+
+// the gathered backward records summed in rank order -> the coefficients of bn_act_bwd_apply over the global count; dgamma / dbeta are
+// THIS rank's share (the flat gradient all-reduce adds the ranks' shares)
+__global__ __launch_bounds__(256) void bn_bwd_merged_finish(const double* __restrict__ recs, int world, int rank, int C,
+                                                            const double* __restrict__ n_total, const float* __restrict__ gamma,
+                                                            const float* __restrict__ rstd, float* __restrict__ dgamma,
+                                                            float* __restrict__ dbeta, float* __restrict__ coef) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double s0 = 0.0, s1 = 0.0;
+    for (int r = 0; r < world; ++r) {
+        s0 += recs[(long)r * 2 * C + c];
+        s1 += recs[(long)r * 2 * C + C + c];
+    }
+    const double* own = recs + (long)rank * 2 * C;
+    if (dgamma) dgamma[c] = (float)own[C + c];
+    if (dbeta) dbeta[c] = (float)own[c];
+    const double n = n_total[0];
+    coef[c] = gamma[c] * rstd[c];
+    coef[C + c] = (float)(s0 / n);
+    coef[2 * C + c] = (float)(s1 / n);
+}
+
 long red_chunk(long npix, int C, int& nparts) {
     // about 16K elements per workgroup, at most 1024 workgroups
     long chunk = (16384 + C - 1) / C;
@@ -638,6 +751,61 @@ int ngan_wgan_stem_grad(const float* z, const float* g, float* gW, float* gb, in
     const long n = (long)S * C * K;
     hipLaunchKernelGGL(stem_grad_kernel, dim3(ngan::ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, z, g, gW, gb, B, K, S, C);
     return ngan::launch_status("ngan_wgan_stem_grad");
+}
+
+int ngan_bn_moments(const float* y, long npix, int C, double* rec, float* work, void* stream) {
+    NGAN_REQUIRE(y && rec && work, NGAN_ERR_ARG, "bn_moments: null pointer");
+    NGAN_REQUIRE(npix > 0 && C > 0, NGAN_ERR_SHAPE, "bn_moments: npix=%ld C=%d", npix, C);
+    int np;
+    RedArgs a{y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, npix, C, red_chunk(npix, C, np), work};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(chan_reduce_stage1<0>, dim3(np), dim3(256), 0, s, a);
+    int st = ngan::launch_status("ngan_bn_moments");
+    if (st) return st;
+    hipLaunchKernelGGL(bn_moments_finish, dim3(ngan::ceil_div(C, 16)), dim3(256), 0, s, work, np, y, npix, C, rec);
+    return ngan::launch_status("ngan_bn_moments(finish)");
+}
+
+int ngan_bn_merge_fold(const double* recs, int world, int C, const float* gamma, const float* beta, float* mean, float* rstd, float* scale,
+                       float* shift, float* run_mean, float* run_var, long long* nbt, float momentum, float eps, double* n_total, void* stream) {
+    NGAN_REQUIRE(recs && gamma && beta && mean && rstd && scale && shift && n_total, NGAN_ERR_ARG, "bn_merge_fold: null pointer");
+    NGAN_REQUIRE((run_mean == nullptr) == (run_var == nullptr), NGAN_ERR_ARG, "bn_merge_fold: running mean and variance go together");
+    NGAN_REQUIRE(world >= 1 && C > 0, NGAN_ERR_SHAPE, "bn_merge_fold: world=%d C=%d", world, C);
+    hipLaunchKernelGGL(bn_merge_fold_kernel, dim3(ngan::ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, recs, world, C, gamma, beta,
+                       mean, rstd, scale, shift, run_mean, run_var, nbt, momentum, eps, n_total);
+    return ngan::launch_status("ngan_bn_merge_fold");
+}
+
+int ngan_bn_act_bwd_partial(const float* y, const float* g, const float* scale, const float* shift, const float* mean, const float* rstd,
+                            int act, float slope, long npix, int C, double* rec, float* work, void* stream) {
+    NGAN_REQUIRE(y && g && scale && shift && mean && rstd && rec && work, NGAN_ERR_ARG, "bn_act_bwd_partial: null pointer");
+    NGAN_REQUIRE(npix > 0 && C > 0, NGAN_ERR_SHAPE, "bn_act_bwd_partial: npix=%ld C=%d", npix, C);
+    int np;
+    RedArgs a{y, g, scale, shift, mean, rstd, slope, act, npix, C, red_chunk(npix, C, np), work};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(chan_reduce_stage1<1>, dim3(np), dim3(256), 0, s, a);
+    int st = ngan::launch_status("ngan_bn_act_bwd_partial");
+    if (st) return st;
+    hipLaunchKernelGGL(bn_bwd_partial_finish, dim3(ngan::ceil_div(C, 16)), dim3(256), 0, s, work, np, C, rec);
+    return ngan::launch_status("ngan_bn_act_bwd_partial(finish)");
+}
+
+int ngan_bn_act_bwd_merged(const float* y, const float* g, const float* scale, const float* shift, const float* mean, const float* rstd,
+                           const float* gamma, int act, float slope, long npix, int C, const double* recs, int world, int rank,
+                           const double* n_total, float* gy, float* dgamma, float* dbeta, float* work, void* stream) {
+    NGAN_REQUIRE(y && g && scale && shift && mean && rstd && gamma && recs && n_total && gy && work, NGAN_ERR_ARG,
+                 "bn_act_bwd_merged: null pointer");
+    NGAN_REQUIRE(world >= 1 && rank >= 0 && rank < world && npix > 0 && C > 0, NGAN_ERR_SHAPE,
+                 "bn_act_bwd_merged: world=%d rank=%d npix=%ld C=%d", world, rank, npix, C);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_bwd_merged_finish, dim3(ngan::ceil_div(C, 256)), dim3(256), 0, s, recs, world, rank, C, n_total, gamma, rstd,
+                       dgamma, dbeta, work);
+    int st = ngan::launch_status("ngan_bn_act_bwd_merged(finish)");
+    if (st) return st;
+    const long n = npix * C;
+    hipLaunchKernelGGL(bn_act_bwd_apply, dim3(ngan::ceil_div(n, 256)), dim3(256), 0, s, y, g, scale, shift, mean, rstd, work, act, slope, n, C,
+                       gy);
+    return ngan::launch_status("ngan_bn_act_bwd_merged");
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@ Adam], then G loss, backward, Adam) as an engine object instead of module-level 
 The epoch-level semantics (LR schedule train.py:232-265, per-epoch alpha advance and growth train.py:318-333) are
 provided by `lr_schedule` / `PGGANTrainer.start_epoch`; data loading, plotting and checkpoints are out of scope.
 """
+import contextlib
 import math
 import os
 
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _C, ops
+from . import _C, ops, wgan_ops
 from .loss_functions import D_W_loss, D_grad_pen_loss, G_W_loss
 from .utils import sample_latent_vec, sample_latent_vec_device
 
@@ -755,16 +756,29 @@ class WGANTrainer:
     -mean + mean + drift * mean(real^2), backward, optimiser step, clamp every critic parameter to +-clip], then one generator step
     -mean(D(G(z))).  Both nets stay in train mode, so every forward uses batch statistics and updates the BatchNorm running buffers,
     as in the reference.  The critic's parameter gradients of the generator step are not computed.  The clamp is fused into the
-    critic's optimiser launch.  Same interface as PGGANTrainer: step / train_iteration / capture / replay, opt_d / opt_g, last_z_g."""
+    critic's optimiser launch.  Same interface as PGGANTrainer: step / train_iteration / capture / replay, opt_d / opt_g, last_z_g.
+
+    sync_batchnorm=True: data parallel over the ranks of `process_group` (an initialised one; default: the default group).  Every
+    training-mode BatchNorm2d forward inside d_compute / g_compute (so also d_step, g_step, train_iteration, step) normalises with the
+    statistics of the union of all ranks' inputs to that call, updates the running buffers identically on every rank and
+    differentiates through the global statistics; the flat gradients are all-reduced between compute and optimiser step (1/world folded
+    into the optimiser).  Ranks with equal batches then reproduce one rank on the whole batch; a ragged split keeps exact statistics
+    and weights each rank's loss by 1/world, as on the PGGAN path.  Every BatchNorm call is a collective, so every rank must run the
+    same sequence of steps (the same n_critic: no adapt_critic over per-rank series).  Each rank draws its own latents: seed each rank
+    differently.  Eager only: capture() raises and step() runs train_iteration.  Forwards outside the steps (a sample grid on rank 0,
+    eval mode) issue no collective."""
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, drift_epsilon=0.001, n_critic=1, clip=0.01,
-                 optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None):
+                 optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None, sync_batchnorm=False):
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
-        world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
-        if world > 1:
-            raise NotImplementedError("WGANTrainer runs on one GPU: BatchNorm batch statistics per rank would differ from the reference's "
-                                      "(synchronised BatchNorm is not implemented)")
+        grouped = dist.is_available() and dist.is_initialized()
+        if sync_batchnorm and not grouped:
+            raise ValueError("sync_batchnorm=True needs an initialised process group (torch.distributed.init_process_group)")
+        world = dist.get_world_size(process_group) if grouped else 1
+        if world > 1 and not sync_batchnorm:
+            raise NotImplementedError("WGANTrainer runs on one GPU unless sync_batchnorm=True: BatchNorm batch statistics per rank would "
+                                      "differ from the reference's")
         if ops.get_conv_precision() != "f32":
             raise NotImplementedError(f"the WGAN nets run in exact fp32 only; conv precision is {ops.get_conv_precision()!r} "
                                       f"(ops.set_conv_precision('f32'))")
@@ -774,7 +788,9 @@ class WGANTrainer:
         self.drift_epsilon = float(drift_epsilon)
         self.device_latents = device_latents
         self.optimizer_kind = optimizer
-        self.world = 1
+        self.world = world
+        self.group = process_group
+        self.sync_batchnorm = bool(sync_batchnorm)
         opt_cls = OPTIMIZERS[optimizer]
         self.flat_g, self.flat_d = FlatParams(generator, opt_cls.STATE), FlatParams(discriminator, opt_cls.STATE)
         self.flat_g.set_active(self.flat_g.params)
@@ -786,10 +802,36 @@ class WGANTrainer:
             self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps)
             self.opt_d = ClippedFusedRMSprop(self.flat_d, learning_rate, rmsprop_alpha, rmsprop_eps)
         self.opt_d.clip = float(clip)
+        if self.sync_batchnorm:
+            self.opt_g.set_grad_scale(1.0 / world)
+            self.opt_d.set_grad_scale(1.0 / world)
+        self._sync = None             # the wgan_ops.SyncBN handle, made on first use (this rank's index is read from the group then)
+        # collectives of the RCCL backend run on a stream of their own (PGGANTrainer._on_comm_stream)
+        self._comm_stream = None
+        self.comm_timing = None       # tools/wgan_time.py: a list that receives (tag, start event, end event) of every collective
+        if self.sync_batchnorm and self.device.type == "cuda" and dist.get_backend(process_group) == "nccl":
+            self._comm_stream = torch.cuda.Stream(device=self.device)
         self.last_z_g = None
         self._one = torch.ones((), device=self.device)
         self._graphs = {}
         self._graph = self._entry = None
+
+    _on_comm_stream = PGGANTrainer._on_comm_stream
+
+    def _bn_sync(self):
+        """the context of a step's passes: with sync_batchnorm, every training-mode BatchNorm2d call in it uses all ranks' statistics"""
+        if not self.sync_batchnorm:
+            return contextlib.nullcontext()
+        if self._sync is None:
+            self._sync = wgan_ops.SyncBN(self.group, self.world, dist.get_rank(self.group),
+                                         lambda fn: self._on_comm_stream(fn, "batchnorm"))
+        return wgan_ops.synchronised(self._sync)
+
+    def _exchange(self, flat):
+        """sync_batchnorm: all-reduce(SUM) of the net's flat gradient (also on a one-rank group: the RCCL path runs on one GPU too)"""
+        if self.sync_batchnorm:
+            self._on_comm_stream(lambda: exchange_gradients(flat, self.world, self.group, force=True),
+                                 "critic" if flat is self.flat_d else "generator")
 
     def _latent(self, batch, z):
         if z is not None:
@@ -806,17 +848,19 @@ class WGANTrainer:
         b = real.size(0)
         self.flat_d.ensure_grad_views()
         self.flat_d.zero_grad()
-        s_real_all = self.D(real)                                    # D(real), then the latent draw, G(z).detach(), D(fake)
-        z = self._latent(b, z)
-        with torch.no_grad():
-            fake = self.G.forward_nhwc(z)
-        s_fake_all = self.D.forward_nhwc(fake)
-        loss, s_real, s_fake = ops.WLossHead.apply(torch.cat([s_real_all, s_fake_all], dim=0), b, self.drift_epsilon)
-        loss.backward(gradient=self._one)
+        with self._bn_sync():
+            s_real_all = self.D(real)                                # D(real), then the latent draw, G(z).detach(), D(fake)
+            z = self._latent(b, z)
+            with torch.no_grad():
+                fake = self.G.forward_nhwc(z)
+            s_fake_all = self.D.forward_nhwc(fake)
+            loss, s_real, s_fake = ops.WLossHead.apply(torch.cat([s_real_all, s_fake_all], dim=0), b, self.drift_epsilon)
+            loss.backward(gradient=self._one)
         return {"D_loss": loss.detach(), "score_real": s_real.detach(), "score_fake": s_fake.detach()}
 
     def d_step(self, real, z=None):
         stats = self.d_compute(real, z)
+        self._exchange(self.flat_d)
         self.opt_d.step()                                            # + clamp_(-clip, clip) in the same launch
         return stats
 
@@ -830,8 +874,9 @@ class WGANTrainer:
         try:
             z = self._latent(b, z)
             self.last_z_g = z
-            loss = ops.WLossHead.apply(self.D.forward_nhwc(self.G.forward_nhwc(z)), b, 0.0)[0]
-            loss.backward(gradient=self._one)
+            with self._bn_sync():
+                loss = ops.WLossHead.apply(self.D.forward_nhwc(self.G.forward_nhwc(z)), b, 0.0)[0]
+                loss.backward(gradient=self._one)
         finally:
             for p in d_params:
                 p.requires_grad_(True)
@@ -839,6 +884,7 @@ class WGANTrainer:
 
     def g_step(self, real, z=None):
         stats = self.g_compute(real, z)
+        self._exchange(self.flat_g)
         self.opt_g.step()
         return stats
 
@@ -877,6 +923,9 @@ class WGANTrainer:
         """Capture one train_iteration for this batch shape into a graph (PGGANTrainer.capture without the data-parallel segments).
         The warm-up runs on a snapshot (parameters, optimiser state, BatchNorm buffers, the device RNG are restored).
         draws: optional {"z_d": [n_critic static tensors] or one, "z_g": static tensor}, refilled by the caller before each replay."""
+        if self.sync_batchnorm:
+            raise NotImplementedError("sync_batchnorm=True runs eagerly: every training-mode BatchNorm2d call is a collective (48 per "
+                                      "n_critic = 1 iteration at the default widths) and no collective is ever captured")
         if draws is None and not self.device_latents:
             raise RuntimeError("graph capture needs device_latents=True or static draws (CPU-drawn latents cannot be replayed)")
         dr = draws or {}
@@ -929,7 +978,8 @@ class WGANTrainer:
         return entry[2]
 
     def step(self, real, use_graph=True):
-        if use_graph and self.device_latents:
+        """graph replay when possible (capturing on first sight of a shape), else eager; always eager with sync_batchnorm"""
+        if use_graph and self.device_latents and not self.sync_batchnorm:
             if not self.has_graph(real.shape):
                 self.capture(real)
             return self.replay(real)

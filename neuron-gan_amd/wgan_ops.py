@@ -11,8 +11,15 @@ writes its raw convolution output and the normalised activation is never stored,
 Inside `ops.inputs_only()`, or for parameters with requires_grad False, weight / bias / affine gradients are not computed (the
 generator step back-propagates through the critic for its input gradient only).  Every reduction is deterministic: eager runs and
 replayed graphs give the same bits.
+
+Inside `synchronised(handle)` (WGANTrainer with sync_batchnorm=True) a training-mode BatchNorm2d normalises with the statistics of
+all ranks' inputs to that call, and its backward with the ranks' summed Σgz, Σgz·x̂: one all-gather of a small fp64 record per forward
+and one per backward (ngan_bn_moments -> ngan_bn_merge_fold, ngan_bn_act_bwd_partial -> ngan_bn_act_bwd_merged).
 """
+import contextlib
+
 import torch
+import torch.distributed as dist
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
@@ -88,11 +95,42 @@ def chan_sum(g):
     return out
 
 
+class SyncBN:
+    """What a synchronised BatchNorm call needs: the process group, its size, this rank's index in it, and `run(fn)`, which issues the
+    collectives of fn (the trainer's communication-stream runner)."""
+
+    def __init__(self, group, world, rank, run):
+        self.group, self.world, self.rank, self.run = group, int(world), int(rank), run
+
+    def gather(self, rec):
+        """all ranks' records, concatenated in rank order"""
+        out = torch.empty(self.world * rec.numel(), device=rec.device, dtype=rec.dtype)
+        self.run(lambda: dist.all_gather_into_tensor(out, rec, group=self.group))
+        return out
+
+
+_sync = None      # the SyncBN handle of the innermost `synchronised` block; None: per-call batch statistics
+
+
+@contextlib.contextmanager
+def synchronised(handle):
+    global _sync
+    prev, _sync = _sync, handle
+    try:
+        yield
+    finally:
+        _sync = prev
+
+
 class BNSpec:
-    """The BatchNorm2d in front of a consumer: its module (buffers updated in place) and whether it runs on batch statistics."""
+    """The BatchNorm2d in front of a consumer: its module (buffers updated in place) and whether it runs on batch statistics.
+    `sync` is the SyncBN handle current when the forward built this spec; the backward, which autograd runs on another thread, uses the
+    same one."""
 
     def __init__(self, module):
         self.module = module
+        self.sync = _sync
+        self.n_total = None       # synchronised: the global pixel count (one double on the device) the backward divides by
 
     def fold(self, y, gamma, beta):
         """(scale, shift, mean, rstd): the on-load transform; mean / rstd are None in eval mode"""
@@ -106,9 +144,19 @@ class BNSpec:
             if bn.momentum is None:
                 raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative average) is not supported")
             momentum = bn.momentum
+            work = _empty(_C.lib().ngan_chan_reduce_workspace_floats(npix, c), y)
+            if self.sync is not None:
+                rec = torch.empty(1 + 2 * c, device=y.device, dtype=torch.float64)
+                _C.call("ngan_bn_moments", y, npix, c, rec, work)
+                recs = self.sync.gather(rec)
+                self.n_total = torch.empty(1, device=y.device, dtype=torch.float64)
+                _C.call("ngan_bn_merge_fold", recs, self.sync.world, c, gamma.detach(), beta.detach(), mean, rstd, scale, shift,
+                        bn.running_mean if track else None, bn.running_var if track else None, bn.num_batches_tracked if track else None,
+                        float(momentum), float(bn.eps), self.n_total)
+                return scale, shift, mean, rstd
             _C.call("ngan_bn_stats", y, npix, c, gamma.detach(), beta.detach(), mean, rstd, scale, shift,
                     bn.running_mean if track else None, bn.running_var if track else None, bn.num_batches_tracked if track else None,
-                    float(momentum), float(bn.eps), _empty(_C.lib().ngan_chan_reduce_workspace_floats(npix, c), y))
+                    float(momentum), float(bn.eps), work)
             return scale, shift, mean, rstd
         _C.call("ngan_bn_fold_eval", gamma.detach(), beta.detach(), bn.running_mean, bn.running_var, float(bn.eps), scale, shift, c)
         return scale, shift, None, None
@@ -125,6 +173,16 @@ def _bn_act_backward(ctx, y, ga, scale, shift, mean, rstd, gamma, want_affine):
     gy = torch.empty_like(y)
     dgamma = _empty(c, y) if want_affine else None
     dbeta = _empty(c, y) if want_affine else None
+    sync = ctx.bn.sync if ctx.bn is not None else None
+    if sync is not None:
+        ga = _check(ga, "bn backward")
+        rec = torch.empty(2 * c, device=y.device, dtype=torch.float64)
+        _C.call("ngan_bn_act_bwd_partial", y, ga, scale, shift, mean, rstd, int(ctx.act), float(ctx.slope), npix, c, rec,
+                _empty(_C.lib().ngan_chan_reduce_workspace_floats(npix, c), y))
+        recs = sync.gather(rec)
+        _C.call("ngan_bn_act_bwd_merged", y, ga, scale, shift, mean, rstd, gamma.detach(), int(ctx.act), float(ctx.slope), npix, c, recs,
+                sync.world, sync.rank, ctx.bn.n_total, gy, dgamma, dbeta, _empty(3 * c, y))
+        return gy, dgamma, dbeta
     work = _empty(_C.lib().ngan_bn_act_bwd_workspace_floats(npix, c), y) if ctx.bn is not None else None
     _C.call("ngan_bn_act_bwd", y, _check(ga, "bn backward"), scale, shift, mean, rstd, gamma.detach() if ctx.bn is not None else None,
             int(ctx.act), float(ctx.slope), npix, c, gy, dgamma, dbeta, work)

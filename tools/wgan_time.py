@@ -3,11 +3,17 @@
 torch.optim and the reference's loop (train.py:470-506) -- the yardstick, a measurement only.  n_critic 1 and 5, Adam and RMSprop.
 Then a per-kernel breakdown of one eager HIP iteration (torch.profiler), n_critic 1, Adam.
 
-    python tools/wgan_time.py [--iters 20] [--warmup 5]      (record: profiles/wgan_time.txt)
+--sync: in a spawned child holding a one-rank RCCL group, n_critic 1, Adam: the replayed graph, the eager iteration, and the eager
+iteration with sync_batchnorm=True (every training-mode BatchNorm call all-gathers its statistics on the communication stream, plus the
+two gradient all-reduces), and the time inside those collectives (events around each communication-stream section).  One rank: what
+this measures is the cost of the synchronised path itself, not an interconnect.
+
+    python tools/wgan_time.py [--iters 20] [--warmup 5] [--sync]      (record: profiles/wgan_time.txt)
 """
 import argparse
 import copy
 import os
+import socket
 import sys
 
 import torch
@@ -96,11 +102,75 @@ def breakdown(real):
     return lines
 
 
+def sync_child(port, iters, warmup, q):
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    torch.cuda.set_device(DEV)
+    real = (torch.rand(B, 1, SIZE, SIZE, generator=torch.Generator().manual_seed(0)) * 2 - 1).to(DEV)
+    G, D = nets()
+    tr = train.WGANTrainer(G, D, optimizer="adam", n_critic=1, device_latents=True)
+    tr.capture(real)          # before the process group exists: WGANTrainer.capture is a GLOBAL-mode capture
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=DEV)
+    try:
+        graph = timed(lambda: tr.replay(real), iters, warmup)
+        G, D = nets()
+        tr = train.WGANTrainer(G, D, optimizer="adam", n_critic=1, device_latents=True)
+        eager = timed(lambda: tr.train_iteration(real), iters, warmup)
+        G, D = nets()
+        tr = train.WGANTrainer(G, D, optimizer="adam", n_critic=1, device_latents=True, sync_batchnorm=True)
+        synced = timed(lambda: tr.train_iteration(real), iters, warmup)
+        tr.comm_timing = []                     # a window of its own: the events are not part of the timings above
+        for _ in range(iters):
+            tr.train_iteration(real)
+        torch.cuda.synchronize()
+        per_tag = {}
+        for tag, e0, e1 in tr.comm_timing:
+            n, ms = per_tag.get(tag, (0, 0.0))
+            per_tag[tag] = (n + 1, ms + e0.elapsed_time(e1))
+        n_bn, ms_bn = per_tag.get("batchnorm", (0, 0.0))
+        n_ex = sum(per_tag.get(t, (0, 0.0))[0] for t in ("critic", "generator"))
+        ms_ex = sum(per_tag.get(t, (0, 0.0))[1] for t in ("critic", "generator"))
+        q.put([f"  sync_batchnorm, one-rank RCCL group, adam n_critic 1: HIP graph replay {graph:8.3f} ms   eager {eager:8.3f} ms   "
+               f"eager + sync_batchnorm {synced:8.3f} ms",
+               f"    inside the collectives per iteration: {n_bn / iters:.0f} BatchNorm all-gathers {ms_bn / iters:7.3f} ms, "
+               f"{n_ex / iters:.0f} gradient all-reduces {ms_ex / iters:7.3f} ms"])
+    except Exception as e:      # noqa: BLE001
+        q.put([f"  (sync measurement failed: {type(e).__name__}: {e})"])
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+def sync_lines(iters, warmup):
+    import torch.multiprocessing as mp
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=sync_child, args=(port, iters, warmup, q))
+    p.start()
+    p.join(900)
+    if p.is_alive():
+        p.kill()
+        p.join()
+    try:
+        return q.get(timeout=5)
+    except Exception:       # noqa: BLE001 (queue.Empty: the child died before reporting)
+        return [f"  (sync measurement: child exit code {p.exitcode})"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--sync", action="store_true", help="only the sync_batchnorm comparison (one-rank RCCL group, spawned child)")
     a = ap.parse_args()
+    if a.sync:
+        print(f"WGAN iteration, G {GW} D {DW}, {SIZE}^2, batch {B}, fp32, {torch.cuda.get_device_name(0)}", flush=True)
+        print("\n".join(sync_lines(a.iters, a.warmup)))
+        return
     real = (torch.rand(B, 1, SIZE, SIZE, generator=torch.Generator().manual_seed(0)) * 2 - 1).to(DEV)
     print(f"WGAN iteration, G {GW} D {DW}, {SIZE}^2, batch {B}, fp32, {torch.cuda.get_device_name(0)}")
     for kind in ("adam", "rmsprop"):
