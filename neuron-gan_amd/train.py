@@ -23,6 +23,7 @@ import torch
 import torch.distributed as dist
 
 from . import _C, ops, wgan_ops
+from .launch import check_sharding, longest_share, shard_bounds
 from .loss_functions import D_W_loss, D_grad_pen_loss, G_W_loss
 from .utils import sample_latent_vec, sample_latent_vec_device
 
@@ -203,6 +204,7 @@ class StemGradExchange:
         self.captured = None     # kept after finish(): under graph replay the same (static) tensors are refilled every step
         self.factors = None      # (z, gc, s2, c, scale) over ALL ranks' samples after finish(): what FusedAdam.step(stem_factors=) takes
         self._gathered = {}      # gather buffers per factor shape: captured Adam launches read them, so they must not move
+        self._padded = {}        # (own rows, longest share) -> zero-padded copies of the two factors (ragged shares)
         self.wgrad_fn = wgrad_fn or (lambda zs, gs, out, n, k, s2, c, scale:
                                      _C.call(ops._k("ngan_linear_wgrad", gs), zs, gs, out, n, k, s2, c, float(scale)))
 
@@ -210,8 +212,13 @@ class StemGradExchange:
         assert weight is self.weight
         self.captured = (z, gc, s2, c, scale)
 
-    def finish(self, run_collectives=None, materialize=True, also=None):
+    def finish(self, run_collectives=None, materialize=True, also=None, longest=None):
         """all-gather the factors and (materialize) write the full-batch gradient into weight.grad (call after backward).
+        longest: the longest share of this step's global batch -- ceil(global batch / world) under the sharding rule (None: every rank
+        holds as many samples as this one).
+        all_gather_into_tensor needs equal contributions, so a rank with a shorter share pads both factors with zero rows up to it (a
+        zero row adds nothing to sum_b gc[b] (x) z[b]); every size inside the collective comes from (global batch, world) alone and
+        is therefore the same on every rank.
         `run_collectives(fn)` executes the collectives (the step driver passes its communication-stream runner,
         PGGANTrainer._on_comm_stream).  With materialize=False the gradient is never formed: `self.factors` goes to the fused Adam.
         `also`: a further collective of the caller (the all-reduce of the generator's other gradients) issued in the SAME
@@ -224,12 +231,23 @@ class StemGradExchange:
         z, gc, s2, c, scale = self.captured
         b, k = z.shape
         if self.world > 1:
-            key = (self.world * b, k) + tuple(gc.shape[1:])
+            rows = b if longest is None else int(longest)
+            assert rows >= b, f"this rank holds {b} samples, more than the longest share {rows} of the global batch"
+            key = (self.world * rows, k) + tuple(gc.shape[1:])
             if key not in self._gathered:
-                self._gathered[key] = (torch.empty((self.world * b, k), device=z.device, dtype=z.dtype),
-                                       torch.empty((self.world * b,) + tuple(gc.shape[1:]), device=gc.device, dtype=gc.dtype))
+                self._gathered[key] = (torch.empty((self.world * rows, k), device=z.device, dtype=z.dtype),
+                                       torch.empty((self.world * rows,) + tuple(gc.shape[1:]), device=gc.device, dtype=gc.dtype))
             zs, gs = self._gathered[key]
-            zc, gcc = z.contiguous(), gc.contiguous()
+            if rows == b:
+                zc, gcc = z.contiguous(), gc.contiguous()
+            else:
+                pkey = (b,) + key
+                if pkey not in self._padded:     # rows b.. are zero from here on: only rows :b are ever written
+                    self._padded[pkey] = (torch.zeros((rows, k), device=z.device, dtype=z.dtype),
+                                          torch.zeros((rows,) + tuple(gc.shape[1:]), device=gc.device, dtype=gc.dtype))
+                zc, gcc = self._padded[pkey]
+                zc[:b].copy_(z)
+                gcc[:b].copy_(gc)
 
             def gather():
                 dist.all_gather_into_tensor(zs, zc, group=self.group)
@@ -280,8 +298,51 @@ def lr_schedule(epoch, base_lr, transit_sch, n_epochs, total_decay=1 / 100):
     return None
 
 
+def _init_share(trainer):
+    """the device scalar that roots every backward of a data-parallel step (see _set_share); one rank keeps the constant `_one`"""
+    trainer._one = torch.ones((), device=trainer.device)
+    trainer._share = torch.ones((), device=trainer.device) if trainer.world > 1 else None
+    trainer._root = trainer._one if trainer.world == 1 else trainer._share
+    trainer._longest = None
+
+
+def _set_share(trainer, b, global_batch):
+    """Before a step on this rank's b samples of a global batch.  global_batch: None -- world * b, equal shares; an int -- the size of
+    the global batch, shared out by the sharding rule (what the epoch drivers pass); a sequence -- every rank's share in rank order,
+    for any other split.  Writes the weight
+    w = b * world / global_batch into device memory.  Every loss is a per-sample mean, so sum_ranks(w_r * grad_r) / world -- the
+    all-reduce and the 1/world of the optimiser launch -- is the gradient of the whole batch's mean whatever the shares are.  The
+    backward passes read w from the device, so a captured graph replays with the weight of the moment; the write itself is never
+    captured (a capture would freeze its value)."""
+    if trainer.world == 1:
+        whole = sum(global_batch) if isinstance(global_batch, (tuple, list)) else global_batch
+        if whole is not None and int(whole) != int(b):
+            raise ValueError(f"one rank holds the whole batch: global_batch={global_batch}, batch {b}")
+        return
+    if global_batch is None:
+        gb, longest = trainer.world * b, None
+    elif isinstance(global_batch, (tuple, list)):                  # every rank's share, in rank order
+        shares = [int(v) for v in global_batch]
+        if len(shares) != trainer.world or min(shares) < 1 or shares[dist.get_rank(trainer.group)] != b:
+            raise ValueError(f"shares {shares} of {trainer.world} ranks do not give this rank its {b} samples")
+        gb, longest = sum(shares), max(shares)
+    else:                                                          # shares by the sharding rule (launch.shard_bounds)
+        gb = int(global_batch)
+        longest = longest_share(gb, trainer.world)
+        if not 0 < b <= longest:
+            raise ValueError(f"this rank's {b} samples are no share of a global batch of {gb} over {trainer.world} ranks by the "
+                             f"sharding rule (at most {longest}); pass every rank's share instead")
+    trainer._longest = longest
+    if not (trainer.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+        trainer._share.fill_(b * trainer.world / gb)
+
+
 class PGGANTrainer:
-    """One object per process (= per GPU).  `train_iteration(real)` is train.py:356-385 with sim_loss off."""
+    """One object per process (= per GPU).  `train_iteration(real)` is train.py:356-385 with sim_loss off.
+
+    Data parallel (an initialised process group): every rank trains its share of the global batch; `global_batch` (an argument of
+    step / train_iteration / d_compute / g_compute / replay: the global batch size, or every rank's share; default world * this rank's
+    batch) makes unequal shares exact -- see `_set_share`."""
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
@@ -323,7 +384,7 @@ class PGGANTrainer:
             self.enable_fused_stem()
         self.force_exchange = False
         self.last_z_g = None
-        self._one = torch.ones((), device=self.device)
+        _init_share(self)
         # collectives of the RCCL backend run on a stream of their own (see _on_comm_stream); created on first need
         self._comm_stream = None
         self.comm_timing = None     # bench.py: a list that receives (tag, start event, end event) of every gradient exchange
@@ -428,15 +489,17 @@ class PGGANTrainer:
             tail = None
             if self.world > 1 or self.force_exchange:
                 tail = lambda: dist.all_reduce(flat.grad[self._stem_elems:], op=dist.ReduceOp.SUM, group=self.group)   # noqa: E731
-            self.stem.finish(lambda fn: self._on_comm_stream(fn, "generator"), materialize=not self._stem_grad_skipped, also=tail)
+            self.stem.finish(lambda fn: self._on_comm_stream(fn, "generator"), materialize=not self._stem_grad_skipped, also=tail,
+                             longest=self._longest)
             return
         if self.world > 1 or self.force_exchange:
             self._on_comm_stream(lambda: exchange_gradients(flat, self.world, self.group, force=self.force_exchange),
                                  "critic" if flat is self.flat_d else "generator")
 
-    def d_compute(self, real, z_d=None, z_gp=None, eps=None):
+    def d_compute(self, real, z_d=None, z_gp=None, eps=None, global_batch=None):
         """D half-step up to (and including) the backward pass: gradients end up in flat_d.grad."""
         b = real.size(0)
+        _set_share(self, b, global_batch)
         self.flat_d.ensure_grad_views()
         self.flat_d.zero_grad()  # Discriminator_net.zero_grad(), train.py:357
         # the two detached generator passes of the D step (loss_functions.py:26, 167) run as one batch-2b pass; with the penalty
@@ -457,20 +520,21 @@ class PGGANTrainer:
         # reproducible from iteration to iteration (ops.flush_wgrad), and the step driver is meant to be bit-reproducible.
         with ops.deferred_wgrad():   # weight-gradient slabs of the whole pass are reduced by one launch at the end
             if gp.requires_grad:
-                gp.backward(gradient=self._one)     # (an explicit root gradient: autograd otherwise fills a ones tensor per call)
-            loss.backward(gradient=self._one)
+                gp.backward(gradient=self._root)    # (an explicit root gradient: autograd otherwise fills a ones tensor per call)
+            loss.backward(gradient=self._root)
         loss = loss.detach() + gp.detach()
         return {"D_loss": loss.detach(), "score_real": s_real.detach(), "score_fake": s_fake.detach(), "D_grad_pen": gp.detach()}
 
-    def d_step(self, real, z_d=None, z_gp=None, eps=None):
-        stats = self.d_compute(real, z_d, z_gp, eps)
+    def d_step(self, real, z_d=None, z_gp=None, eps=None, global_batch=None):
+        stats = self.d_compute(real, z_d, z_gp, eps, global_batch)
         self._exchange(self.flat_d)
         self.opt_d.step()  # train.py:366
         return stats
 
-    def g_compute(self, real, z=None, skip_stem_grad=False):
+    def g_compute(self, real, z=None, skip_stem_grad=False, global_batch=None):
         """skip_stem_grad (g_step with fused_stem): the stem's gradient is neither zeroed nor stored -- its factors wait in self.stem"""
         b = real.size(0)
+        _set_share(self, b, global_batch)
         self.flat_g.ensure_grad_views()
         self._stem_grad_skipped = bool(skip_stem_grad and self.fused_stem)
         if self._stem_grad_skipped:
@@ -487,7 +551,7 @@ class PGGANTrainer:
             ops.linear_grad_sink = self.stem.sink if self._stem_sink_active else None
             try:
                 with ops.deferred_wgrad():
-                    loss.backward(gradient=self._one)  # train.py:384
+                    loss.backward(gradient=self._root)  # train.py:384
             finally:
                 ops.linear_grad_sink = None
         finally:
@@ -517,19 +581,20 @@ class PGGANTrainer:
         norms, clipping or logging helpers must call materialize_stem_grad() first (or check this flag)."""
         return not self._stem_grad_skipped
 
-    def g_step(self, real, z=None):
-        stats = self.g_compute(real, z, skip_stem_grad=True)
+    def g_step(self, real, z=None, global_batch=None):
+        stats = self.g_compute(real, z, skip_stem_grad=True, global_batch=global_batch)
         self._exchange(self.flat_g)
         self.g_adam()
         return stats
 
-    def train_iteration(self, real, z_d=None, z_gp=None, eps=None, z_g=None):
+    def train_iteration(self, real, z_d=None, z_gp=None, eps=None, z_g=None, global_batch=None):
+        """global_batch: the size of the whole batch this rank's `real` is a share of (None: world * real.size(0))"""
         stats = {}
         for _ in range(self.n_critic):  # train.py:356
-            stats.update(self.d_step(real, z_d, z_gp, eps))
+            stats.update(self.d_step(real, z_d, z_gp, eps, global_batch))
         if self.n_critic == 0:          # adaptive critic schedule chose no critic step: losses for monitoring only (train.py:369-372)
-            stats.update(self.d_compute(real, z_d, z_gp, eps))
-        stats.update(self.g_step(real, z_g))
+            stats.update(self.d_compute(real, z_d, z_gp, eps, global_batch))
+        stats.update(self.g_step(real, z_g, global_batch))
         return stats
 
     # ---- optimiser state for checkpoints (optional extra key; the reference saves none) ---------------------------
@@ -579,7 +644,17 @@ class PGGANTrainer:
             bufs += [flat.flat] + [getattr(flat, buf) for buf in opt.STATE] + [flat.seg_step]
         return bufs
 
-    def capture(self, real_example, warmup=1, draws=None):
+    def _graph_key(self, shape, global_batch=None):
+        """Graphs are kept per input shape and, data parallel with a stated global batch, per global batch size.  A capture contains
+        collectives (its warm-up iterations and the exchanges between its segments), so all ranks must capture at the same step; the
+        global batch size is what every rank sees alike, while one rank's share of two global sizes can have the same shape where
+        another rank's has not.  (The captured generator update also reads the gathered stem factors, whose row count
+        world x longest share follows from the global size.)  The share weight itself is read from device memory."""
+        if self.world == 1 or global_batch is None:
+            return tuple(shape)
+        return tuple(shape) + ("global", tuple(global_batch) if isinstance(global_batch, (tuple, list)) else int(global_batch))
+
+    def capture(self, real_example, warmup=1, draws=None, global_batch=None):
         """Capture `train_iteration` for this batch shape into HIP graphs (latents and epsilon drawn on the GPU inside
         the graph).  Afterwards `replay(real)` copies `real` into the static input of the graphs captured for its shape and
         launches them.  One GPU: one graph for the whole iteration.  Data parallel: three graphs -- [D forward/backward],
@@ -593,7 +668,9 @@ class PGGANTrainer:
         (`refresh_stage`), so a ragged last batch costs one extra capture per stage, not two per epoch.
 
         draws: optional dict of STATIC device tensors {"z_d", "z_gp", "eps", "z_g"} used instead of drawing inside the graph; the
-        caller refills them before each replay (how the parity tests replay an eager trajectory exactly)."""
+        caller refills them before each replay (how the parity tests replay an eager trajectory exactly).
+        global_batch: as in train_iteration.  The share weight is read from device memory by the captured backward passes, so the
+        graphs serve every global batch with the same longest share (`_graph_key`)."""
         if draws is None and not self.device_latents:
             raise RuntimeError("graph capture needs device_latents=True or static draws (CPU-drawn latents cannot be replayed)")
         dr = draws or {}
@@ -603,6 +680,7 @@ class PGGANTrainer:
         if segmented and self.n_critic != 1:
             raise RuntimeError("segmented (data-parallel) capture supports n_critic = 1")
         static_real = real_example.clone()
+        _set_share(self, static_real.size(0), global_batch)     # the write stays outside the captures
         n_packed_before = ops.registry_size()
         state = self._training_state()
         saved = [t.clone() for t in state]
@@ -612,7 +690,7 @@ class PGGANTrainer:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
-                self.train_iteration(static_real, *d_args, z_g)
+                self.train_iteration(static_real, *d_args, z_g, global_batch)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         for t, v in zip(state, saved):
@@ -625,7 +703,13 @@ class PGGANTrainer:
         self.opt_g.repack()       # steps find them complete
         ops.refresh_packed()      # (copies of tensors that belong to neither optimiser)
         torch.cuda.synchronize()
-        if ops.registry_size() != n_packed_before and self._graphs:
+        stale = ops.registry_size() != n_packed_before and bool(self._graphs)
+        if self.world > 1:
+            # every rank forgets its graphs or none does: a rank re-capturing alone would wait for the others in its first collective
+            flag = torch.tensor([float(stale)], device=self.device)
+            self._on_comm_stream(lambda: dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=self.group), "capture")
+            stale = bool(flag.item())
+        if stale:
             # This shape registered packed-weight copies the earlier shapes' graphs know nothing about (the pack format of a layer
             # can depend on the batch: ngan_conv3x3_algorithm).  The re-pack launches captured in those graphs run from tables that
             # do not list the new copies, so a replay of them would leave the new copies stale for this shape's next replay:
@@ -654,7 +738,7 @@ class PGGANTrainer:
         gc_was_enabled = gc.isenabled()
         gc.disable()
         try:
-            graphs, stats = self._capture_segments(segmented, mode, static_real, d_args, z_g)
+            graphs, stats = self._capture_segments(segmented, mode, static_real, d_args, z_g, global_batch)
         finally:
             if gc_was_enabled:
                 gc.enable()
@@ -667,23 +751,23 @@ class PGGANTrainer:
         entry = (graphs, static_real, stats, self.stem.captured if self.stem is not None else None, ops.table_tensors(),
                  (self._stem_grad_skipped, self._stem_sink_active))
         self._graph, self._entry = graphs, entry
-        self._graphs[tuple(real_example.shape)] = entry
+        self._graphs[self._graph_key(real_example.shape, global_batch)] = entry
         return graphs
 
-    def _capture_segments(self, segmented, mode, static_real, d_args, z_g):
+    def _capture_segments(self, segmented, mode, static_real, d_args, z_g, global_batch=None):
         if not segmented:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode=mode):
-                stats = self.train_iteration(static_real, *d_args, z_g)
+                stats = self.train_iteration(static_real, *d_args, z_g, global_batch)
             graphs = [graph]
         else:
             ga, gb, gc = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(ga, capture_error_mode=mode):
-                stats = self.d_compute(static_real, *d_args)
+                stats = self.d_compute(static_real, *d_args, global_batch)
             self._exchange(self.flat_d)                  # eager, on the communication stream; its result is discarded below
             with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode=mode):
                 self.opt_d.step()
-                stats.update(self.g_compute(static_real, z_g, skip_stem_grad=True))
+                stats.update(self.g_compute(static_real, z_g, skip_stem_grad=True, global_batch=global_batch))
             self._exchange(self.flat_g)
             with torch.cuda.graph(gc, pool=ga.pool(), capture_error_mode=mode):
                 self.g_adam()
@@ -693,14 +777,14 @@ class PGGANTrainer:
             self.flat_g.grad.zero_()
         return graphs, stats
 
-    def has_graph(self, shape):
-        return tuple(shape) in self._graphs
+    def has_graph(self, shape, global_batch=None):
+        return self._graph_key(shape, global_batch) in self._graphs
 
-    def replay(self, real=None):
+    def replay(self, real=None, global_batch=None):
         """One training iteration from the captured graphs.  `real` selects the graphs by its shape (capture() them first);
         without an argument the most recently captured graphs run on their static input as it stands."""
         if real is not None:
-            entry = self._graphs.get(tuple(real.shape))
+            entry = self._graphs.get(self._graph_key(real.shape, global_batch))
             if entry is None:
                 raise RuntimeError(f"no graphs captured for input shape {tuple(real.shape)}: call capture() first (and again after "
                                    f"every growth event)")
@@ -710,7 +794,8 @@ class PGGANTrainer:
             if self._graph is None:
                 raise RuntimeError("call capture() first (and again after every growth event)")
             entry = self._entry
-        graphs, _, stats, stem_factors, _, stem_flags = entry
+        graphs, static_real, stats, stem_factors, _, stem_flags = entry
+        _set_share(self, static_real.size(0), global_batch)
         if self.stem is not None:
             self.stem.captured = stem_factors     # the factors THESE graphs fill (see capture())
         self._stem_grad_skipped, self._stem_sink_active = stem_flags
@@ -724,13 +809,13 @@ class PGGANTrainer:
             graphs[2].replay()
         return stats
 
-    def step(self, real, use_graph=True):
+    def step(self, real, use_graph=True, global_batch=None):
         """train on one batch: graph replay when possible (capturing on first sight of a shape), else eager"""
         if use_graph and self.device_latents and self.n_critic == 1:
-            if not self.has_graph(real.shape):
-                self.capture(real)
-            return self.replay(real)
-        return self.train_iteration(real)
+            if not self.has_graph(real.shape, global_batch):
+                self.capture(real, global_batch=global_batch)
+            return self.replay(real, global_batch)
+        return self.train_iteration(real, global_batch=global_batch)
 
 
 class _ClipMixin:
@@ -762,8 +847,9 @@ class WGANTrainer:
     training-mode BatchNorm2d forward inside d_compute / g_compute (so also d_step, g_step, train_iteration, step) normalises with the
     statistics of the union of all ranks' inputs to that call, updates the running buffers identically on every rank and
     differentiates through the global statistics; the flat gradients are all-reduced between compute and optimiser step (1/world folded
-    into the optimiser).  Ranks with equal batches then reproduce one rank on the whole batch; a ragged split keeps exact statistics
-    and weights each rank's loss by 1/world, as on the PGGAN path.  Every BatchNorm call is a collective, so every rank must run the
+    into the optimiser).  The ranks then reproduce one rank on the whole batch: with equal batches as they are, with unequal shares
+    when every rank passes `global_batch` (step / train_iteration / d_compute / g_compute), which weights its loss by
+    b_rank * world / global_batch (`_set_share`); the statistics are exact either way.  Every BatchNorm call is a collective, so every rank must run the
     same sequence of steps (the same n_critic: no adapt_critic over per-rank series).  Each rank draws its own latents: seed each rank
     differently.  Eager only: capture() raises and step() runs train_iteration.  Forwards outside the steps (a sample grid on rank 0,
     eval mode) issue no collective."""
@@ -812,7 +898,7 @@ class WGANTrainer:
         if self.sync_batchnorm and self.device.type == "cuda" and dist.get_backend(process_group) == "nccl":
             self._comm_stream = torch.cuda.Stream(device=self.device)
         self.last_z_g = None
-        self._one = torch.ones((), device=self.device)
+        _init_share(self)
         self._graphs = {}
         self._graph = self._entry = None
 
@@ -843,9 +929,10 @@ class WGANTrainer:
     def _bn_buffers(self):
         return [b for net in (self.G, self.D) for b in net.buffers()]
 
-    def d_compute(self, real, z=None):
+    def d_compute(self, real, z=None, global_batch=None):
         """D_W_loss (loss_functions.py:14-45) and its backward: gradients end up in flat_d.grad"""
         b = real.size(0)
+        _set_share(self, b, global_batch)
         self.flat_d.ensure_grad_views()
         self.flat_d.zero_grad()
         with self._bn_sync():
@@ -855,17 +942,18 @@ class WGANTrainer:
                 fake = self.G.forward_nhwc(z)
             s_fake_all = self.D.forward_nhwc(fake)
             loss, s_real, s_fake = ops.WLossHead.apply(torch.cat([s_real_all, s_fake_all], dim=0), b, self.drift_epsilon)
-            loss.backward(gradient=self._one)
+            loss.backward(gradient=self._root)
         return {"D_loss": loss.detach(), "score_real": s_real.detach(), "score_fake": s_fake.detach()}
 
-    def d_step(self, real, z=None):
-        stats = self.d_compute(real, z)
+    def d_step(self, real, z=None, global_batch=None):
+        stats = self.d_compute(real, z, global_batch)
         self._exchange(self.flat_d)
         self.opt_d.step()                                            # + clamp_(-clip, clip) in the same launch
         return stats
 
-    def g_compute(self, real, z=None):
+    def g_compute(self, real, z=None, global_batch=None):
         b = real.size(0)
+        _set_share(self, b, global_batch)
         self.flat_g.ensure_grad_views()
         self.flat_g.zero_grad()
         d_params = self.flat_d.params
@@ -876,27 +964,28 @@ class WGANTrainer:
             self.last_z_g = z
             with self._bn_sync():
                 loss = ops.WLossHead.apply(self.D.forward_nhwc(self.G.forward_nhwc(z)), b, 0.0)[0]
-                loss.backward(gradient=self._one)
+                loss.backward(gradient=self._root)
         finally:
             for p in d_params:
                 p.requires_grad_(True)
         return {"G_loss": loss.detach()}
 
-    def g_step(self, real, z=None):
-        stats = self.g_compute(real, z)
+    def g_step(self, real, z=None, global_batch=None):
+        stats = self.g_compute(real, z, global_batch)
         self._exchange(self.flat_g)
         self.opt_g.step()
         return stats
 
-    def train_iteration(self, real, z_d=None, z_g=None):
-        """z_d: None, one latent batch (used by every critic step) or a sequence of n_critic batches"""
+    def train_iteration(self, real, z_d=None, z_g=None, global_batch=None):
+        """z_d: None, one latent batch (used by every critic step) or a sequence of n_critic batches
+        global_batch: the size of the whole batch this rank's `real` is a share of (None: world * real.size(0))"""
         stats = {}
         for i in range(self.n_critic):
             z = z_d[i] if isinstance(z_d, (list, tuple)) else z_d
-            stats.update(self.d_step(real, z))
+            stats.update(self.d_step(real, z, global_batch))
         if self.n_critic == 0:
-            stats.update(self.d_compute(real, z_d[0] if isinstance(z_d, (list, tuple)) else z_d))
-        stats.update(self.g_step(real, z_g))
+            stats.update(self.d_compute(real, z_d[0] if isinstance(z_d, (list, tuple)) else z_d, global_batch))
+        stats.update(self.g_step(real, z_g, global_batch))
         return stats
 
     def set_lr(self, lr):
@@ -977,13 +1066,14 @@ class WGANTrainer:
         entry[0].replay()
         return entry[2]
 
-    def step(self, real, use_graph=True):
+    def step(self, real, use_graph=True, global_batch=None):
         """graph replay when possible (capturing on first sight of a shape), else eager; always eager with sync_batchnorm"""
         if use_graph and self.device_latents and not self.sync_batchnorm:
+            _set_share(self, real.size(0), global_batch)      # (one rank: checks the argument, writes nothing)
             if not self.has_graph(real.shape):
                 self.capture(real)
             return self.replay(real)
-        return self.train_iteration(real)
+        return self.train_iteration(real, global_batch=global_batch)
 
 
 # =====================================================================================================================
@@ -1023,8 +1113,105 @@ class TensorImageDataset(torch.utils.data.Dataset):
         return self._cache[self.image_size][i]
 
 
+def epoch_order(n_images, seed, epoch, world=1):
+    """The permutation of the dataset that epoch `epoch` trains in (DataLoader(shuffle=True), train.py:153).  One rank draws it from
+    torch's global generator, as ever; N ranks all draw the same one from a host generator seeded by (seed, epoch)."""
+    if world == 1:
+        return torch.randperm(n_images).tolist()
+    gen = torch.Generator().manual_seed(int(seed) * 1000003 + int(epoch))
+    return torch.randperm(n_images, generator=gen).tolist()
+
+
+class _Ranks:
+    """What the epoch drivers know about the ranks of a run: the sharding rule of launch.py applied to one epoch, and the collectives
+    of the monitors.  One rank (no group): every method is the identity and nothing of torch.distributed is called."""
+
+    def __init__(self, trainer, process_group, n_images, batch_size):
+        self.trainer = trainer
+        self.group = process_group if process_group is not None else getattr(trainer, "group", None)
+        if process_group is not None:
+            self.world = dist.get_world_size(process_group)
+        else:
+            self.world = int(getattr(trainer, "world", 1))
+        self.rank = dist.get_rank(self.group) if self.world > 1 else 0
+        self.on_gpu = trainer.device.type == "cuda"
+        if self.world > 1:
+            check_sharding(n_images, batch_size, self.world)
+
+    def order(self, n_images, seed, epoch):
+        return epoch_order(n_images, seed, epoch, self.world)
+
+    def share(self, n):
+        return shard_bounds(n, self.world, self.rank)
+
+    def run(self, fn, tag="monitors"):
+        """a collective of the driver: on the trainer's communication stream on a GPU, in line on a CPU device"""
+        if self.on_gpu and hasattr(self.trainer, "_on_comm_stream"):
+            self.trainer._on_comm_stream(fn, tag)
+        else:
+            fn()
+
+    def sum_(self, t):
+        if self.world > 1:
+            self.run(lambda: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group))
+        return t
+
+    def gather_rows(self, t, n_global):
+        """the rows of every rank's `t` (its share of a global batch of n_global samples) in rank order: shares are padded to the
+        longest one for the all-gather and the padding is dropped again"""
+        if self.world == 1:
+            return t
+        rows = longest_share(n_global, self.world)
+        mine = torch.zeros((rows,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)
+        mine[:t.shape[0]].copy_(t)
+        out = torch.empty((self.world * rows,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)
+        self.run(lambda: dist.all_gather_into_tensor(out, mine, group=self.group))
+        parts = []
+        for r in range(self.world):
+            lo, hi = shard_bounds(n_global, self.world, r)
+            parts.append(out[r * rows:r * rows + (hi - lo)])
+        return torch.cat(parts, dim=0)
+
+    def assert_same(self, value, what):
+        """one tiny all-reduce: every rank holds the same integer"""
+        if self.world > 1:
+            t = torch.tensor([float(value), -float(value)], device=self.trainer.device)
+            self.run(lambda: dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group))
+            hi, lo = t.tolist()
+            if hi != -lo:
+                raise RuntimeError(f"the ranks disagree on {what}: between {-lo:g} and {hi:g} (rank {self.rank}: {value})")
+
+    def barrier(self):
+        if self.world > 1:
+            t = torch.zeros(1, device=self.trainer.device)
+            self.sum_(t)
+            t.tolist()                  # the host waits: rank 0's file is complete before any rank goes on
+
+
+def _slice_draws(draws, epoch, k, n_global, lo, hi, device):
+    """this rank's rows of the global draw tensors of batch k (`draws(epoch, k, n_global)`); a list (the WGAN path's per-critic-step
+    latents) is sliced element by element"""
+    if draws is None:
+        return {}
+    cut = lambda v: v[lo:hi].to(device)   # noqa: E731
+    return {name: ([cut(x) for x in v] if isinstance(v, (list, tuple)) else cut(v)) for name, v in draws(epoch, k, n_global).items()}
+
+
+def _fill_static(static, fresh):
+    for name, v in fresh.items():
+        if isinstance(v, (list, tuple)):
+            for a, b in zip(static[name], v):
+                a.copy_(b, non_blocking=True)
+        else:
+            static[name].copy_(v, non_blocking=True)
+
+
+def _clone_draws(fresh):
+    return {name: ([x.clone() for x in v] if isinstance(v, (list, tuple)) else v.clone()) for name, v in fresh.items()}
+
+
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
-                samples_dir=None, on_epoch=None):
+                samples_dir=None, on_epoch=None, process_group=None, draws=None):
     """The reference's epoch loop (train.py:298-451) over a PGGANTrainer.
     Per epoch: advance alpha / grow (318-333), one pass over the dataset in batches of cfg.batch_size (350-394), sample-weighted
     epoch means of the monitors (387-398), a status line every 10 epochs (401-422), LR schedule (424-426), loss series (429-432),
@@ -1032,7 +1219,14 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     epoch late through pinned memory, so the host never stalls the launch stream; a NaN loss raises ValueError like the
     reference's loss modules do (loss_functions.py:35-41, 70-72).
     on_epoch(epoch, trainer): optional observer, called once per epoch after the alpha / growth update, i.e. with the structure and
-    the learning rate the epoch trains with (what the reference's status line prints, train.py:401-422)."""
+    the learning rate the epoch trains with (what the reference's status line prints, train.py:401-422).
+
+    Data parallel (process_group, default the trainer's): cfg.batch_size stays the GLOBAL batch.  Every rank
+    draws the same permutation and trains its `shard_bounds` slice of every global batch, passing the global size to the trainer;
+    the monitor sums are all-reduced once per epoch, so the series, the adaptive critic schedule and the NaN check are the same on
+    every rank; rank 0 alone logs, saves and plots.  With one rank nothing of this is active.
+    draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
+    (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
     from .utils import Calculate_D_steps, similarity_loss
     adapt_period = 100                                                # Disc_adapt_update_period, train.py:190
@@ -1043,9 +1237,14 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     dev = trainer.device
     epoch_final = epoch_final if epoch_final is not None else cfg.N_epochs + 1
     n_images = len(dataset)
+    ranks = _Ranks(trainer, process_group, n_images, cfg.batch_size)
+    if ranks.rank != 0:
+        log = lambda *a, **k: None    # noqa: E731
     names = ["score_real", "score_fake", "D_loss", "G_loss", "D_grad_pen"]
-    pinned = torch.zeros(2, len(names), pin_memory=True)
+    on_gpu = dev.type == "cuda"       # (a CPU device: the stub trainers of the host tests; monitors are then read synchronously)
+    pinned = torch.zeros(2, len(names), pin_memory=on_gpu)
     events = [None, None]
+    statics = {}                      # graph key -> the static draw tensors its graphs read
     pending = [None, None]
     series = {n: [] for n in names}
     dataset.set_image_size(G.image_size)
@@ -1054,7 +1253,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     def consume(slot):
         if events[slot] is None:
             return
-        events[slot].synchronize()
+        if on_gpu:
+            events[slot].synchronize()
         ep = pending[slot]
         vals = pinned[slot].tolist()
         events[slot] = None
@@ -1076,6 +1276,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     for epoch in range(epoch_init, epoch_final):
         if trainer.start_epoch(epoch, cfg.transit_sch):
             dataset.set_image_size(G.image_size)
+            ranks.assert_same(G.image_size, "the image size after a growth event")
         if on_epoch is not None:
             on_epoch(epoch, trainer)
         # number of critic steps this epoch (train.py:336-340); the score series lags one epoch here (deferred read-back)
@@ -1086,27 +1287,46 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
         if sim_decay > 0 and sim_lambda > 0:                          # train.py:343-348
             sim_lambda = cfg.sim_loss_lambda * (1 - sim_decay) ** (epoch - 1) if sim_lambda > 1e-5 else 0.0
         acc = torch.zeros(len(names), device=dev)
-        order = torch.randperm(n_images).tolist()                     # DataLoader(shuffle=True), train.py:153
-        for i in range(0, n_images, cfg.batch_size):
+        order = ranks.order(n_images, getattr(cfg, "seed", 0), epoch)   # DataLoader(shuffle=True), train.py:153
+        for k, i in enumerate(range(0, n_images, cfg.batch_size)):
+            batch = order[i:i + cfg.batch_size]                      # the global batch; this rank trains batch[lo:hi]
+            lo, hi = ranks.share(len(batch))
             if hasattr(dataset, "batch"):                          # device dataset: one augmentation launch per batch (data.py)
-                images = dataset.batch(order[i:i + cfg.batch_size])
+                images = dataset.batch(batch[lo:hi])
             else:
-                images = torch.stack([dataset[j] for j in order[i:i + cfg.batch_size]]).to(dev)
+                images = torch.stack([dataset[j] for j in batch[lo:hi]]).to(dev)
             b = images.size(0)
             trainer.n_critic = n_d_steps
-            stats = trainer.step(images, use_graph=use_graph)        # graphs are cached per shape until the next growth event
+            shared = {"global_batch": len(batch)} if ranks.world > 1 else {}
+            if draws is None:
+                stats = trainer.step(images, use_graph=use_graph, **shared)   # graphs are cached per shape until the next growth event
+            else:
+                own = _slice_draws(draws, epoch, k, len(batch), lo, hi, dev)
+                if use_graph and n_d_steps == 1:
+                    if not trainer.has_graph(images.shape, **shared):
+                        key = trainer._graph_key(images.shape, **shared)
+                        statics[key] = _clone_draws(own)
+                        trainer.capture(images, draws=statics[key], **shared)
+                    _fill_static(statics[trainer._graph_key(images.shape, **shared)], own)
+                    stats = trainer.replay(images, **shared)
+                else:
+                    stats = trainer.train_iteration(images, **own, **shared)
             g_loss = stats["G_loss"]
             if sim_lambda > 0:
                 # the reference adds similarity_loss(real images, latents) to the generator loss (train.py:379-381); it depends on
-                # neither network, so it changes the monitored value only
-                g_loss = g_loss + similarity_loss(images, trainer.last_z_g, sim_lambda)
+                # neither network, so it changes the monitored value only.  It couples all pairs of the GLOBAL batch: the ranks gather
+                # images and latents (DESIGN.md section 6 has the bytes) and every rank adds its share of the one global value
+                z_g = own["z_g"] if draws is not None and "z_g" in own else trainer.last_z_g
+                g_loss = g_loss + similarity_loss(ranks.gather_rows(images, len(batch)), ranks.gather_rows(z_g, len(batch)), sim_lambda)
             acc += b * torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss,
                                     stats["D_grad_pen"].float()])
         slot = epoch & 1
         consume(slot)
+        ranks.sum_(acc)                                                # N ranks: ONE all-reduce per epoch, of the five sums
         pinned[slot].copy_(acc / n_images, non_blocking=True)
-        events[slot] = torch.cuda.Event()
-        events[slot].record()
+        events[slot] = torch.cuda.Event() if on_gpu else True
+        if on_gpu:
+            events[slot].record()
         pending[slot] = epoch
         consume(slot ^ 1)                                              # the previous epoch's numbers are ready by now
         lr = lr_schedule(epoch, cfg.learning_rate, cfg.transit_sch, cfg.N_epochs)
@@ -1116,10 +1336,14 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
         if checkpoint is not None and epoch % cfg.checkpointing_period == 0:
             consume(slot)
             checkpoint.lr = trainer.opt_g.param_groups[0]["lr"]
-            checkpoint.save_state(epoch)
-            if samples_dir is not None:
-                from .utils import plot_gen_samples
-                plot_gen_samples(G, N_images=16, seed=0, filename=os.path.join(samples_dir, "Samples_{}_{:d}.png".format(cfg.ID, epoch)))
+            if ranks.rank == 0:                                        # replicas are identical: rank 0's state is everyone's
+                checkpoint.save_state(epoch)
+                if samples_dir is not None:
+                    from .utils import plot_gen_samples
+                    plot_gen_samples(G, N_images=16, seed=0, filename=os.path.join(samples_dir, "Samples_{}_{:d}.png".format(cfg.ID, epoch)))
+            else:
+                checkpoint.epoch = epoch
+            ranks.barrier()
     consume(0)
     consume(1)
     return series
@@ -1140,12 +1364,17 @@ def wgan_critic_steps(score_real, score_fake, n_critic, period=10):
 
 
 def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print, samples_dir=None,
-               eval_noise=None):
+               eval_noise=None, process_group=None, draws=None):
     """The reference's WGAN epoch loop (train.py:454-536): per epoch the SUMS over its batches of score_real, score_fake, D_loss and
     G_loss (printed every epoch, stored in the checkpoint's series); at the checkpoint period `save_state` and a 16-image grid from G in
     eval mode on `eval_noise` (drawn once at start-up, train.py:269).  adapt_critic: `wgan_critic_steps` over the series so far.
     sim_loss_lambda > 0: similarity_loss(images, latents) is added to the monitored G_loss (train.py:493-496; it depends on neither
-    network, so it changes no gradient).  Returns the per-epoch sums."""
+    network, so it changes no gradient).  Returns the per-epoch sums.
+
+    Data parallel (process_group, default the trainer's, a WGANTrainer(sync_batchnorm=True)): the sharding of `pggan_train`; a batch's
+    monitored value is the share-weighted mean over the ranks, the per-epoch sums of these are all-reduced once per epoch, rank 0
+    alone logs, saves and plots.  Eager whatever use_graph says (a synchronised BatchNorm is a collective; logged once).
+    draws(epoch, k, n_global) -> {"z_d", "z_g"}: optional global latents of batch k (z_d one tensor or one per critic step)."""
     from .utils import plot_gen_samples, similarity_loss
     G = trainer.G
     device = trainer.device
@@ -1155,9 +1384,16 @@ def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final
         eval_noise = sample_latent_vec((16, G.latent_dim), device=device)
     sim_lambda = float(getattr(cfg, 'sim_loss_lambda', 0.0) or 0.0)
     n_images = len(dataset)
+    ranks = _Ranks(trainer, process_group, n_images, cfg.batch_size)
+    if ranks.rank != 0:
+        log = lambda *a, **k: None    # noqa: E731
+    if ranks.world > 1 and use_graph:
+        log("wgan_train: {} ranks run eagerly (synchronised BatchNorm cannot be captured)".format(ranks.world))
+        use_graph = False
     n_critic_max = trainer.n_critic
     names = ("score_real", "score_fake", "D_loss", "G_loss")
     history = []
+    statics = {}
     if checkpoint is not None and epoch_init > 1:       # a resumed run continues the series it saved
         past = [dict(zip(names, v)) for v in zip(checkpoint.Loss_real[:epoch_init - 1], checkpoint.Loss_fake[:epoch_init - 1],
                                                  checkpoint.Loss_D[:epoch_init - 1], checkpoint.Loss_G[:epoch_init - 1])]
@@ -1169,19 +1405,39 @@ def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final
                 seen = past + history
                 trainer.n_critic = wgan_critic_steps([h["score_real"] for h in seen], [h["score_fake"] for h in seen], n_critic_max)
             acc = torch.zeros(len(names), device=device)
-            order = torch.randperm(n_images).tolist()                 # DataLoader(shuffle=True), train.py:153
-            for i in range(0, n_images, cfg.batch_size):
+            order = ranks.order(n_images, getattr(cfg, "seed", 0), epoch)   # DataLoader(shuffle=True), train.py:153
+            for k, i in enumerate(range(0, n_images, cfg.batch_size)):
+                batch = order[i:i + cfg.batch_size]                # the global batch; this rank trains batch[lo:hi]
+                lo, hi = ranks.share(len(batch))
                 if hasattr(dataset, "batch"):                      # device dataset: one augmentation launch per batch (data.py)
-                    images = dataset.batch(order[i:i + cfg.batch_size])
+                    images = dataset.batch(batch[lo:hi])
                 else:
-                    images = torch.stack([dataset[j] for j in order[i:i + cfg.batch_size]]).to(device)
+                    images = torch.stack([dataset[j] for j in batch[lo:hi]]).to(device)
                 images = images.float()
-                stats = trainer.step(images, use_graph=use_graph and trainer.n_critic == n_critic_max)
+                shared = {"global_batch": len(batch)} if ranks.world > 1 else {}
+                graph = use_graph and trainer.n_critic == n_critic_max
+                if draws is None:
+                    stats = trainer.step(images, use_graph=graph, **shared)
+                else:
+                    own = _slice_draws(draws, epoch, k, len(batch), lo, hi, device)
+                    if graph:                                      # (one rank only: see above)
+                        key = tuple(images.shape)
+                        if not trainer.has_graph(key):
+                            statics[key] = _clone_draws(own)
+                            trainer.capture(images, draws=statics[key])
+                        _fill_static(statics[key], own)
+                        stats = trainer.replay(images)
+                    else:
+                        stats = trainer.train_iteration(images, **own, **shared)
                 g_loss = stats["G_loss"]
                 if sim_lambda > 0:
-                    g_loss = g_loss + similarity_loss(images, trainer.last_z_g, sim_lambda)
-                acc += torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss])   # sums, one read per epoch
-            vals = acc.tolist()
+                    z_g = own["z_g"] if draws is not None and "z_g" in own else trainer.last_z_g
+                    g_loss = g_loss + similarity_loss(ranks.gather_rows(images, len(batch)), ranks.gather_rows(z_g, len(batch)), sim_lambda)
+                row = torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss])
+                # sums of the per-batch means (train.py:503-506), one read per epoch; N ranks: a batch's value is the share-weighted
+                # mean over the ranks
+                acc += row if ranks.world == 1 else row * (images.size(0) / len(batch))
+            vals = ranks.sum_(acc).tolist()
             if any(math.isnan(v) for v in vals):
                 raise ValueError('loss is nan at epoch {}'.format(epoch))
             sums = dict(zip(names, vals))
@@ -1194,10 +1450,14 @@ def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final
                 epoch, sums["score_real"], sums["score_fake"], sums["D_loss"], sums["G_loss"], trainer.n_critic))
             if checkpoint is not None and epoch % cfg.checkpointing_period == 0:
                 checkpoint.lr = trainer.opt_g.param_groups[0]["lr"]
-                checkpoint.save_state(epoch)
-                if samples_dir is not None:
-                    plot_gen_samples(G, eval_noise=eval_noise,
-                                     filename=os.path.join(samples_dir, 'Test_images_{}_{}.png'.format(cfg.ID, epoch)))
+                if ranks.rank == 0:
+                    checkpoint.save_state(epoch)
+                    if samples_dir is not None:
+                        plot_gen_samples(G, eval_noise=eval_noise,
+                                         filename=os.path.join(samples_dir, 'Test_images_{}_{}.png'.format(cfg.ID, epoch)))
+                else:
+                    checkpoint.epoch = epoch
+                ranks.barrier()
     finally:
         trainer.n_critic = n_critic_max
     return history
@@ -1241,42 +1501,73 @@ def build_arg_parser():
     p.add_argument('--images', type=str, default='', help='.pt / .npy file with the training images (N, C, R, R) in [-1, 1]; '
                                                           'synthetic uniform images when omitted')
     p.add_argument('--N_epochs_session', type=int, default=None)
+    p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
+                                                        'launch.py); batch_size stays the global batch')
     return p
 
 
 def cli_overrides(argv, options, names):
     """{name: value} of the configuration names given literally on the command line (train.py:95-104): only those override the
     configuration module or file"""
-    given = [a[2:] for a in argv if a.startswith('--') and a not in ('--configs', '--images')]   # train.py:95
+    given = [a[2:] for a in argv if a.startswith('--') and a not in ('--configs', '--images', '--gpus')]   # train.py:95
     return {a: getattr(options, a) for a in given if a in names}
 
 
-def make_trainer(config, G, D):
+def make_trainer(config, G, D, process_group=None, distributed=False):
     """The trainer `main()` trains with: RMSprop when config.RMSprop is set, else Adam with betas (beta1, 0.999) (train.py:220-225).
-    wgan without pggan: a WGANTrainer (weight clipping at 0.01, reference train.py:489-490); wgan with pggan is refused."""
+    wgan without pggan: a WGANTrainer (weight clipping at 0.01, reference train.py:489-490); wgan with pggan is refused.
+    distributed: a launched rank -- the trainer exchanges over `process_group` (None: the default group); the WGAN nets then train
+    with synchronised BatchNorm."""
     if config.wgan and config.pggan:
         raise ValueError("wgan=True together with pggan=True is not a configuration the reference can train (it fails at "
                          "Generator_net.image_size); choose one")
     if config.wgan:
-        kw = dict(learning_rate=config.learning_rate, drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, device_latents=True)
+        kw = dict(learning_rate=config.learning_rate, drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, device_latents=True,
+                  process_group=process_group, sync_batchnorm=bool(distributed))
         if config.RMSprop:
             return WGANTrainer(G, D, optimizer="rmsprop", **kw)
         return WGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
     kw = dict(learning_rate=config.learning_rate, grad_pen_lambda=config.grad_pen_lambda, drift_epsilon=config.drift_epsilon,
-              n_critic=config.n_critic, alpha_step=config.alpha_step, device_latents=True)
+              n_critic=config.n_critic, alpha_step=config.alpha_step, device_latents=True, process_group=process_group)
     if config.RMSprop:
         return PGGANTrainer(G, D, optimizer="rmsprop", **kw)
     return PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
 
 
 def main(argv=None):
-    """`python -m neuron_gan_amd.train ...` -- bootstrap of the reference's train.py:94-296, 623-625 for the PGGAN path."""
+    """The command line (`python neuron-gan_amd/launch.py ...`, or `load_package().train.main(argv)`): bootstrap of the reference's
+    train.py:94-296, 623-625.  `--gpus N` (N > 1) starts N rank processes and waits for them (launch.py); a process that finds RANK
+    and WORLD_SIZE in its environment is such a rank: cuda:LOCAL_RANK, an `nccl` process group, the same driver."""
     import sys
+    argv = list(sys.argv[1:] if argv is None else argv)
+    options = build_arg_parser().parse_args(argv)
+    launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ       # a rank of launch.py, or of any external launcher
+    if options.gpus > 1 and not launched:
+        # the launching process: it has not touched a GPU and never will (no call below this line runs in it)
+        from . import launch
+        return launch.launch(launch.launch_plan(options.gpus, argv))
+    if not launched:
+        return _train_main(argv, options, 0, None)
+    if not torch.cuda.is_available():
+        raise RuntimeError("the HIP path needs a GPU (there is no CPU fallback)")
+    local = int(os.environ.get("LOCAL_RANK", os.environ["RANK"]))
+    device = torch.device('cuda', local)
+    torch.cuda.set_device(device)
+    dist.init_process_group('nccl', rank=int(os.environ["RANK"]), world_size=int(os.environ["WORLD_SIZE"]), device_id=device)
+    try:
+        return _train_main(argv, options, local, dist.group.WORLD)
+    finally:
+        dist.destroy_process_group()
+
+
+def _train_main(argv, options, local_rank, group):
+    """main() in a process that trains: `group` None -- one GPU, no process group, today's run; else a rank of `group` on
+    cuda:local_rank.  Every rank reads the same configuration, images and checkpoint; its dataset's augmentation stream and its
+    device latents are seeded config.seed + rank."""
     from .configs import config
     from . import models
     from .utils import Checkpointer
-    argv = list(sys.argv[1:] if argv is None else argv)
-    options = build_arg_parser().parse_args(argv)
+    rank = dist.get_rank(group) if group is not None else 0
     overrides = cli_overrides(argv, options, config.configs_name)
     if options.configs:
         config.import_configs(options.configs, overrides, create_dirs=True)
@@ -1290,9 +1581,10 @@ def main(argv=None):
         raise NotImplementedError("the DCGAN path is disabled in the reference itself (train.py:629); choose pggan or wgan")
     if config.device != 'cuda':
         raise RuntimeError("the HIP path needs device='cuda' (there is no CPU fallback)")
-    config.print_configs()
-    torch.manual_seed(config.seed)
-    device = torch.device('cuda:0')
+    if rank == 0:
+        config.print_configs()
+    torch.manual_seed(config.seed)             # every rank builds the same nets; a rank's own streams are seeded below
+    device = torch.device('cuda', local_rank)
     n_up = len(config.N_gen_features) - 1
     if options.images:
         data = torch.load(options.images) if options.images.endswith('.pt') else torch.from_numpy(np.load(options.images))
@@ -1302,13 +1594,13 @@ def main(argv=None):
             # antialiased Resize to the stage resolution); it takes [0, 1] images and renormalises to [-1, 1] itself
             from .data import NeuronDataset
             dataset = NeuronDataset((data + 1.0) * 0.5, augmentations=True, im_translation=float(getattr(config, 'translation', 0.0)),
-                                    device=device, seed=config.seed)
+                                    device=device, seed=config.seed + rank)
         else:
             dataset = TensorImageDataset(data.to(device))
     else:
         dataset = TensorImageDataset.synthetic(16, config.image_size, config.N_colors, device=device)
     if config.wgan:
-        return _wgan_main(config, dataset, device, Checkpointer)
+        return _wgan_main(config, dataset, device, Checkpointer, group)
     size_init = dataset.image_size_max // (2 ** n_up)                                       # train.py:162-165
     G = models.Generator_PG(config.N_gen_features, image_size_init=size_init).to(device)    # train.py:172-175
     D = models.Discriminator_PG(config.N_dis_features, image_size_init=size_init).to(device)
@@ -1316,9 +1608,11 @@ def main(argv=None):
     # the trainer exists before the checkpoint is read, so that `--resume` also restores the optimiser state this implementation
     # adds to its checkpoints (Adam moments or RMSprop square averages, per-tensor step counts; the reference saves none,
     # utils.py:160-169)
-    trainer = make_trainer(config, G, D)
+    if rank > 0:
+        torch.manual_seed(config.seed + rank)  # latents (host and device generators): each rank draws its own
+    trainer = make_trainer(config, G, D, process_group=group, distributed=group is not None)
     checkpoint = Checkpointer(G, D, config.learning_rate, filename, N_epochs=config.N_epochs, device=device, extra_checkpoint_period=1e3,
-                              trainer=trainer)
+                              trainer=trainer, verbose=rank == 0)
     if config.resume and os.path.exists(filename):
         checkpoint.load_state()
     elif config.weights_init:
@@ -1331,10 +1625,10 @@ def main(argv=None):
         trainer.opt_g.set_lr(lr0)
     epoch_final = epoch_init + config.N_epochs_session if config.N_epochs_session else config.N_epochs + 1
     return pggan_train(trainer, dataset, config, checkpoint=checkpoint, epoch_init=epoch_init, epoch_final=epoch_final,
-                       samples_dir=config.samples_sub_dir)
+                       samples_dir=config.samples_sub_dir, process_group=group)
 
 
-def _wgan_main(config, dataset, device, Checkpointer):
+def _wgan_main(config, dataset, device, Checkpointer, group=None):
     """main() for wgan=True, pggan=False (train.py:172-180, 204-210, 269, 454-536)"""
     from . import models
     from .utils import init_weights
@@ -1346,9 +1640,12 @@ def _wgan_main(config, dataset, device, Checkpointer):
     if not resume and not config.weights_init:
         G.apply(init_weights)
         D.apply(init_weights)
-    trainer = make_trainer(config, G, D)
+    rank = dist.get_rank(group) if group is not None else 0
+    if rank > 0:
+        torch.manual_seed(config.seed + rank)  # latents: each rank draws its own (the nets above are the same on every rank)
+    trainer = make_trainer(config, G, D, process_group=group, distributed=group is not None)
     checkpoint = Checkpointer(G, D, config.learning_rate, filename, N_epochs=config.N_epochs, device=device, extra_checkpoint_period=1e3,
-                              trainer=trainer)
+                              trainer=trainer, verbose=rank == 0)
     if resume:
         checkpoint.load_state()
     elif config.weights_init:
@@ -1357,7 +1654,7 @@ def _wgan_main(config, dataset, device, Checkpointer):
     epoch_init = checkpoint.epoch + 1
     epoch_final = epoch_init + config.N_epochs_session if config.N_epochs_session else config.N_epochs + 1
     return wgan_train(trainer, dataset, config, checkpoint=checkpoint, epoch_init=epoch_init, epoch_final=epoch_final,
-                      samples_dir=config.samples_sub_dir, eval_noise=eval_noise)
+                      samples_dir=config.samples_sub_dir, eval_noise=eval_noise, process_group=group)
 
 
 if __name__ == '__main__':
