@@ -148,7 +148,9 @@ int ngan_conv3x3_wgrad_reduce_many(const void* entries, int n, void* stream);
  * bwdbwd: given h = dL/d(gc) of a bwd call made with gr == NULL:
  *           ggy = (h' - y*t)/r,  gy_out = -(s*h' + t*gy)/r,  gr_out = -C*(u - s*t)/r^2
  *           with h' = m*h, s = mean_c(gy*y), t = mean_c(h'*y), u = mean_c(h'*gy)
- * C must be a multiple of 4 with C/4 a power of two <= 64. */
+ * C is any multiple of 4.  C/4 a power of two <= 64 (C = 4, 8, 16 ... 256) runs in the lane-group kernels (C/4 consecutive lanes per
+ * pixel, butterfly reductions); every other C -- 48, 96, 320, 512, 1024 ... -- in csrc/wide.hip: one thread per pixel walking the
+ * channels, fixed summation order, meant for the wide presets' small images.  y may alias c and gc may alias gy (in-place calls). */
 int ngan_lrelu_pixelnorm_fwd(const float* c, const float* bias, float* y, float* rnorm, long npix, int C,
                              float slope, float eps, void* stream);
 int ngan_lrelu_pixelnorm_bwd(const float* gy, const float* gr, const float* y, const float* rnorm, float* gc,
@@ -197,7 +199,8 @@ int ngan_to_image_bwd_pnbwd_acc(const float* g, const float* t, const float* y, 
 int ngan_up2_fwd(const float* x, float* y, int B, int h, int w, int C, void* stream);
 int ngan_up2_adjoint(const float* gy, float* gx, int B, int h, int w, int C, void* stream);
 /* up2_adjoint followed by the backward of the LeakyReLU -> PixelNorm that produced the low-resolution tensor `yprev` (B,h,w,C) with
- * norms `rnorm`: out = m*(g' - yprev*mean_c(g'*yprev))/rnorm, g' = up2_adjoint(g).  C/4 a power of two <= 64. */
+ * norms `rnorm`: out = m*(g' - yprev*mean_c(g'*yprev))/rnorm, g' = up2_adjoint(g).  C is any multiple of 4: one fused kernel where C/4
+ * is a power of two <= 64, otherwise two launches (ngan_up2_adjoint into `out`, then the PixelNorm backward of csrc/wide.hip in place). */
 int ngan_up2_adjoint_pnbwd(const float* g, const float* yprev, const float* rnorm, float* out, int B, int h, int w, int C,
                            float slope, void* stream);
 int ngan_pool2_fwd(const float* x, float* y, int B, int h, int w, int C, void* stream);

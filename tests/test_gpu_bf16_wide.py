@@ -184,10 +184,20 @@ def _check(got, ref, absref, what):
 @pytest.mark.parametrize("C", WIDE_C)
 def test_wide_pixelnorm_operators_against_fp64(bf16_mode, C):
     """ngan_bf16_lrelu_pixelnorm_fwd / bwd / bwd2 / bwdbwd at channel counts of csrc/wide.hip"""
-    ngan = bf16_mode
+    _wide_pixelnorm_operators(bf16_mode, C, 96)
+
+
+@pytest.mark.parametrize("P", [257, 1000])
+@pytest.mark.parametrize("C", WIDE_C)
+def test_wide_pixelnorm_operators_across_blocks_against_fp64(bf16_mode, C, P):
+    """the same with more pixels than one 256-thread block of csrc/wide.hip's one-thread-per-pixel kernels: one pixel into the second
+    block, and three full blocks with a ragged fourth (same bounds)"""
+    _wide_pixelnorm_operators(bf16_mode, C, P)
+
+
+def _wide_pixelnorm_operators(ngan, C, P):
     Cc = ngan._C
     torch.manual_seed(C)
-    P = 96
     c = rbf(torch.randn(P, C))
     bias = torch.randn(C) * 0.3
     y = torch.empty(P, C, device=DEV, dtype=BF)
@@ -242,10 +252,19 @@ def test_wide_pixelnorm_operators_against_fp64(bf16_mode, C):
 @pytest.mark.parametrize("C", WIDE_C)
 def test_wide_channel_sum_and_image_edges_against_fp64(bf16_mode, C):
     """ngan_bf16_channel_sum, to_image_fwd / bwd (+ the PixelNorm-backward variant), from_image_dx / dw at csrc/wide.hip's widths"""
-    ngan = bf16_mode
+    _wide_channel_sum_and_image_edges(bf16_mode, C, 2, 8, 8)
+
+
+@pytest.mark.parametrize("C", WIDE_C)
+def test_wide_channel_sum_and_image_edges_across_blocks_against_fp64(bf16_mode, C):
+    """the same on 2 x 20 x 25 = 1000 pixels: three full 256-thread blocks and a ragged fourth (same bounds)"""
+    _wide_channel_sum_and_image_edges(bf16_mode, C, 2, 20, 25)
+
+
+def _wide_channel_sum_and_image_edges(ngan, C, B, H, W):
     Cc = ngan._C
     torch.manual_seed(5 * C)
-    B, H, W, Ncol = 2, 8, 8, 1
+    Ncol = 1
     P = B * H * W
     g = rbf(torch.randn(P, C))
     out = torch.empty(C, device=DEV)

@@ -62,11 +62,12 @@ def pn_ref(x):
     return x / torch.sqrt(torch.mean(x * x, dim=1, keepdim=True) + 1e-8)
 
 
-def run_both(f_hip, f_ref, tensors, grad_names, x_name=None, tol1=2e-4, tol2=1e-3):
+def run_both(f_hip, f_ref, tensors, grad_names, x_name=None, tol1=2e-4, tol2=1e-3, dev=DEV):
     """tensors: dict name -> fp32 CPU tensor in NCHW / parameter layout.  f_* take the dict, return one tensor (NCHW-like).
-    Checks forward, grads wrt grad_names, and (if x_name) grads of sum((dL/dx)^2) wrt grad_names."""
+    Checks forward, grads wrt grad_names, and (if x_name) grads of sum((dL/dx)^2) wrt grad_names.  dev: where f_hip's tensors live
+    ("cpu": tests/test_wide_f32_bounds_cpu.py holds torch's own fp32 evaluation to the same tolerances)."""
     ref_in = {k: v.double().clone().requires_grad_(k in grad_names or k == x_name) for k, v in tensors.items()}
-    hip_in = {k: v.to(DEV).clone().requires_grad_(k in grad_names or k == x_name) for k, v in tensors.items()}
+    hip_in = {k: v.to(dev).clone().requires_grad_(k in grad_names or k == x_name) for k, v in tensors.items()}
     out_r = f_ref(ref_in)
     out_h = f_hip(hip_in)
     assert out_h.shape == out_r.shape, (out_h.shape, out_r.shape)
@@ -75,7 +76,7 @@ def run_both(f_hip, f_ref, tensors, grad_names, x_name=None, tol1=2e-4, tol2=1e-
     v = torch.randn(out_r.shape, dtype=torch.float64)
     names = list(grad_names) + ([x_name] if x_name and x_name not in grad_names else [])
     gr = torch.autograd.grad((out_r * v).sum(), [ref_in[k] for k in names], create_graph=x_name is not None)
-    gh = torch.autograd.grad((out_h * v.float().to(DEV)).sum(), [hip_in[k] for k in names], create_graph=x_name is not None)
+    gh = torch.autograd.grad((out_h * v.float().to(dev)).sum(), [hip_in[k] for k in names], create_graph=x_name is not None)
     for k, a, b in zip(names, gh, gr):
         ok, info = grad_close(a, b, tol1)
         assert ok, f"grad {k}: (rel L2, outlier fraction) = {info}"
@@ -393,7 +394,7 @@ def test_conv_raw_all_orders(ngan, case, conv_precision):
     run_both(f_hip, f_ref, t, [k for k in t if k != "x"], x_name="x")
 
 
-@pytest.mark.parametrize("C", [16, 32, 64, 128])
+@pytest.mark.parametrize("C", [4, 8, 16, 32, 64, 128, 256])
 def test_lrelu_pixelnorm_all_orders(ngan, C):
     ops = ngan.ops
     torch.manual_seed(C)
@@ -433,7 +434,7 @@ def test_to_image_first_order(ngan):
              t, ["x", "w"])
 
 
-@pytest.mark.parametrize("C", [1, 16, 128])
+@pytest.mark.parametrize("C", [1, 8, 16, 128, 256])
 def test_resample_pairs(ngan, C):
     ops = ngan.ops
     torch.manual_seed(4)
