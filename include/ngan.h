@@ -329,6 +329,27 @@ size_t ngan_augment_workspace_bytes(int B, int P);
 int ngan_augment_batch(const float* src, const int* idx, const void* params, float* workspace, float* out,
                        int N, int B, int P, int R, int S, void* stream);
 
+/* ---- data set: the load loop of data/NeuronDataset.py:84-107 for a whole folder of 8-bit, one-colour, square images of one size R
+ * (decoded on the host): histogram, 4-class multi-Otsu thresholds (skimage.filters.threshold_multiotsu(img, classes=4)), mean and
+ * standard deviation of the noise floor, pad by R / 4 and Gaussian noise in every zero pixel (replace_zero_with_noise, 13-19).
+ * pixels = R * R <= 2^23, at most 65535 images per call (NGAN_ERR_SHAPE beyond).  Integer atomics only: results are reproducible.
+ *   images     (N, pixels) unsigned bytes           hist    (N, 256) counts, overwritten
+ *   thresholds (N, 3) levels t0 < t1 < t2: the lexicographically smallest triplet lo <= t0 < t1 < t2 <= hi - 1 (lo / hi: lowest /
+ *              highest occupied level) with the largest sum over the classes lo..t0, t0+1..t1, t1+1..t2, t2+1..hi of S^2 / P, where
+ *              P = sum h[v], S = sum v h[v] are exact integers, each term is evaluated in fp64 and an empty class contributes 0
+ *   record     (N, 3) doubles { count, mean, std } of the pixels 0 < v < t0 (population standard deviation), in level units
+ *   status     (N) 0 ok; 1 fewer than four occupied levels; 2 no pixel with 0 < v < t0 (thresholds and record are zeros for both)
+ *   workspace  ngan_multiotsu_workspace_bytes(N) bytes
+ *   normals    (N, P, P) standard-normal draws, P = R + 2 * (R / 4);  canvases (N, P, P) in [0, 1]: the source level (0 in the pad),
+ *              a level of 0 replaced by trunc(min(max(mean + std * draw, 0), 255)) in fp64, divided by 255.  normals and canvases
+ *              must be 16-byte aligned. */
+size_t ngan_multiotsu_workspace_bytes(int n_images);
+int ngan_u8_histogram(const unsigned char* images, unsigned int* hist, int n_images, long pixels, void* stream);
+int ngan_multiotsu4_noise_stats(const unsigned int* hist, void* workspace, int* thresholds, double* record, int* status,
+                                int n_images, void* stream);
+int ngan_u8_pad_noise_fill(const unsigned char* images, const float* normals, const double* record, float* canvases, int n_images,
+                           int R, void* stream);
+
 /* ==== bf16 activation storage ("bf16" mode, precision code 5): BASELINE.json's C2 configuration ==================================
  * The reference computes in the default dtype (/root/reference/train.py:136-144: fp32); this mode is an addition with its OWN,
  * stated tolerance -- never the headline.  The bounds are the ones the tests assert (tests/test_gpu_bf16.py, tests/test_gpu_bf16_wide.py),

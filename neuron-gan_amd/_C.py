@@ -65,6 +65,10 @@ SIGNATURES = {
     "ngan_rmsprop_step": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P],
     "ngan_linear_wgrad_rmsprop": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "ngan_augment_batch": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    # the data set (include/ngan.h, "data set" section)
+    "ngan_u8_histogram": [_P, _P, _I, _L, _P],
+    "ngan_multiotsu4_noise_stats": [_P, _P, _P, _P, _P, _I, _P],
+    "ngan_u8_pad_noise_fill": [_P, _P, _P, _P, _I, _I, _P],
     "ngan_conv3x3_up2_border": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],
     "ngan_first_block_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P],
     "ngan_first_block_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
@@ -105,6 +109,7 @@ NON_STATUS = {
     "ngan_last_error": ([], ctypes.c_char_p),
     "ngan_conv3x3_wgrad_workspace_bytes": ([_I, _I, _I, _I, _I], _Z),
     "ngan_augment_workspace_bytes": ([_I, _I], _Z),
+    "ngan_multiotsu_workspace_bytes": ([_I], _Z),
     "ngan_first_block_workspace_floats": ([_I, _I, _I], _Z),
     "ngan_first_block_table_floats": ([_I], _Z),
     "ngan_conv3x3_wgrad_kernel_name": ([_I, _I, _I, _I, _I, _I, _I, ctypes.c_char_p, _I], _I),

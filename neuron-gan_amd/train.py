@@ -1078,8 +1078,8 @@ class WGANTrainer:
 
 # =====================================================================================================================
 # Epoch-level driver and command line: the reference's train.py as functions instead of module-level code.
-# Out of scope and therefore absent: the PNG dataset with PIL/skimage augmentations (data/NeuronDataset.py), score plots,
-# gradient-norm histograms, interactive prompts.  Images come from a tensor file or are synthetic.
+# Out of scope and therefore absent: score plots, gradient-norm histograms, interactive prompts.  Images come from the folder
+# `dataset_dir` (data.NeuronDataset.from_directory), from a tensor file (`--images`) or are synthetic (`dataset_source`).
 # =====================================================================================================================
 class TensorImageDataset(torch.utils.data.Dataset):
     """Images (N, C, R, R) in [-1, 1] held on the GPU; `set_image_size` serves them at the current stage's resolution by
@@ -1513,6 +1513,22 @@ def cli_overrides(argv, options, names):
     return {a: getattr(options, a) for a in given if a in names}
 
 
+def dataset_source(argv, options, config):
+    """Where the training images come from: "images" (`--images file`), "directory" (config.dataset_dir exists: the reference's
+    way of running, train.py:147) or "synthetic".  A folder the user named -- `--dataset_dir` on the command line, or a value
+    other than the package's default once the `--configs` file has been read -- that does not exist is the reference's ValueError
+    (data/NeuronDataset.py:54-55); only the default folder, which a checkout does not hold, falls back to synthetic images."""
+    if options.images:
+        return "images"
+    if os.path.exists(config.dataset_dir):
+        return "directory"
+    default = os.path.abspath(config.configs_name['dataset_dir'])
+    on_cli = any(a == '--dataset_dir' or a.startswith('--dataset_dir=') for a in argv)
+    if on_cli or os.path.abspath(config.dataset_dir) != default:
+        raise ValueError('The dataset path {} does not exist.'.format(config.dataset_dir))
+    return "synthetic"
+
+
 def make_trainer(config, G, D, process_group=None, distributed=False):
     """The trainer `main()` trains with: RMSprop when config.RMSprop is set, else Adam with betas (beta1, 0.999) (train.py:220-225).
     wgan without pggan: a WGANTrainer (weight clipping at 0.01, reference train.py:489-490); wgan with pggan is refused.
@@ -1586,7 +1602,8 @@ def _train_main(argv, options, local_rank, group):
     torch.manual_seed(config.seed)             # every rank builds the same nets; a rank's own streams are seeded below
     device = torch.device('cuda', local_rank)
     n_up = len(config.N_gen_features) - 1
-    if options.images:
+    source = dataset_source(argv, options, config)
+    if source == "images":
         data = torch.load(options.images) if options.images.endswith('.pt') else torch.from_numpy(np.load(options.images))
         data = data.float()
         if data.dim() == 4 and data.shape[1] == 1:
@@ -1597,6 +1614,16 @@ def _train_main(argv, options, local_rank, group):
                                     device=device, seed=config.seed + rank)
         else:
             dataset = TensorImageDataset(data.to(device))
+    elif source == "directory":
+        # the reference's data set (train.py:147): every rank fills its canvases from the same seed, so all ranks hold the same
+        # images, and keeps its own augmentation stream
+        from .data import NeuronDataset
+        dataset = NeuronDataset.from_directory(config.dataset_dir, image_size=config.image_size, augmentations=True,
+                                               im_translation=float(config.translation), device=device, seed=config.seed + rank,
+                                               fill_seed=config.seed)
+        if rank == 0:
+            print('Dataset: {} images of {} x {} pixels from {}'.format(len(dataset), dataset.image_size_max, dataset.image_size_max,
+                                                                        config.dataset_dir))
     else:
         dataset = TensorImageDataset.synthetic(16, config.image_size, config.N_colors, device=device)
     if config.wgan:
