@@ -300,6 +300,35 @@ int ngan_rmsprop_step(float* p, const float* g, float* v, const long* seg_off, c
 int ngan_linear_wgrad_rmsprop(const float* z, const float* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K, int S,
                               int C, float scale, void* stream);
 
+/* ---- the averaged generator: an exponential moving average of the parameters (an addition of this implementation with no reference
+ * counterpart; opt-in, off by default) ------------------------------------------------------------------------------------------------
+ * Update rule, the same in every entry point below:   e' = fmaf(w, p' - e, e)
+ *   p'      the parameter value the step has just computed (the fp32 value it stores)
+ *   ema     the average e, laid out like p; fp32 in every arithmetic mode (the parameters are fp32 masters in the bf16 mode too)
+ *   ema_w   ONE device float, w = fp32(1 - beta) rounded on the host from the double: read by the kernel, so a captured graph replays
+ *           with the decay of the moment (as `hyper` does for the learning rate)
+ * The difference is rounded once and the fused multiply-add once, in every kernel, so all forms give the same bits.
+ * ngan_adam_step_ema / ngan_rmsprop_step_ema: the arguments of ngan_adam_step / ngan_rmsprop_step plus ema, ema_w.  Same work list,
+ *   same seg_active gating, same step-count launch; p, m, v and the step counts come out bit-identical to the plain entry points.  An
+ *   inactive tensor keeps its average.
+ * ngan_linear_wgrad_adam_ema / ngan_linear_wgrad_rmsprop_ema: the stem launches with the average updated in the same epilogue (ema is
+ *   the stem weight's slice); same shape rules (K a multiple of 16, at most 512) and host-side validation.
+ * ngan_ema_step: the update alone, e' = fmaf(w, p - e, e), for the active tensors of the same segment / chunk tables -- for a path
+ *   that cannot use a folded form, and the yardstick of the folded ones (plain step + this = folded step, bit for bit). */
+int ngan_adam_step_ema(float* p, const float* g, float* m, float* v, const long* seg_off, const long* seg_len,
+                       const int* seg_active, float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off,
+                       int n_chunks, const float* hyper, int n_hyper, float* ema, const float* ema_w, void* stream);
+int ngan_rmsprop_step_ema(float* p, const float* g, float* v, const long* seg_off, const long* seg_len, const int* seg_active,
+                          float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off, int n_chunks, const float* hyper,
+                          int n_hyper, float* ema, const float* ema_w, void* stream);
+int ngan_linear_wgrad_adam_ema(const float* z, const float* gc, float* p, float* m, float* v, const float* seg_step,
+                               const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, float* ema, const float* ema_w,
+                               void* stream);
+int ngan_linear_wgrad_rmsprop_ema(const float* z, const float* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K,
+                                  int S, int C, float scale, float* ema, const float* ema_w, void* stream);
+int ngan_ema_step(const float* p, float* ema, const long* seg_off, const long* seg_len, const int* seg_active, const int* chunk_seg,
+                  const long* chunk_off, int n_chunks, const float* ema_w, void* stream);
+
 /* ---- the critic's first layer pair as one operator (first-order passes): FromImage (ONE colour channel, models.py:161-165) folded
  * into the block's first 3x3 conv + LeakyReLU + PixelNorm (models.py:252-264).  f[c] = wf[c]*p + bf[c] is affine in one number per
  * pixel, so the conv over its C channels is a 3x3 conv over ONE channel with A[n][t] = scale*sum_c W[n][c][t]*wf[c] and a
@@ -432,6 +461,11 @@ int ngan_bf16_linear_wgrad_adam(const float* z, const ngan_bf16* gc, float* p, f
                                 const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, void* stream);
 int ngan_bf16_linear_wgrad_rmsprop(const float* z, const ngan_bf16* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K,
                                    int S, int C, float scale, void* stream);
+int ngan_bf16_linear_wgrad_adam_ema(const float* z, const ngan_bf16* gc, float* p, float* m, float* v, const float* seg_step,
+                                    const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, float* ema,
+                                    const float* ema_w, void* stream);
+int ngan_bf16_linear_wgrad_rmsprop_ema(const float* z, const ngan_bf16* gc, float* p, float* v, const float* hyper, int n_hyper, int B,
+                                       int K, int S, int C, float scale, float* ema, const float* ema_w, void* stream);
 int ngan_bf16_linear_dgrad(const ngan_bf16* gc, const float* Wt, float* gz, int B, int K, int S, int C, float scale, void* stream);
 int ngan_bf16_final_dot_fwd(const ngan_bf16* y, const float* W, const float* bias, float* out, int B, int S2, int C, float scale, void* stream);
 int ngan_bf16_final_dot_dx(const float* go, const float* W, ngan_bf16* gy, int B, int S2, int C, float scale, void* stream);

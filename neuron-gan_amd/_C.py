@@ -64,6 +64,12 @@ SIGNATURES = {
     "ngan_adam_step": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P],
     "ngan_rmsprop_step": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P],
     "ngan_linear_wgrad_rmsprop": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    # the averaged generator (include/ngan.h): the plain steps' arguments plus ema, ema_w
+    "ngan_adam_step_ema": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P],
+    "ngan_rmsprop_step_ema": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P],
+    "ngan_linear_wgrad_adam_ema": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P],
+    "ngan_linear_wgrad_rmsprop_ema": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P],
+    "ngan_ema_step": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "ngan_augment_batch": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     # the data set (include/ngan.h, "data set" section)
     "ngan_u8_histogram": [_P, _P, _I, _L, _P],
@@ -98,7 +104,8 @@ SIGNATURES = {
 for _op in ("lrelu_pixelnorm_fwd", "lrelu_pixelnorm_bwd", "lrelu_pixelnorm_bwd2", "lrelu_pixelnorm_bwdbwd", "channel_sum", "channel_sum_acc",
             "from_image_fwd", "from_image_dx", "from_image_dw", "from_image_dw_acc", "to_image_fwd", "to_image_bwd", "to_image_bwd_pnbwd",
             "to_image_bwd_pnbwd_acc", "up2_fwd", "up2_adjoint", "up2_adjoint_pnbwd", "pool2_fwd", "pool2_adjoint", "lerp", "fade_bwd",
-            "linear_lrelu_pn_fwd", "linear_wgrad", "linear_wgrad_acc", "linear_wgrad_adam", "linear_wgrad_rmsprop", "linear_dgrad", "final_dot_fwd", "final_dot_dx",
+            "linear_lrelu_pn_fwd", "linear_wgrad", "linear_wgrad_acc", "linear_wgrad_adam", "linear_wgrad_rmsprop", "linear_wgrad_adam_ema", "linear_wgrad_rmsprop_ema",
+            "linear_dgrad", "final_dot_fwd", "final_dot_dx",
             "final_dot_dw", "final_dot_dw_acc"):
     SIGNATURES["ngan_bf16_" + _op] = SIGNATURES["ngan_" + _op]
 SIGNATURES["ngan_bf16_conv3x3_fwd"] = [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P]

@@ -11,11 +11,12 @@ The directory name carries a hyphen, so it is loaded under the module name `neur
     utils.py           sample_latent_vec
     configs/config.py  module-as-singleton configuration
     train.py           the G/D step driver (flat parameters, fused Adam, data-parallel gradient exchange), epoch driver, CLI
+    eval.py            sample grid from a checkpoint (the reference's eval.py), optionally from the averaged generator
     launch.py          sharding rule of a data-parallel run and the `--gpus N` rank launcher (standard library only)
     data.py            device-resident dataset with the reference's augmentation chain as one launch per batch
     workmodel.py       algorithmic FLOP / byte model of an iteration (what bench.py's roofline figures divide by)
 """
-from . import _C, launch, ops, wgan_ops, utils, models, loss_functions, train, data, workmodel  # noqa: F401
+from . import _C, launch, ops, wgan_ops, utils, models, loss_functions, train, data, workmodel, eval  # noqa: F401, A004
 from .configs import config  # noqa: F401
 
 __version__ = "0.1.0"

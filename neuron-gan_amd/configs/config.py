@@ -28,7 +28,7 @@ _DEFAULTS = dict(
     # training
     ID=uuid.uuid4().hex[:4], RMSprop=False, learning_rate=0.0001, batch_size=8, N_epochs=150000, N_epochs_session=None,
     beta1=0.5, sim_loss_lambda=0.0, sim_loss_lambda_decay_rate=0.0, drift_epsilon=0.001, resume=False, N_workers=2,
-    seed=1, checkpointing_period=100, device='default', pin_memory=False,
+    seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -85,6 +85,9 @@ def validate_configs(create_dirs=False):
     assert g['image_size'] == 2 ** image_size_log, 'Image size must be a power of 2.'
     assert g['device'] in ['cpu', 'cuda', 'mps'], f"device:{g['device']} is not supported."
     assert g['ID'] != '', 'The training ID is undefined.'
+    # the averaged generator (an addition of this implementation): 0 is off, otherwise the decay
+    if not (isinstance(g['ema_beta'], (int, float)) and 0 <= g['ema_beta'] < 1):
+        raise ValueError(f"ema_beta={g['ema_beta']!r} must lie in [0, 1)")
     if g['pggan']:
         err_msg = 'The number of layers in the generator and discriminator must match.'
         assert len(g['N_gen_features']) == len(g['N_dis_features']), err_msg

@@ -140,9 +140,15 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float* __restri
 // of the parameter and its optimiser state (p, m, v are the tensor's slices of the flat buffers, m unused by RMSprop; step / hyper as in
 // ngan_adam_step / ngan_rmsprop_step).  The stem holds 16.8 M of the generator's 17.1 M parameters: the stored form costs a 67 MB zero
 // fill, a 67 MB read-modify-write here and a 67 MB read in the flat optimiser kernel.
+// EMA (with STEM_ADAM / STEM_RMSPROP): the lane also updates its elements of the averaged weights, e' = ema_update(w, p', e), while
+// the new p' is still in its registers -- a separate pass would read the 67 MB of p again.  e is loaded together with p, m, v (one
+// more quad in flight per step of the epilogue loop, issued before the arithmetic waits for any of them).
 enum StemRule { STEM_STORE = 0, STEM_ADAM = 1, STEM_RMSPROP = 2 };
-struct StemUpdate { float* p; float* m; float* v; const float* hyper; const float* step; };
-template <typename T, int NT, int RULE = STEM_STORE>
+struct StemUpdate { float* p; float* m; float* v; const float* hyper; const float* step; float* ema; const float* ema_w; };
+__device__ __forceinline__ void stem_ema(float* e, float w, const float4& pv, const float4& ev) {
+    st4(e, make_float4(ema_update(w, pv.x, ev.x), ema_update(w, pv.y, ev.y), ema_update(w, pv.z, ev.z), ema_update(w, pv.w, ev.w)));
+}
+template <typename T, int NT, int RULE = STEM_STORE, bool EMA = false>
 __global__ __launch_bounds__(256) void linear_wgrad_mfma_kernel(const float* __restrict__ z, const T* __restrict__ gc,
                                                                 float* __restrict__ gW, int B, int K, int S, int C, float scale,
                                                                 int accumulate, StemUpdate ad = StemUpdate{}) {
@@ -171,11 +177,13 @@ __global__ __launch_bounds__(256) void linear_wgrad_mfma_kernel(const float* __r
     if (RULE == STEM_ADAM) {
         if (rok) {
             const AdamCoef k = adam_coef(ad.hyper, ad.step[0]);
+            const float w = EMA ? ad.ema_w[0] : 0.f;
             const long o = row * K + kq * 4;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
                 if (t < nt) {
                     float4 pv = ld4(ad.p + o + t * 16), mv = ld4(ad.m + o + t * 16), vv = ld4(ad.v + o + t * 16);
+                    const float4 ev = EMA ? ld4(ad.ema + o + t * 16) : f4zero();
                     adam_update(k, acc[t][0] * scale, pv.x, mv.x, vv.x);
                     adam_update(k, acc[t][1] * scale, pv.y, mv.y, vv.y);
                     adam_update(k, acc[t][2] * scale, pv.z, mv.z, vv.z);
@@ -183,6 +191,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_mfma_kernel(const float* __r
                     st4(ad.m + o + t * 16, mv);
                     st4(ad.v + o + t * 16, vv);
                     st4(ad.p + o + t * 16, pv);
+                    if (EMA) stem_ema(ad.ema + o + t * 16, w, pv, ev);
                 }
         }
         return;
@@ -190,17 +199,20 @@ __global__ __launch_bounds__(256) void linear_wgrad_mfma_kernel(const float* __r
     if (RULE == STEM_RMSPROP) {
         if (rok) {
             const RmspropCoef k = rmsprop_coef(ad.hyper);
+            const float w = EMA ? ad.ema_w[0] : 0.f;
             const long o = row * K + kq * 4;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
                 if (t < nt) {
                     float4 pv = ld4(ad.p + o + t * 16), vv = ld4(ad.v + o + t * 16);
+                    const float4 ev = EMA ? ld4(ad.ema + o + t * 16) : f4zero();
                     rmsprop_update(k, acc[t][0] * scale, pv.x, vv.x);
                     rmsprop_update(k, acc[t][1] * scale, pv.y, vv.y);
                     rmsprop_update(k, acc[t][2] * scale, pv.z, vv.z);
                     rmsprop_update(k, acc[t][3] * scale, pv.w, vv.w);
                     st4(ad.v + o + t * 16, vv);
                     st4(ad.p + o + t * 16, pv);
+                    if (EMA) stem_ema(ad.ema + o + t * 16, w, pv, ev);
                 }
         }
         return;
@@ -409,19 +421,31 @@ extern "C" int ngan_bf16_linear_wgrad(const float* z, const ngan_bf16* gc, float
     return linear_wgrad_impl<__bf16>(z, BF(gc), gW, B, K, S, C, scale, 0, stream);
 }
 
-template <typename T>
+// EMA: the `_ema` entry points (ema, ema_w required); otherwise both are null and the plain instantiations run
+template <typename T, bool EMA = false>
 static int linear_wgrad_adam_impl(const float* z, const T* gc, float* p, float* m, float* v, const float* seg_step,
-                                  const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, void* stream) {
-    NGAN_REQUIRE(z && gc && p && m && v && seg_step && hyper, NGAN_ERR_ARG, "linear_wgrad_adam: null pointer");
+                                  const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, void* stream,
+                                  float* ema = nullptr, const float* ema_w = nullptr) {
+    NGAN_REQUIRE(z && gc && p && m && v && seg_step && hyper && (!EMA || (ema && ema_w)), NGAN_ERR_ARG, "linear_wgrad_adam: null pointer");
     NGAN_REQUIRE(n_hyper == NGAN_ADAM_HYPER_FLOATS, NGAN_ERR_ARG, "linear_wgrad_adam: hyper holds %d floats, this library reads %d (include/ngan.h)",
                  n_hyper, NGAN_ADAM_HYPER_FLOATS);
     NGAN_REQUIRE(B > 0 && S > 0 && C > 0 && K > 0 && K % 16 == 0 && K <= 512, NGAN_ERR_SHAPE,
                  "linear_wgrad_adam: B=%d K=%d S=%d C=%d unsupported (K a multiple of 16, at most 512)", B, K, S, C);
     const dim3 grid(ngan::ceil_div((long)C * S, 64)), block(256);
-    const StemUpdate ad{p, m, v, hyper, seg_step};
-    if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, STEM_ADAM>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
-    else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, STEM_ADAM>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
-    return ngan::launch_status("ngan_linear_wgrad_adam");
+    const StemUpdate ad{p, m, v, hyper, seg_step, ema, ema_w};
+    if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, STEM_ADAM, EMA>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
+    else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, STEM_ADAM, EMA>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
+    return ngan::launch_status(EMA ? "ngan_linear_wgrad_adam_ema" : "ngan_linear_wgrad_adam");
+}
+extern "C" int ngan_linear_wgrad_adam_ema(const float* z, const float* gc, float* p, float* m, float* v, const float* seg_step,
+                                          const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, float* ema,
+                                          const float* ema_w, void* stream) {
+    return linear_wgrad_adam_impl<float, true>(z, gc, p, m, v, seg_step, hyper, n_hyper, B, K, S, C, scale, stream, ema, ema_w);
+}
+extern "C" int ngan_bf16_linear_wgrad_adam_ema(const float* z, const ngan_bf16* gc, float* p, float* m, float* v, const float* seg_step,
+                                               const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, float* ema,
+                                               const float* ema_w, void* stream) {
+    return linear_wgrad_adam_impl<__bf16, true>(z, BF(gc), p, m, v, seg_step, hyper, n_hyper, B, K, S, C, scale, stream, ema, ema_w);
 }
 extern "C" int ngan_linear_wgrad_adam(const float* z, const float* gc, float* p, float* m, float* v, const float* seg_step,
                                       const float* hyper, int n_hyper, int B, int K, int S, int C, float scale, void* stream) {
@@ -432,19 +456,27 @@ extern "C" int ngan_bf16_linear_wgrad_adam(const float* z, const ngan_bf16* gc, 
     return linear_wgrad_adam_impl<__bf16>(z, BF(gc), p, m, v, seg_step, hyper, n_hyper, B, K, S, C, scale, stream);
 }
 
-template <typename T>
+template <typename T, bool EMA = false>
 static int linear_wgrad_rmsprop_impl(const float* z, const T* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K, int S,
-                                     int C, float scale, void* stream) {
-    NGAN_REQUIRE(z && gc && p && v && hyper, NGAN_ERR_ARG, "linear_wgrad_rmsprop: null pointer");
+                                     int C, float scale, void* stream, float* ema = nullptr, const float* ema_w = nullptr) {
+    NGAN_REQUIRE(z && gc && p && v && hyper && (!EMA || (ema && ema_w)), NGAN_ERR_ARG, "linear_wgrad_rmsprop: null pointer");
     NGAN_REQUIRE(n_hyper == NGAN_RMSPROP_HYPER_FLOATS, NGAN_ERR_ARG,
                  "linear_wgrad_rmsprop: hyper holds %d floats, this library reads %d (include/ngan.h)", n_hyper, NGAN_RMSPROP_HYPER_FLOATS);
     NGAN_REQUIRE(B > 0 && S > 0 && C > 0 && K > 0 && K % 16 == 0 && K <= 512, NGAN_ERR_SHAPE,
                  "linear_wgrad_rmsprop: B=%d K=%d S=%d C=%d unsupported (K a multiple of 16, at most 512)", B, K, S, C);
     const dim3 grid(ngan::ceil_div((long)C * S, 64)), block(256);
-    const StemUpdate ad{p, nullptr, v, hyper, nullptr};
-    if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, STEM_RMSPROP>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
-    else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, STEM_RMSPROP>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
-    return ngan::launch_status("ngan_linear_wgrad_rmsprop");
+    const StemUpdate ad{p, nullptr, v, hyper, nullptr, ema, ema_w};
+    if (K <= 128) hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 8, STEM_RMSPROP, EMA>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
+    else hipLaunchKernelGGL((linear_wgrad_mfma_kernel<T, 32, STEM_RMSPROP, EMA>), grid, block, 0, (hipStream_t)stream, z, gc, nullptr, B, K, S, C, scale, 0, ad);
+    return ngan::launch_status(EMA ? "ngan_linear_wgrad_rmsprop_ema" : "ngan_linear_wgrad_rmsprop");
+}
+extern "C" int ngan_linear_wgrad_rmsprop_ema(const float* z, const float* gc, float* p, float* v, const float* hyper, int n_hyper, int B,
+                                             int K, int S, int C, float scale, float* ema, const float* ema_w, void* stream) {
+    return linear_wgrad_rmsprop_impl<float, true>(z, gc, p, v, hyper, n_hyper, B, K, S, C, scale, stream, ema, ema_w);
+}
+extern "C" int ngan_bf16_linear_wgrad_rmsprop_ema(const float* z, const ngan_bf16* gc, float* p, float* v, const float* hyper, int n_hyper,
+                                                  int B, int K, int S, int C, float scale, float* ema, const float* ema_w, void* stream) {
+    return linear_wgrad_rmsprop_impl<__bf16, true>(z, BF(gc), p, v, hyper, n_hyper, B, K, S, C, scale, stream, ema, ema_w);
 }
 extern "C" int ngan_linear_wgrad_rmsprop(const float* z, const float* gc, float* p, float* v, const float* hyper, int n_hyper, int B, int K,
                                          int S, int C, float scale, void* stream) {

@@ -96,6 +96,11 @@ __device__ __forceinline__ void rmsprop_update(const RmspropCoef& k, float g, fl
     v = vv;
     p -= k.lr * (gv / (sqrtf(vv) + k.eps));                        // p.addcdiv_(g, sqrt(v) + eps, -lr)
 }
+// One element of the averaged generator (an addition of this implementation, off by default): e' = e + w (p' - e) with w = 1 - beta
+// rounded from the host's double and p' the parameter value the step has just stored.  The difference is rounded once and the fused
+// multiply-add once; the fmaf is explicit, so the folded forms (adam.hip, the stem epilogues of linear.hip) and ngan_ema_step give
+// the same bits whatever the compiler contracts elsewhere.  The average is fp32 in every arithmetic mode.
+__device__ __forceinline__ float ema_update(float w, float p, float e) { return fmaf(w, p - e, e); }
 
 // ---- activation storage type (round 4: "bf16" mode, precision code 5 of include/ngan.h) -------------------------------------------
 // Every kernel that reads or writes an ACTIVATION tensor (a conv / stem / FromImage output, or the gradient w.r.t. one) is a template

@@ -558,18 +558,22 @@ class Generator_PG(_ProgressiveNet):
         self.ToIm = self.ToIm_list.pop(0)
 
     @classmethod
-    def from_state_dict(cls, filename, device=torch.device('cpu'), verbose=True):
+    def from_state_dict(cls, filename, device=torch.device('cpu'), verbose=True, use_ema=False):
         """Rebuild a generator from a checkpoint written by `Checkpointer` (reference models.py:394-444), including
-        checkpoints in the older layout that still carry merged ToIm_list / conv_block_list entries."""
-        from .utils import load_checkpoint_dict
+        checkpoints in the older layout that still carry merged ToIm_list / conv_block_list entries.
+        use_ema: load the averaged weights ('Generator_ema_state', written by a trainer with ema_beta > 0) instead of the training
+        weights; KeyError if the file holds none."""
+        from .utils import EMA_KEY, load_checkpoint_dict
         saved = load_checkpoint_dict(filename, device)
+        if use_ema and EMA_KEY not in saved:
+            raise KeyError(f"{EMA_KEY}: {filename} holds no averaged generator (it was written without ema_beta)")
         attrs = saved['Generator_attrs']
         ctor = {k: attrs[k] for k in ('N_features_per_layer', 'image_size_init', 'LeakyReLU_neg_slope', 'N_colors') if k in attrs}
         if 'latent_dim' in attrs:
             ctor['latent_dim'] = attrs['latent_dim']
         obj = cls(**ctor)
         obj.set_resolution(attrs['image_size'], float(attrs['alpha']))
-        state = saved['Generator_state']
+        state = saved[EMA_KEY] if use_ema else saved['Generator_state']
         n_toim = _count_list_entries(state, 'ToIm_list')
         if n_toim > len(obj.ToIm_list):
             if verbose:

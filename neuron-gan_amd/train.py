@@ -35,7 +35,8 @@ class FlatParams:
     """All parameters of a net as views into one flat buffer (plus flat grad / optimiser state buffers).
 
     state: the names of the optimiser's state buffers to allocate (`FusedAdam.STATE`, the default, or `FusedRMSprop.STATE`); the
-    others are None -- a RMSprop trainer holds no first-moment buffer (70 MB at the default widths)."""
+    others are None -- a RMSprop trainer holds no first-moment buffer (70 MB at the default widths).
+    ema: the averaged weights (`enable_ema`), None unless an optimiser was asked to average."""
 
     def __init__(self, net: torch.nn.Module, state=("exp_avg", "exp_avg_sq")):
         self.params = list(net.parameters())
@@ -50,6 +51,7 @@ class FlatParams:
         self.flat = torch.zeros(total, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(total, device=dev, dtype=torch.float32)
         self.exp_avg = self.exp_avg_sq = self.square_avg = None
+        self.ema = self._swap_scratch = None
         self.state_names = tuple(state)
         for name in self.state_names:
             assert name in ("exp_avg", "exp_avg_sq", "square_avg"), name
@@ -84,6 +86,28 @@ class FlatParams:
     def zero_grad(self):
         self.grad.zero_()
 
+    def enable_ema(self):
+        """Allocate the averaged weights: `total` fp32 elements laid out like `flat`, a copy of `flat` as it is now (no zero start,
+        hence no bias correction)."""
+        if self.ema is None:
+            self.ema = self.flat.clone()
+        return self.ema
+
+    def swap_ema(self):
+        """Exchange the contents of `flat` and `ema` in place, bit for bit.  The parameters are views of `flat` and captured graphs hold
+        its address, so the buffers stay where they are; the exchange goes through a 4 MB scratch (kept), not a second copy of the net.
+        The caller refreshes the packed conv weights (PGGANTrainer.averaged_generator)."""
+        assert self.ema is not None, "no averaged weights: enable_ema() first"
+        n = min(self.total, 1 << 20)
+        if self._swap_scratch is None:
+            self._swap_scratch = torch.empty(n, device=self.flat.device, dtype=torch.float32)
+        for o in range(0, self.total, n):
+            a, b = self.flat[o:o + n], self.ema[o:o + n]
+            t = self._swap_scratch[:a.numel()]
+            t.copy_(a)
+            a.copy_(b)
+            b.copy_(t)
+
     def ensure_grad_views(self):
         """Re-attach .grad views if something (e.g. Module.zero_grad) detached them."""
         for p, off in zip(self.params, self.offsets):
@@ -97,13 +121,33 @@ class _FlatOptimizer:
     replays with the learning rate of the moment."""
     KIND = STATE = GRAD_SCALE = None      # set by the subclass: checkpoint kind, FlatParams buffers, index of grad_scale in `hyper`
 
-    def __init__(self, flat: FlatParams, lr, hyper_host):
+    ema_fold = True      # False: the plain launches followed by ngan_ema_step (the form the fold is measured against)
+
+    def __init__(self, flat: FlatParams, lr, hyper_host, ema_beta=None):
         missing = [b for b in self.STATE if getattr(flat, b) is None]
         assert not missing, f"FlatParams(net, state={self.STATE}) is missing {missing}"
         self.flat = flat
         self.hyper_host = hyper_host
         self.hyper = torch.tensor(self.hyper_host, dtype=torch.float32, device=flat.flat.device)
         self.param_groups = [{"lr": float(lr)}]  # same handle the reference's update_lr() writes to (train.py:253-265)
+        # ema_beta: keep e' = e + (1 - beta)(p' - e) of every parameter this optimiser updates (flat.ema), inside the step's own
+        # launches.  None: no buffer, and exactly the launches of a build without the feature.
+        self.ema_beta = self.ema_w = None
+        if ema_beta is not None:
+            flat.enable_ema()
+            self.ema_w = torch.zeros(1, dtype=torch.float32, device=flat.flat.device)
+            self.set_ema_beta(ema_beta)
+
+    def set_ema_beta(self, beta):
+        """the decay of the average from the next step on; w = fp32(1 - beta), rounded from the double, lives in one device float the
+        kernels read, so captured graphs replay with it"""
+        if self.ema_w is None:
+            raise RuntimeError("this optimiser keeps no average (ema_beta=None at construction)")
+        beta = float(beta)
+        if not 0.0 < beta < 1.0:
+            raise ValueError(f"ema_beta must lie in (0, 1), got {beta}")
+        self.ema_beta = beta
+        self.ema_w.copy_(torch.tensor([1.0 - beta], dtype=torch.float32), non_blocking=True)
 
     def set_lr(self, lr):
         self.param_groups[0]["lr"] = float(lr)
@@ -129,10 +173,14 @@ class _FlatOptimizer:
             assert f.active_host[0] == 1, "the stem is active at every stage"
             n0 = (f.params[0].numel() + ADAM_CHUNK - 1) // ADAM_CHUNK
         n_chunks = int(f.chunk_seg.numel()) - n0
-        self._flat_step(f, n0, n_chunks)                  # also advances every active step count
+        fold = self.ema_w is not None and self.ema_fold
+        self._flat_step(f, n0, n_chunks, fold)            # also advances every active step count
         if stem_factors is not None:
             z, gc, s2, c, scale = stem_factors
-            self._stem_step(f, f.params[0].numel(), z, gc, s2, c, float(scale))
+            self._stem_step(f, f.params[0].numel(), z, gc, s2, c, float(scale), fold)
+        if self.ema_w is not None and not fold:
+            _C.call("ngan_ema_step", f.flat, f.ema, f.seg_off, f.seg_len, f.seg_active, f.chunk_seg, f.chunk_off,
+                    int(f.chunk_seg.numel()), self.ema_w)
         self.repack()
 
     def repack(self):
@@ -145,19 +193,28 @@ class FusedAdam(_FlatOptimizer):
     """optim.Adam(params, lr, betas=(beta1, 0.999)) semantics of train.py:224-225 in one kernel launch."""
     KIND, STATE, GRAD_SCALE = "adam", ("exp_avg", "exp_avg_sq"), 4
 
-    def __init__(self, flat: FlatParams, lr=1e-4, betas=(0.5, 0.999), eps=1e-8):
+    def __init__(self, flat: FlatParams, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, ema_beta=None):
         # {lr, beta1, beta2, eps, grad_scale, 1 - beta1, 1 - beta2, ln beta1, ln beta2}: include/ngan.h, ngan_adam_step
         super().__init__(flat, lr, [float(lr), float(betas[0]), float(betas[1]), float(eps), 1.0, 1.0 - float(betas[0]),
                                     1.0 - float(betas[1]),
-                                    *(math.log(float(b)) if float(b) > 0 else float("-inf") for b in betas)])   # (beta = 0: 1 - 0^t = 1)
+                                    *(math.log(float(b)) if float(b) > 0 else float("-inf") for b in betas)],   # (beta = 0: 1 - 0^t = 1)
+                         ema_beta)
 
-    def _flat_step(self, f, n0, n_chunks):
-        _C.call("ngan_adam_step", f.flat, f.grad, f.exp_avg, f.exp_avg_sq, f.seg_off, f.seg_len, f.seg_active, f.seg_step,
+    def _flat_step(self, f, n0, n_chunks, ema=False):
+        args = (f.flat, f.grad, f.exp_avg, f.exp_avg_sq, f.seg_off, f.seg_len, f.seg_active, f.seg_step,
                 len(f.params), f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel())
+        if ema:
+            _C.call("ngan_adam_step_ema", *args, f.ema, self.ema_w)
+        else:
+            _C.call("ngan_adam_step", *args)
 
-    def _stem_step(self, f, n, z, gc, s2, c, scale):
-        _C.call(ops._k("ngan_linear_wgrad_adam", gc), z, gc, f.flat[:n], f.exp_avg[:n], f.exp_avg_sq[:n], f.seg_step[:1], self.hyper,
+    def _stem_step(self, f, n, z, gc, s2, c, scale, ema=False):
+        args = (z, gc, f.flat[:n], f.exp_avg[:n], f.exp_avg_sq[:n], f.seg_step[:1], self.hyper,
                 self.hyper.numel(), z.shape[0], z.shape[1], s2, c, scale)
+        if ema:
+            _C.call(ops._k("ngan_linear_wgrad_adam_ema", gc), *args, f.ema[:n], self.ema_w)
+        else:
+            _C.call(ops._k("ngan_linear_wgrad_adam", gc), *args)
 
 
 class FusedRMSprop(_FlatOptimizer):
@@ -166,17 +223,24 @@ class FusedRMSprop(_FlatOptimizer):
     square_avg; per-tensor step counts are kept as torch keeps state['step'], though the update does not read them."""
     KIND, STATE, GRAD_SCALE = "rmsprop", ("square_avg",), 3
 
-    def __init__(self, flat: FlatParams, lr=1e-4, alpha=0.99, eps=1e-8):
+    def __init__(self, flat: FlatParams, lr=1e-4, alpha=0.99, eps=1e-8, ema_beta=None):
         # {lr, alpha, eps, grad_scale, 1 - alpha}: include/ngan.h, ngan_rmsprop_step (1 - alpha rounded from the double, as torch)
-        super().__init__(flat, lr, [float(lr), float(alpha), float(eps), 1.0, 1.0 - float(alpha)])
+        super().__init__(flat, lr, [float(lr), float(alpha), float(eps), 1.0, 1.0 - float(alpha)], ema_beta)
 
-    def _flat_step(self, f, n0, n_chunks):
-        _C.call("ngan_rmsprop_step", f.flat, f.grad, f.square_avg, f.seg_off, f.seg_len, f.seg_active, f.seg_step, len(f.params),
+    def _flat_step(self, f, n0, n_chunks, ema=False):
+        args = (f.flat, f.grad, f.square_avg, f.seg_off, f.seg_len, f.seg_active, f.seg_step, len(f.params),
                 f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel())
+        if ema:
+            _C.call("ngan_rmsprop_step_ema", *args, f.ema, self.ema_w)
+        else:
+            _C.call("ngan_rmsprop_step", *args)
 
-    def _stem_step(self, f, n, z, gc, s2, c, scale):
-        _C.call(ops._k("ngan_linear_wgrad_rmsprop", gc), z, gc, f.flat[:n], f.square_avg[:n], self.hyper, self.hyper.numel(),
-                z.shape[0], z.shape[1], s2, c, scale)
+    def _stem_step(self, f, n, z, gc, s2, c, scale, ema=False):
+        args = (z, gc, f.flat[:n], f.square_avg[:n], self.hyper, self.hyper.numel(), z.shape[0], z.shape[1], s2, c, scale)
+        if ema:
+            _C.call(ops._k("ngan_linear_wgrad_rmsprop_ema", gc), *args, f.ema[:n], self.ema_w)
+        else:
+            _C.call(ops._k("ngan_linear_wgrad_rmsprop", gc), *args)
 
 
 OPTIMIZERS = {"adam": FusedAdam, "rmsprop": FusedRMSprop}
@@ -337,7 +401,79 @@ def _set_share(trainer, b, global_batch):
         trainer._share.fill_(b * trainer.world / gb)
 
 
-class PGGANTrainer:
+def _check_ema_beta(ema_beta):
+    """0 or None: averaging off (-> None); else a decay in (0, 1)"""
+    if ema_beta is None or float(ema_beta) == 0.0:
+        return None
+    if not 0.0 < float(ema_beta) < 1.0:
+        raise ValueError(f"ema_beta must be 0 (off) or lie in (0, 1), got {ema_beta}")
+    return float(ema_beta)
+
+
+class _AveragedGenerator:
+    """The averaged generator of a trainer (`ema_beta`; an addition of this implementation, the reference has none): an exponential
+    moving average of the generator's parameters, e' = e + (1 - beta)(p' - e) once per generator step, kept by the generator's
+    optimiser inside its own launches (flat_g.ema, laid out like flat_g.flat, so it survives growth untouched; a tensor that is not
+    yet trained keeps average = parameter).  Replicas of a data-parallel run hold identical parameters and therefore identical
+    averages: nothing is exchanged.  Buffers that are no parameters (the WGAN generator's BatchNorm statistics) are not averaged."""
+
+    @property
+    def ema_enabled(self):
+        return self.flat_g.ema is not None
+
+    def _need_ema(self):
+        if not self.ema_enabled:
+            raise RuntimeError("this trainer keeps no averaged generator (ema_beta=0)")
+
+    def set_ema_beta(self, beta):
+        """the decay from the next generator step on -- captured graphs replay with it, no re-capture"""
+        self._need_ema()
+        self.opt_g.set_ema_beta(beta)
+
+    @contextlib.contextmanager
+    def averaged_generator(self):
+        """Inside the context `self.G` computes with the averaged weights; on exit the training weights are back bit for bit and
+        the captured graphs are as valid as before.  The contents of flat_g.flat and flat_g.ema are exchanged in place -- parameters
+        are views and graphs hold addresses, so nothing may move -- and the packed conv weights, which are copies of the parameters
+        made at a weight epoch, are rebuilt on the way in AND on the way out.  Not for use inside a training step or a capture."""
+        self._need_ema()
+        assert not getattr(self, "_ema_swapped", False), "averaged_generator() is already active"
+        self._swap_ema(True)
+        try:
+            yield self.G
+        finally:
+            self._swap_ema(False)
+
+    def _swap_ema(self, entering):
+        self.flat_g.swap_ema()
+        self._ema_swapped = entering
+        ops.bump_weight_epoch()       # every packed copy is stale now ...
+        ops.refresh_packed()          # ... and rebuilt from what the parameters hold (one launch)
+
+    def _ema_slices(self):
+        f = self.flat_g
+        for name, p in self.G.named_parameters():
+            o = f.offsets[f.index[id(p)]]
+            yield name, p, f.flat[o:o + p.numel()], f.ema[o:o + p.numel()]
+
+    def ema_state(self):
+        """the averaged weights under the generator's CURRENT state_dict keys (what from_state_dict understands at this stage)"""
+        self._need_ema()
+        assert not getattr(self, "_ema_swapped", False), "inside averaged_generator() the average is in the parameters themselves"
+        return {name: e.detach().clone().view(p.shape) for name, p, _, e in self._ema_slices()}
+
+    def load_ema_state(self, state):
+        """inverse of ema_state(); a tensor `state` does not hold (or holds with another shape) starts from the current weights"""
+        self._need_ema()
+        for name, p, w, e in self._ema_slices():
+            v = state.get(name)
+            if v is not None and tuple(v.shape) == tuple(p.shape):
+                e.copy_(v.reshape(-1))
+            else:
+                e.copy_(w)
+
+
+class PGGANTrainer(_AveragedGenerator):
     """One object per process (= per GPU).  `train_iteration(real)` is train.py:356-385 with sim_loss off.
 
     Data parallel (an initialised process group): every rank trains its share of the global batch; `global_batch` (an argument of
@@ -346,12 +482,15 @@ class PGGANTrainer:
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
-                 rmsprop_alpha=0.99, rmsprop_eps=1e-8):
+                 rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0):
         """optimizer: "adam" -- optim.Adam(params, lr, betas=(beta1, 0.999)), the reference's default -- or "rmsprop" --
         optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps), what the reference's RMSprop switch selects (train.py:220-225);
-        beta1 only matters for Adam"""
+        beta1 only matters for Adam
+        ema_beta: 0 or None -- off (no buffer, no launch: the code path of a build without the feature); 0 < ema_beta < 1 -- keep the
+        averaged generator with this decay (`_AveragedGenerator`)"""
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
+        ema_beta = _check_ema_beta(ema_beta)
         self.G, self.D = generator, discriminator
         self.device = next(generator.parameters()).device
         self.n_critic = n_critic
@@ -361,10 +500,10 @@ class PGGANTrainer:
         opt_cls = OPTIMIZERS[optimizer]
         self.flat_g, self.flat_d = FlatParams(generator, opt_cls.STATE), FlatParams(discriminator, opt_cls.STATE)
         if optimizer == "adam":
-            self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999))
+            self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999), ema_beta=ema_beta)
             self.opt_d = FusedAdam(self.flat_d, learning_rate, (beta1, 0.999))
         else:
-            self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps)
+            self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps, ema_beta=ema_beta)
             self.opt_d = FusedRMSprop(self.flat_d, learning_rate, rmsprop_alpha, rmsprop_eps)
         self.d_loss = D_W_loss(generator, discriminator, drift_epsilon=drift_epsilon, check_nan=False)
         self.gp_loss = D_grad_pen_loss(generator, discriminator, Lambda=grad_pen_lambda)
@@ -638,10 +777,13 @@ class PGGANTrainer:
 
     # ---- HIP-graph capture of a whole iteration ---------------------------------------------------------------
     def _training_state(self):
-        """everything a training iteration changes on the device (parameters, optimiser state and step counts, the device RNG)"""
+        """everything a training iteration changes on the device (parameters, optimiser state and step counts, the averaged
+        generator when there is one, the device RNG)"""
         bufs = []
         for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
             bufs += [flat.flat] + [getattr(flat, buf) for buf in opt.STATE] + [flat.seg_step]
+            if flat.ema is not None:
+                bufs.append(flat.ema)
         return bufs
 
     def _graph_key(self, shape, global_batch=None):
@@ -825,18 +967,20 @@ class _ClipMixin:
 
 
 class ClippedFusedAdam(_ClipMixin, FusedAdam):
-    def _flat_step(self, f, n0, n_chunks):
+    def _flat_step(self, f, n0, n_chunks, ema=False):
+        assert not ema, "the clipped steps are the critic's: no average"
         _C.call("ngan_adam_step_clip", f.flat, f.grad, f.exp_avg, f.exp_avg_sq, f.seg_off, f.seg_len, f.seg_active, f.seg_step,
                 len(f.params), f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel(), float(self.clip))
 
 
 class ClippedFusedRMSprop(_ClipMixin, FusedRMSprop):
-    def _flat_step(self, f, n0, n_chunks):
+    def _flat_step(self, f, n0, n_chunks, ema=False):
+        assert not ema, "the clipped steps are the critic's: no average"
         _C.call("ngan_rmsprop_step_clip", f.flat, f.grad, f.square_avg, f.seg_off, f.seg_len, f.seg_active, f.seg_step, len(f.params),
                 f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel(), float(self.clip))
 
 
-class WGANTrainer:
+class WGANTrainer(_AveragedGenerator):
     """The reference's WGAN loop (train.py:470-506) for Generator_wgan / Discriminator_wgan: n_critic x [D(real), D(G(z).detach()),
     -mean + mean + drift * mean(real^2), backward, optimiser step, clamp every critic parameter to +-clip], then one generator step
     -mean(D(G(z))).  Both nets stay in train mode, so every forward uses batch statistics and updates the BatchNorm running buffers,
@@ -855,9 +999,12 @@ class WGANTrainer:
     eval mode) issue no collective."""
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, drift_epsilon=0.001, n_critic=1, clip=0.01,
-                 optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None, sync_batchnorm=False):
+                 optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None, sync_batchnorm=False,
+                 ema_beta=0.0):
+        """ema_beta: as PGGANTrainer's -- the averaged generator's parameters; its BatchNorm buffers stay the live ones"""
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
+        ema_beta = _check_ema_beta(ema_beta)
         grouped = dist.is_available() and dist.is_initialized()
         if sync_batchnorm and not grouped:
             raise ValueError("sync_batchnorm=True needs an initialised process group (torch.distributed.init_process_group)")
@@ -882,10 +1029,10 @@ class WGANTrainer:
         self.flat_g.set_active(self.flat_g.params)
         self.flat_d.set_active(self.flat_d.params)
         if optimizer == "adam":
-            self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999))
+            self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999), ema_beta=ema_beta)
             self.opt_d = ClippedFusedAdam(self.flat_d, learning_rate, (beta1, 0.999))
         else:
-            self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps)
+            self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps, ema_beta=ema_beta)
             self.opt_d = ClippedFusedRMSprop(self.flat_d, learning_rate, rmsprop_alpha, rmsprop_eps)
         self.opt_d.clip = float(clip)
         if self.sync_batchnorm:
@@ -1006,6 +1153,8 @@ class WGANTrainer:
         bufs = []
         for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
             bufs += [flat.flat] + [getattr(flat, buf) for buf in opt.STATE] + [flat.seg_step]
+            if flat.ema is not None:
+                bufs.append(flat.ema)
         return bufs + self._bn_buffers()
 
     def capture(self, real_example, warmup=1, draws=None):
@@ -1341,6 +1490,10 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
                 if samples_dir is not None:
                     from .utils import plot_gen_samples
                     plot_gen_samples(G, N_images=16, seed=0, filename=os.path.join(samples_dir, "Samples_{}_{:d}.png".format(cfg.ID, epoch)))
+                    if getattr(trainer, "ema_enabled", False):       # the same latents through the averaged generator
+                        with trainer.averaged_generator():
+                            plot_gen_samples(G, N_images=16, seed=0,
+                                             filename=os.path.join(samples_dir, "Samples_ema_{}_{:d}.png".format(cfg.ID, epoch)))
             else:
                 checkpoint.epoch = epoch
             ranks.barrier()
@@ -1455,6 +1608,10 @@ def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final
                     if samples_dir is not None:
                         plot_gen_samples(G, eval_noise=eval_noise,
                                          filename=os.path.join(samples_dir, 'Test_images_{}_{}.png'.format(cfg.ID, epoch)))
+                        if getattr(trainer, "ema_enabled", False):   # the same latents through the averaged generator
+                            with trainer.averaged_generator():
+                                plot_gen_samples(G, eval_noise=eval_noise,
+                                                 filename=os.path.join(samples_dir, 'Samples_ema_{}_{}.png'.format(cfg.ID, epoch)))
                 else:
                     checkpoint.epoch = epoch
                 ranks.barrier()
@@ -1501,6 +1658,7 @@ def build_arg_parser():
     p.add_argument('--images', type=str, default='', help='.pt / .npy file with the training images (N, C, R, R) in [-1, 1]; '
                                                           'synthetic uniform images when omitted')
     p.add_argument('--N_epochs_session', type=int, default=None)
+    p.add_argument('--ema_beta', type=float, default=0.0, help='decay of the averaged generator (e.g. 0.999); 0: off')
     p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
                                                         'launch.py); batch_size stays the global batch')
     return p
@@ -1539,12 +1697,13 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
                          "Generator_net.image_size); choose one")
     if config.wgan:
         kw = dict(learning_rate=config.learning_rate, drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, device_latents=True,
-                  process_group=process_group, sync_batchnorm=bool(distributed))
+                  process_group=process_group, sync_batchnorm=bool(distributed), ema_beta=getattr(config, 'ema_beta', 0.0))
         if config.RMSprop:
             return WGANTrainer(G, D, optimizer="rmsprop", **kw)
         return WGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
     kw = dict(learning_rate=config.learning_rate, grad_pen_lambda=config.grad_pen_lambda, drift_epsilon=config.drift_epsilon,
-              n_critic=config.n_critic, alpha_step=config.alpha_step, device_latents=True, process_group=process_group)
+              n_critic=config.n_critic, alpha_step=config.alpha_step, device_latents=True, process_group=process_group,
+              ema_beta=getattr(config, 'ema_beta', 0.0))
     if config.RMSprop:
         return PGGANTrainer(G, D, optimizer="rmsprop", **kw)
     return PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)

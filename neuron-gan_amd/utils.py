@@ -42,7 +42,9 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # ---------------------------------------------------------------------------------------------------------------------
 # Checkpoints: same dictionary layout as the reference's Checkpointer (utils.py:142-223), so files written
 # by either side load in the other.  One optional extra key, 'optimizer_state', carries the fused Adam's moments and
-# per-tensor step counts (the reference does not save optimiser state at all).
+# per-tensor step counts (the reference does not save optimiser state at all).  A trainer that keeps an averaged generator
+# (train.py, `ema_beta`) adds 'Generator_ema_state': the averaged weights under the keys of 'Generator_state', tensors only.  The
+# reference's loaders read the keys they know and ignore the rest.
 # ---------------------------------------------------------------------------------------------------------------------
 import os  # noqa: E402
 
@@ -82,6 +84,9 @@ def load_checkpoint_dict(filename, device=torch.device('cpu')):
         return torch.load(filename, map_location=device, weights_only=True)
 
 
+EMA_KEY = 'Generator_ema_state'
+
+
 class Checkpointer:
     def __init__(self, Generator_net, Discriminator_net, lr: float, filename: str, N_epochs=100, verbose=True,
                  device=torch.device('cpu'), extra_checkpoint_period=50e3, trainer=None):
@@ -97,7 +102,7 @@ class Checkpointer:
         self.verbose = verbose
         self.device = device
         self.extra_checkpoint_period = extra_checkpoint_period
-        self.trainer = trainer      # optional PGGANTrainer: adds / restores 'optimizer_state'
+        self.trainer = trainer      # optional PGGANTrainer: adds / restores 'optimizer_state' (and 'Generator_ema_state')
 
     def save_state(self, epoch):
         self.epoch = epoch
@@ -114,6 +119,8 @@ class Checkpointer:
                            'Loss_G': self.Loss_G[:epoch], 'Loss_D': self.Loss_D[:epoch]}
         if self.trainer is not None:
             checkpoint_dict['optimizer_state'] = self.trainer.optimizer_state()
+            if getattr(self.trainer, 'ema_enabled', False):
+                checkpoint_dict[EMA_KEY] = cpu(self.trainer.ema_state())
         torch.save(checkpoint_dict, self.filename)
         if epoch % self.extra_checkpoint_period == 0:
             base, ext = os.path.splitext(self.filename)
@@ -162,6 +169,10 @@ class Checkpointer:
                     # the reference never restores an optimiser (utils.py:213-215): start this one fresh, as it would
                     self.trainer.reset_optimizer_state()
                     print('{} holds {} state; the {} optimiser starts fresh'.format(source, saved_kind, self.trainer.optimizer_kind))
+            if getattr(self.trainer, 'ema_enabled', False):
+                self.trainer.load_ema_state(checkpoint_dict.get(EMA_KEY, {}))
+                if EMA_KEY not in checkpoint_dict:
+                    print('{} holds no {}; the averaged generator starts from the loaded weights'.format(source, EMA_KEY))
         if self.verbose:
             print(('Loaded training state from {}' if filename is None else 'Loaded weights from {}').format(source))
 
