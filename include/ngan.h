@@ -217,7 +217,8 @@ int ngan_fade_bwd(const float* g, const float* alpha, float* ga, float* gb, long
 int ngan_xhat(const float* real, const float* fake, const float* eps, float* out, int B, long n, void* stream);
 
 /* ---- gradient penalty pieces: loss_functions.py:176 (ATen linalg_vector_norm) ----------------------------------
- * norms[b] = ||g[b,:]||_2 (two fixed-order stages; rows 16-byte aligned, n a multiple of 4);   scale_rows: out[b,:] = coef[b] * g[b,:] */
+ * norms[b] = ||g[b,:]||_2 (two fixed-order stages; g 16-byte aligned and n a multiple of 4 so that every row is, or B = 1 with any n:
+ * NGAN_ERR_SHAPE otherwise);   scale_rows: out[b,:] = coef[b] * g[b,:] */
 int ngan_sample_l2norm(const float* g, float* norms, float* workspace /* 64*B floats */, int B, long n, void* stream);
 int ngan_scale_rows(const float* g, const float* coef, float* out, int B, long n, void* stream);
 /* the penalty's scalar head and its adjoint: out1 = lambda * mean((norms - 1)^2);  coef[b] = g_out * 2 lambda (norms[b] - 1) / (B norms[b])
@@ -240,11 +241,18 @@ int ngan_latent_normalize(float* z, int rows, int dim, float clamp, void* stream
 /* ---- generator stem: Linear_normalized -> Unflatten -> LeakyReLU -> PixelNorm, models.py:299-311 (ATen mm) --------
  * fwd:   y[b][p][c] = PN(LReLU(scale * sum_k z[b][k] * Wt[c*S + p][k])),  y (B,S,C), rnorm (B,S); W is (C*S, K)
  * wgrad: gW[c*S+p][k] = scale * sum_b gc[b][p][c] * z[b][k]
- * dgrad: gz[b][k] = scale * sum_{p,c} gc[b][p][c] * W[c*S+p][k] */
+ * dgrad: gz[b][k] = scale * sum_{p,c} gc[b][p][c] * W[c*S+p][k]
+ * Shapes (NGAN_ERR_SHAPE otherwise), any B > 0:
+ *   fwd:   K a multiple of 16, and 64 * (K + C + 9) bytes of LDS (16 samples x (K + 4) latents and (C + 4) channels, 16 norms) at most
+ *          160 KiB, i.e. K + C <= 2551; above 64 KiB (K + C > 1015) the launch raises the kernel's dynamic-LDS limit first.
+ *   wgrad: K a multiple of 4, at most 1024.  K a multiple of 16 and at most 512 takes the MFMA form (one pass over the samples, the
+ *          only form with accumulate and with the optimiser epilogues); every other K the row-streaming form (16-sample register
+ *          chunks, fp32 read-modify-write across the chunks).
+ *   dgrad: any K. */
 int ngan_linear_lrelu_pn_fwd(const float* z, const float* Wt, float* y, float* rnorm, int B, int K, int S, int C,
                              float scale, float slope, float eps, void* stream);
 int ngan_linear_wgrad(const float* z, const float* gc, float* gW, int B, int K, int S, int C, float scale, void* stream);
-/* accumulate != 0: gW += ... (K <= 512, a multiple of 16): adds straight into the parameter's gradient buffer */
+/* accumulate != 0: gW += ... (K <= 512, a multiple of 16; NGAN_ERR_SHAPE for any other K): adds straight into the parameter's gradient buffer */
 int ngan_linear_wgrad_acc(const float* z, const float* gc, float* gW, int B, int K, int S, int C, float scale, int accumulate,
                           void* stream);
 /* the same contraction with Adam applied in its epilogue instead of a stored gradient (K <= 512, a multiple of 16; any B -- the

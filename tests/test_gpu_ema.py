@@ -127,7 +127,7 @@ def test_flat_steps_with_average(ngan, kind):
 # ---- 1-3: the four stem forms, both MFMA instantiations ---------------------------------------------------------------------------
 @pytest.mark.parametrize("act", ["f32", "bf16"])
 @pytest.mark.parametrize("rule", ["adam", "rmsprop"])
-@pytest.mark.parametrize("B,K,S2,C", [(6, 32, 9, 20), (5, 512, 4, 24)])      # K <= 128 and K > 128: NT = 8 and NT = 32; rows % 64 != 0
+@pytest.mark.parametrize("B,K,S2,C", [(6, 32, 9, 20), (5, 512, 4, 24), (5, 144, 9, 20)])      # K <= 128 and K > 128: NT = 8 and NT = 32; rows % 64 != 0; 144: nt = 9 < NT = 32
 def test_stem_epilogues_with_average(ngan, rule, act, B, K, S2, C):
     Cc = ngan._C
     torch.manual_seed(31)
