@@ -564,6 +564,40 @@ int ngan_bn_act_bwd_merged(const float* y, const float* g, const float* scale, c
                            const float* gamma, int act, float slope, long npix, int C, const double* recs, int world, int rank,
                            const double* n_total, float* gy, float* dgamma, float* dbeta, float* work, void* stream);
 
+/* ---- sample quality: sliced Wasserstein distance on Laplacian-pyramid patches (Karras et al. 2018, section 5; an addition of this
+ * implementation, off by default; neuron-gan_amd/metrics.py drives it) -----------------------------------------------------------
+ * Images are channels-last (B, H, W, C) fp32 with C = 1 or 3 (NGAN_ERR_SHAPE otherwise).  The Gaussian is separable, [1 4 6 4 1] / 16
+ * per axis, with the MIRROR boundary `d c b | a b c d | c b a` (the edge sample is not repeated: scipy's mode='mirror', torch's
+ * 'reflect').  fp32 arithmetic with explicit fused multiply-adds in a fixed order; every sum over many values is fp64 in two fixed
+ * stages through a caller workspace (no floating-point atomics): all results are bit-reproducible.
+ * pyr_down:    out (B, H/2, W/2, C) = the filtered input at its even rows and columns.  H, W even, at least 4.
+ * laplacian:   lap = fine - up(coarse); fine, lap (B, H, W, C), coarse (B, H/2, W/2, C); up = zeros inserted at the odd positions,
+ *              filtered with 4 x the same Gaussian, mirror boundary on the fine grid.  H, W even, at least 4.
+ * descriptors: n patches (image, top row, left column) as int32 triples, given twice: `pos_host` in host memory, checked here
+ *              (0 <= image < B, 0 <= row <= H - 7, 0 <= column <= W - 7, NGAN_ERR_ARG otherwise), and `pos`, the same triples in
+ *              device memory, which the kernel reads.  Row row_offset + i of desc (any number of rows x 49 C) receives the 7 x 7 x C
+ *              neighbourhood of patch i at column c * 49 + dy * 7 + dx.  sums (2 C doubles) = [sum d per channel, sum d^2 per
+ *              channel] over the n * 49 values of each channel; accumulate != 0 adds to what sums holds, so one descriptor matrix
+ *              and one pair of sums grow minibatch by minibatch.  workspace: the bytes the _workspace_bytes function names.
+ * project:     proj[j][i] = sum_k ((desc[i][k] - mean_c(k)) / std_c(k)) * dirs[k][j], i < n; +inf for n <= i < n_pad.  desc (n, 49 C),
+ *              dirs (49 C, n_dirs), proj (n_dirs, n_pad): one contiguous column per direction.  mean = S1 / (49 n) and the population
+ *              standard deviation come from sums in fp64; (desc - mean) / std is formed in fp64 and rounded once, the sum runs over
+ *              k = 0, 1, ... with one fmaf each.  n_pad: a power of two >= n (NGAN_ERR_SHAPE otherwise).
+ * sort_columns: every one of the n_dirs columns of length n_pad (a power of two) ascending, in place: a bitonic network; the stages
+ *              whose stride fits a block of sort_block_elements values run in LDS, larger strides as passes over global memory.
+ * l1:          out[0] (one double) = (1 / (n n_dirs)) sum_j sum_{i < n} |a[j][i] - b[j][i]|; a, b (n_dirs, n_pad). */
+int ngan_swd_pyr_down(const float* in, float* out, int B, int H, int W, int C, void* stream);
+int ngan_swd_laplacian(const float* fine, const float* coarse, float* lap, int B, int H, int W, int C, void* stream);
+size_t ngan_swd_descriptors_workspace_bytes(int n, int C);
+int ngan_swd_descriptors(const float* images, const int* pos_host, const int* pos, float* desc, double* sums, void* workspace, int n,
+                         long row_offset, int accumulate, int B, int H, int W, int C, void* stream);
+int ngan_swd_project(const float* desc, const double* sums, const float* dirs, float* proj, int n, int n_pad, int n_dirs, int C,
+                     void* stream);
+int ngan_swd_sort_block_elements(void);
+int ngan_swd_sort_columns(float* cols, int n_dirs, int n_pad, void* stream);
+size_t ngan_swd_l1_workspace_bytes(int n, int n_dirs);
+int ngan_swd_l1(const float* a, const float* b, double* out, void* workspace, int n, int n_pad, int n_dirs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

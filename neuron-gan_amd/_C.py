@@ -98,6 +98,13 @@ SIGNATURES = {
     "ngan_bn_merge_fold": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P],
     "ngan_bn_act_bwd_partial": [_P, _P, _P, _P, _P, _P, _I, _F, _L, _I, _P, _P, _P],
     "ngan_bn_act_bwd_merged": [_P, _P, _P, _P, _P, _P, _P, _I, _F, _L, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    # sliced Wasserstein distance (include/ngan.h, last section; metrics.py)
+    "ngan_swd_pyr_down": [_P, _P, _I, _I, _I, _I, _P],
+    "ngan_swd_laplacian": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "ngan_swd_descriptors": [_P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P],
+    "ngan_swd_project": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ngan_swd_sort_columns": [_P, _I, _I, _P],
+    "ngan_swd_l1": [_P, _P, _P, _P, _I, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -131,6 +138,9 @@ NON_STATUS = {
     "ngan_s2_wgrad_workspace_floats": ([_I, _I, _I, _I, _I], _L),
     "ngan_chan_reduce_workspace_floats": ([_L, _I], _L),
     "ngan_bn_act_bwd_workspace_floats": ([_L, _I], _L),
+    "ngan_swd_descriptors_workspace_bytes": ([_I, _I], _Z),
+    "ngan_swd_l1_workspace_bytes": ([_I, _I], _Z),
+    "ngan_swd_sort_block_elements": ([], _I),
 }
 
 _lib = None

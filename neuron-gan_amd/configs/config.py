@@ -29,6 +29,7 @@ _DEFAULTS = dict(
     ID=uuid.uuid4().hex[:4], RMSprop=False, learning_rate=0.0001, batch_size=8, N_epochs=150000, N_epochs_session=None,
     beta1=0.5, sim_loss_lambda=0.0, sim_loss_lambda_decay_rate=0.0, drift_epsilon=0.001, resume=False, N_workers=2,
     seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
+    swd_period=0, swd_images=8192, swd_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -88,6 +89,11 @@ def validate_configs(create_dirs=False):
     # the averaged generator (an addition of this implementation): 0 is off, otherwise the decay
     if not (isinstance(g['ema_beta'], (int, float)) and 0 <= g['ema_beta'] < 1):
         raise ValueError(f"ema_beta={g['ema_beta']!r} must lie in [0, 1)")
+    # the sliced Wasserstein distance at checkpoints (an addition of this implementation): swd_period 0 is off, otherwise every
+    # checkpoint whose epoch is a multiple of it is scored on swd_images images per side
+    for name, lowest in (('swd_period', 0), ('swd_images', 1), ('swd_seed', 0)):
+        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
+            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
     if g['pggan']:
         err_msg = 'The number of layers in the generator and discriminator must match.'
         assert len(g['N_gen_features']) == len(g['N_dis_features']), err_msg

@@ -4,7 +4,14 @@
 
 Same flags, meaning and defaults: -weights is a file in config.weights_dir, -output a file in config.images_dir (an absolute path is
 taken as it is).  Added: --ema samples from the averaged generator the checkpoint carries ('Generator_ema_state', written by a run
-with --ema_beta; KeyError if it holds none).  The generator runs on the HIP kernels, so this needs a GPU, like train.py."""
+with --ema_beta; KeyError if it holds none).  --swd [N] prints, instead of writing a grid, the sliced Wasserstein distance (metrics.py)
+of the checkpoint's generator per pyramid level against N images (default 8192) of the data set that --dataset_dir (a folder, as
+train.py reads it; default config.dataset_dir) or --images (a .pt / .npy file of (N, C, R, R) images in [-1, 1]) names; with --ema
+the table of the averaged generator follows.
+
+    python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --swd 8192 --dataset_dir data/science_2022 [--ema]
+
+The generator runs on the HIP kernels, so this needs a GPU, like train.py."""
 import argparse
 import os
 import sys
@@ -17,7 +24,32 @@ def build_arg_parser():
     p.add_argument('-weights', type=str, default='gen_dis_default.pth', help='Filename of the weights stored in ./weights')
     # addition of this implementation
     p.add_argument('--ema', action='store_true', default=False, help='sample from the averaged generator of the checkpoint')
+    p.add_argument('--swd', type=int, nargs='?', const=8192, default=None, metavar='N',
+                   help='print the sliced Wasserstein distance per pyramid level against N images of the data set (default 8192)')
+    p.add_argument('--swd_seed', type=int, default=0, help='seed of the SWD patch corners, directions, latents and augmentations')
+    p.add_argument('--dataset_dir', type=str, default='', help='folder of training images (default: config.dataset_dir)')
+    p.add_argument('--images', type=str, default='', help='.pt / .npy file with the images (N, C, R, R) in [-1, 1]')
     return p
+
+
+def load_dataset(options, config, device):
+    """the data set `--swd` scores against, read the way train.py reads it"""
+    import numpy as np
+    import torch
+    from .data import NeuronDataset
+    from .train import TensorImageDataset
+    if options.images:
+        data = torch.load(options.images) if options.images.endswith('.pt') else torch.from_numpy(np.load(options.images))
+        data = data.float()
+        if data.dim() == 4 and data.shape[1] == 1:
+            return NeuronDataset((data + 1.0) * 0.5, augmentations=True, im_translation=float(config.translation), device=device,
+                                 seed=options.swd_seed)
+        return TensorImageDataset(data.to(device))
+    directory = os.path.abspath(options.dataset_dir or config.dataset_dir)
+    if not os.path.exists(directory):
+        raise ValueError('The dataset path {} does not exist.'.format(directory))
+    return NeuronDataset.from_directory(directory, augmentations=True, im_translation=float(config.translation), device=device,
+                                        seed=options.swd_seed, fill_seed=options.swd_seed)
 
 
 def main(argv=None):
@@ -33,6 +65,17 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise RuntimeError("the HIP path needs a GPU (there is no CPU fallback)")
     device = torch.device('cuda')
+    if options.swd is not None:
+        from .metrics import evaluate_swd, format_table
+        if options.swd < 1:
+            raise ValueError('--swd {}: at least one image'.format(options.swd))
+        dataset = load_dataset(options, config, device)
+        for use_ema in ((False, True) if options.ema else (False,)):
+            G = Generator_PG.from_state_dict(weights, device=device, use_ema=use_ema, verbose=False).to(device)
+            res = evaluate_swd(G, dataset, n_images=options.swd, batch_size=min(options.swd, 32), seed=options.swd_seed)
+            print(format_table(res, 'SWD x 1e3, {} generator of {} against {} images'.format(
+                'averaged' if use_ema else 'training', options.weights, options.swd)))
+        return 0
     G = Generator_PG.from_state_dict(weights, device=device, use_ema=options.ema).to(device)
     plot_gen_samples(G, N_images=options.n, filename=output)
     return 0

@@ -1,0 +1,313 @@
+"""Sample quality: the sliced Wasserstein distance (SWD) on Laplacian-pyramid patches (Karras et al. 2018, section 5) -- an addition of
+this implementation, the reference has no quality metric.  Every stage is a kernel of csrc/swd.hip (include/ngan.h, last section):
+
+    pyr_down / laplacian / laplacian_pyramid   the pyramid, channels-last fp32
+    patch_descriptors                          7 x 7 x C neighbourhoods -> rows of a descriptor matrix, fp64 channel sums alongside
+    project                                    per-channel normalisation and the random projections, direction-major, +inf padded
+    sort_columns                               bitonic sort of every projected column
+    sliced_wasserstein                         mean |sorted A - sorted B| over all directions and descriptors
+
+`SWD` feeds minibatches of real and generated images and reports one value (x 1e3) per pyramid level R, R/2, ..., 16;
+`evaluate_swd` drives it from a generator and a dataset.  All randomness (patch corners, directions, augmentation draws) comes from
+private host generators seeded by `seed`: torch's global generator is never consumed, so a run trains the same with the metric on."""
+import torch
+
+from . import _C
+
+NHOOD = 7                     # the kernels' patch size
+MIN_LEVEL = 16                # the coarsest pyramid level of the published metric
+
+
+def _images(x):
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.dtype == torch.float32):
+        raise TypeError("expected a 4-d fp32 tensor of channels-last images (B, H, W, C)")
+    if x.shape[3] not in (1, 3):
+        raise ValueError(f"C={x.shape[3]}: 1 or 3 colour channels")
+    return x.contiguous()
+
+
+def channels_last(images):
+    """(B, C, R, R) or (B, R, R, C) images -> contiguous fp32 (B, R, R, C); one colour channel needs no copy"""
+    if images.dim() != 4:
+        raise ValueError(f"images must have 4 dimensions, got {tuple(images.shape)}")
+    images = images.detach().float()
+    if images.shape[3] in (1, 3) and images.shape[1] == images.shape[2]:
+        return images.contiguous()
+    if images.shape[1] not in (1, 3) or images.shape[2] != images.shape[3]:
+        raise ValueError(f"images must be (B, C, R, R) or (B, R, R, C) with C in (1, 3), got {tuple(images.shape)}")
+    if images.shape[1] == 1:
+        return images.contiguous().view(images.shape[0], images.shape[2], images.shape[3], 1)
+    return images.permute(0, 2, 3, 1).contiguous()
+
+
+def pyr_down(x):
+    """Gaussian [1 4 6 4 1] / 16 per axis, mirror boundary, sampled at the even rows and columns: (B, H, W, C) -> (B, H/2, W/2, C)"""
+    x = _images(x)
+    b, h, w, c = x.shape
+    out = torch.empty(b, h // 2, w // 2, c, device=x.device, dtype=torch.float32)
+    _C.call("ngan_swd_pyr_down", x, out, b, h, w, c)
+    return out
+
+
+def laplacian(fine, coarse):
+    """fine - up(coarse), up = zero-insert x2 filtered with 4 x the Gaussian (mirror boundary on the fine grid)"""
+    fine, coarse = _images(fine), _images(coarse)
+    b, h, w, c = fine.shape
+    if tuple(coarse.shape) != (b, h // 2, w // 2, c):
+        raise ValueError(f"coarse must be {(b, h // 2, w // 2, c)}, got {tuple(coarse.shape)}")
+    out = torch.empty_like(fine)
+    _C.call("ngan_swd_laplacian", fine, coarse, out, b, h, w, c)
+    return out
+
+
+def laplacian_pyramid(images, num_levels):
+    """[lap_0, ..., lap_{L-2}, gauss_{L-1}] of channels-last images: level l is H / 2^l pixels wide; the last keeps the low-pass"""
+    if num_levels < 1:
+        raise ValueError("num_levels must be at least 1")
+    cur = _images(images)
+    out = []
+    for _ in range(num_levels - 1):
+        nxt = pyr_down(cur)
+        out.append(laplacian(cur, nxt))
+        cur = nxt
+    out.append(cur)
+    return out
+
+
+def _positions(positions):
+    pos = torch.as_tensor(positions).to(dtype=torch.int32, device="cpu").contiguous()
+    if pos.dim() != 2 or pos.shape[1] != 3 or pos.shape[0] == 0:
+        raise ValueError(f"positions must be (n, 3) triples (image, top row, left column), got {tuple(pos.shape)}")
+    return pos
+
+
+def patch_descriptors(images, positions, out=None, sums=None, row_offset=0, accumulate=False):
+    """Rows row_offset .. row_offset + n of `out` (any rows x 49 C; default a new (n, 49 C) matrix) = the 7 x 7 x C neighbourhoods
+    at `positions` ((n, 3) int triples: image, top row, left column; validated by the entry point on the host), channel-major;
+    `sums` (2 C doubles) = per-channel sum and sum of squares, added to when accumulate.  Returns (out, sums)."""
+    x = _images(images)
+    b, h, w, c = x.shape
+    pos = _positions(positions)
+    n = pos.shape[0]
+    if out is None:
+        out = torch.empty(row_offset + n, 49 * c, device=x.device, dtype=torch.float32)
+    if out.dim() != 2 or out.shape[1] != 49 * c or out.shape[0] < row_offset + n or out.dtype != torch.float32:
+        raise ValueError(f"out must be fp32 (>= {row_offset + n}, {49 * c}), got {tuple(out.shape)}")
+    if sums is None:
+        if accumulate:
+            raise ValueError("accumulate needs the sums to add to")
+        sums = torch.empty(2 * c, device=x.device, dtype=torch.float64)
+    ws = torch.empty(max(1, _C.lib().ngan_swd_descriptors_workspace_bytes(n, c) // 8), device=x.device, dtype=torch.float64)
+    _C.call("ngan_swd_descriptors", x, pos.data_ptr(), pos.to(x.device), out, sums, ws, n, int(row_offset), int(bool(accumulate)),
+            b, h, w, c)
+    return out, sums
+
+
+def descriptor_sums(desc):
+    """what patch_descriptors returns as `sums`, for a descriptor matrix that came from elsewhere"""
+    d = desc.double().view(desc.shape[0], -1, 49)
+    return torch.cat([d.sum((0, 2)), (d * d).sum((0, 2))])
+
+
+def next_pow2(n):
+    p = 1
+    while p < n:
+        p *= 2
+    return p
+
+
+def project(desc, sums, dirs, n_pad=None):
+    """(n_dirs, n_pad) projections of the normalised descriptors on the columns of dirs (49 C, n_dirs); columns n .. n_pad are +inf"""
+    n, k = desc.shape
+    c = k // 49
+    if k != 49 * c or tuple(dirs.shape[:1]) != (k,) or dirs.dim() != 2:
+        raise ValueError(f"desc (n, 49 C) and dirs (49 C, n_dirs) expected, got {tuple(desc.shape)} and {tuple(dirs.shape)}")
+    n_pad = next_pow2(n) if n_pad is None else int(n_pad)
+    proj = torch.empty(dirs.shape[1], n_pad, device=desc.device, dtype=torch.float32)
+    _C.call("ngan_swd_project", desc, sums, dirs.contiguous(), proj, n, n_pad, dirs.shape[1], c)
+    return proj
+
+
+def sort_columns(cols):
+    """ascending, in place, every row of the direction-major (n_dirs, n_pad) matrix; n_pad a power of two"""
+    _C.call("ngan_swd_sort_columns", cols, cols.shape[0], cols.shape[1])
+    return cols
+
+
+def sort_block_elements():
+    return int(_C.lib().ngan_swd_sort_block_elements())
+
+
+def sorted_l1(a, b, n):
+    """one fp64 device scalar: mean |a - b| over the first n entries of every sorted column"""
+    out = torch.empty(1, device=a.device, dtype=torch.float64)
+    ws = torch.empty(max(1, _C.lib().ngan_swd_l1_workspace_bytes(n, a.shape[0]) // 8), device=a.device, dtype=torch.float64)
+    _C.call("ngan_swd_l1", a, b, out, ws, n, a.shape[1], a.shape[0])
+    return out
+
+
+def sliced_wasserstein(descA, descB, dirs, sumsA=None, sumsB=None):
+    """fp64 device scalar: the sliced Wasserstein distance of two descriptor sets of equal size, each normalised by its own per-channel
+    mean and population standard deviation; dirs (49 C, n_dirs) holds the unit directions of all repeats side by side (the mean over
+    repeats of the per-repeat mean is the mean over all columns)"""
+    if descA.shape != descB.shape:
+        raise ValueError(f"the two sets need the same number of descriptors, got {tuple(descA.shape)} and {tuple(descB.shape)}")
+    n = descA.shape[0]
+    sumsA = descriptor_sums(descA) if sumsA is None else sumsA
+    sumsB = descriptor_sums(descB) if sumsB is None else sumsB
+    pa = sort_columns(project(descA, sumsA, dirs))
+    pb = sort_columns(project(descB, sumsB, dirs))
+    return sorted_l1(pa, pb, n)
+
+
+def draw_directions(n_features, dir_repeats, dirs_per_repeat, generator):
+    """per repeat randn(n_features, dirs_per_repeat) with unit columns, fp32; the repeats side by side"""
+    reps = []
+    for _ in range(dir_repeats):
+        d = torch.randn(n_features, dirs_per_repeat, generator=generator, dtype=torch.float32)
+        reps.append(d / d.square().sum(0, keepdim=True).sqrt())
+    return torch.cat(reps, 1)
+
+
+class SWD:
+    """Accumulates the descriptors of real and generated minibatches and reports the distance per pyramid level.
+
+        m = SWD(image_size=64); m.feed('real', x); m.feed('fake', G(z)); m.result()
+
+    Levels are image_size, image_size / 2, ..., 16 (none below 16 x 16: `result()` then says so).  Per image and level
+    nhoods_per_image patches with top-left corners uniform in [0, H - 7], drawn independently for the two sets unless feed() is
+    given `positions` (one (n, 3) int tensor per level); dir_repeats x dirs_per_repeat unit directions per level, drawn at
+    construction.  n_images: how many images each set will hold, if known -- the descriptor matrices are then allocated once."""
+
+    def __init__(self, image_size, n_colors=1, nhood_size=NHOOD, nhoods_per_image=128, dir_repeats=4, dirs_per_repeat=128, seed=0,
+                 device="cuda", n_images=None):
+        if nhood_size != NHOOD:
+            raise ValueError(f"nhood_size={nhood_size}: the kernels gather {NHOOD} x {NHOOD} patches")
+        if n_colors not in (1, 3):
+            raise ValueError(f"n_colors={n_colors}: 1 or 3")
+        if image_size < 1 or image_size & (image_size - 1):
+            raise ValueError(f"image_size={image_size} must be a power of two")
+        self.image_size, self.n_colors, self.nhoods_per_image = int(image_size), int(n_colors), int(nhoods_per_image)
+        self.device = torch.device(device)
+        self.levels = []
+        r = self.image_size
+        while r >= MIN_LEVEL:
+            self.levels.append(r)
+            r //= 2
+        self.gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        self.dirs = [draw_directions(49 * self.n_colors, dir_repeats, dirs_per_repeat, self.gen) for _ in self.levels]
+        self._capacity = None if n_images is None else int(n_images) * self.nhoods_per_image
+        self.desc = {w: [None] * len(self.levels) for w in ("real", "fake")}
+        self.sums = {w: [None] * len(self.levels) for w in ("real", "fake")}
+        self.count = {w: [0] * len(self.levels) for w in ("real", "fake")}
+
+    def draw_positions(self, batch, size):
+        yx = torch.randint(0, size - NHOOD + 1, (batch, self.nhoods_per_image, 2), generator=self.gen, dtype=torch.int32)
+        idx = torch.arange(batch, dtype=torch.int32).view(batch, 1, 1).expand(batch, self.nhoods_per_image, 1)
+        return torch.cat([idx, yx], 2).reshape(-1, 3)
+
+    def _room(self, which, level, n):
+        k = 49 * self.n_colors
+        have, used = self.desc[which][level], self.count[which][level]
+        if have is None or have.shape[0] < used + n:
+            rows = max(used + n, self._capacity or 0, 2 * (0 if have is None else have.shape[0]))
+            grown = torch.empty(rows, k, device=self.device, dtype=torch.float32)
+            if used:
+                grown[:used].copy_(have[:used])
+            self.desc[which][level] = grown
+        if self.sums[which][level] is None:
+            self.sums[which][level] = torch.zeros(2 * self.n_colors, device=self.device, dtype=torch.float64)
+        return self.desc[which][level]
+
+    def feed(self, which, images, positions=None):
+        if which not in self.desc:
+            raise ValueError(f"which={which!r}: 'real' or 'fake'")
+        x = channels_last(images.to(self.device))
+        if tuple(x.shape[1:]) != (self.image_size, self.image_size, self.n_colors):
+            raise ValueError(f"images must be {self.image_size} pixels wide with {self.n_colors} colours, got {tuple(images.shape)}")
+        if not self.levels:
+            return
+        if positions is not None and len(positions) != len(self.levels):
+            raise ValueError(f"positions: one (n, 3) tensor per level, {len(self.levels)} levels")
+        for l, level in enumerate(laplacian_pyramid(x, len(self.levels))):
+            pos = self.draw_positions(x.shape[0], self.levels[l]) if positions is None else _positions(positions[l])
+            out = self._room(which, l, pos.shape[0])
+            used = self.count[which][l]
+            patch_descriptors(level, pos, out=out, sums=self.sums[which][l], row_offset=used, accumulate=used > 0)
+            self.count[which][l] = used + pos.shape[0]
+
+    def result(self, dirs=None):
+        """{'levels': [R, R/2, ..., 16], 'swd': [per level, x 1e3], 'mean': their mean}; no level (a stage below 16 x 16): empty lists,
+        mean None and a 'note'.  dirs: optional (49 C, n_dirs) directions per level instead of the drawn ones."""
+        if not self.levels:
+            return {"levels": [], "swd": [], "mean": None,
+                    "note": f"{self.image_size} x {self.image_size} images are below {MIN_LEVEL} x {MIN_LEVEL}: no pyramid level to score"}
+        vals = []
+        for l, size in enumerate(self.levels):
+            n = self.count["real"][l]
+            if n == 0 or n != self.count["fake"][l]:
+                raise ValueError(f"level {size}: {n} real and {self.count['fake'][l]} generated descriptors; feed both sets equally")
+            for which in ("real", "fake"):
+                s = self.sums[which][l].tolist()
+                c = self.n_colors
+                for ch in range(c):
+                    mean = s[ch] / (49.0 * n)
+                    if not s[c + ch] / (49.0 * n) - mean * mean > 0.0:
+                        raise ValueError(f"level {size}: channel {ch} of the {which} set has zero variance")
+            d = (self.dirs[l] if dirs is None else dirs[l]).to(self.device, torch.float32)
+            vals.append(sliced_wasserstein(self.desc["real"][l][:n], self.desc["fake"][l][:n], d, self.sums["real"][l],
+                                           self.sums["fake"][l]))
+        swd = [v * 1e3 for v in torch.cat(vals).tolist()]
+        return {"levels": list(self.levels), "swd": swd, "mean": sum(swd) / len(swd)}
+
+
+def evaluate_swd(generator, dataset, n_images=8192, batch_size=64, seed=0, nhoods_per_image=128, dir_repeats=4, dirs_per_repeat=128):
+    """SWD of `generator` against `dataset` at the generator's current resolution: n_images reals through the dataset's own
+    augmentation chain (its indices cycled, its random draws taken from a private generator so that the training stream is left
+    where it was), n_images fakes under no_grad from latents of the sampler's distribution (utils.sample_latent_vec, 'randn': normal
+    draws clamped to [-5, 5], projected on the unit sphere) drawn from a private generator -- the sampler's own seeded form calls
+    torch.manual_seed, which reseeds the device generator that a trainer's device latents come from; one minibatch of images per
+    side alive at a time."""
+    device = next(generator.parameters()).device
+    size = int(generator.image_size)
+    metric = SWD(size, n_colors=int(getattr(generator, "N_colors", 1)), nhoods_per_image=nhoods_per_image, dir_repeats=dir_repeats,
+                 dirs_per_repeat=dirs_per_repeat, seed=seed, device=device, n_images=n_images)
+    if not metric.levels:
+        return metric.result()
+    aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
+    lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
+    old_size = dataset.image_size
+    own_gen = getattr(dataset, "gen", None)
+    dataset.set_image_size(size)
+    if own_gen is not None:
+        dataset.gen = aug
+    try:
+        n_data = len(dataset)
+        for i in range(0, n_images, batch_size):
+            b = min(batch_size, n_images - i)
+            idx = [(i + j) % n_data for j in range(b)]
+            if hasattr(dataset, "batch"):
+                reals = dataset.batch(idx)
+            else:
+                reals = torch.stack([dataset[j] for j in idx]).to(device)
+            metric.feed("real", reals)
+            del reals
+            z = torch.randn(b, generator.latent_dim, generator=lat).clamp(-5, 5)
+            z = (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
+            with torch.no_grad():
+                fakes = generator(z).detach()
+            metric.feed("fake", fakes)
+            del fakes
+    finally:
+        if own_gen is not None:
+            dataset.gen = own_gen
+        dataset.set_image_size(old_size)
+    return metric.result()
+
+
+def format_table(result, title="SWD x 1e3"):
+    if not result["levels"]:
+        return f"{title}: {result['note']}"
+    head = " ".join(f"{r:>9d}" for r in result["levels"]) + "      mean"
+    row = " ".join(f"{v:9.3f}" for v in result["swd"]) + f" {result['mean']:9.3f}"
+    return f"{title}\n{head}\n{row}"

@@ -1359,6 +1359,31 @@ def _clone_draws(fresh):
     return {name: ([x.clone() for x in v] if isinstance(v, (list, tuple)) else v.clone()) for name, v in fresh.items()}
 
 
+def score_swd(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
+    """One SWD evaluation of the training generator and, when the trainer averages, of the averaged one (metrics.evaluate_swd with
+    cfg.swd_images images per side in minibatches of cfg.batch_size, seed cfg.swd_seed): logged in one line and appended to
+    checkpoint.SWD as {epoch, image_size, levels, swd, swd_ema}.  Eager, outside any captured graph, no collective; it draws from
+    private generators only, so the run trains on as if it had not happened."""
+    from .metrics import evaluate_swd
+    G = trainer.G
+    kw = dict(n_images=int(getattr(cfg, 'swd_images', 8192)), batch_size=int(cfg.batch_size), seed=int(getattr(cfg, 'swd_seed', 0)))
+    res = evaluate_swd(G, dataset, **kw)
+    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "levels": list(res["levels"]), "swd": list(res["swd"]),
+             "swd_ema": None}
+    if getattr(trainer, "ema_enabled", False):
+        with trainer.averaged_generator():
+            entry["swd_ema"] = list(evaluate_swd(G, dataset, **kw)["swd"])
+    fmt = lambda v: "[" + ", ".join("{:.3f}".format(x) for x in v) + "]"   # noqa: E731
+    if not entry["levels"]:
+        log("Epoch:{}, SWD: {}".format(epoch, res["note"]))
+    else:
+        log("Epoch:{}, SWD x1e3 at {}: {}{}".format(epoch, entry["levels"], fmt(entry["swd"]),
+                                                   "" if entry["swd_ema"] is None else ", averaged generator: " + fmt(entry["swd_ema"])))
+    if checkpoint is not None:
+        checkpoint.SWD.append(entry)
+    return entry
+
+
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
                 samples_dir=None, on_epoch=None, process_group=None, draws=None):
     """The reference's epoch loop (train.py:298-451) over a PGGANTrainer.
@@ -1374,6 +1399,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     draws the same permutation and trains its `shard_bounds` slice of every global batch, passing the global size to the trainer;
     the monitor sums are all-reduced once per epoch, so the series, the adaptive critic schedule and the NaN check are the same on
     every rank; rank 0 alone logs, saves and plots.  With one rank nothing of this is active.
+    cfg.swd_period > 0: rank 0 scores every checkpoint whose epoch is a multiple of it (`score_swd`) before it is written; the other
+    ranks wait at the checkpoint's barrier.
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
     (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
@@ -1382,6 +1409,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     sim_lambda = float(getattr(cfg, 'sim_loss_lambda', 0.0))          # train.py:300
     sim_decay = float(getattr(cfg, 'sim_loss_lambda_decay_rate', 0.0))
     adapt_critic = bool(getattr(cfg, 'adapt_critic', False))
+    swd_period = int(getattr(cfg, 'swd_period', 0) or 0)
     G, D = trainer.G, trainer.D
     dev = trainer.device
     epoch_final = epoch_final if epoch_final is not None else cfg.N_epochs + 1
@@ -1486,6 +1514,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
             consume(slot)
             checkpoint.lr = trainer.opt_g.param_groups[0]["lr"]
             if ranks.rank == 0:                                        # replicas are identical: rank 0's state is everyone's
+                if swd_period > 0 and epoch % swd_period == 0:
+                    score_swd(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 checkpoint.save_state(epoch)
                 if samples_dir is not None:
                     from .utils import plot_gen_samples
@@ -1659,6 +1689,10 @@ def build_arg_parser():
                                                           'synthetic uniform images when omitted')
     p.add_argument('--N_epochs_session', type=int, default=None)
     p.add_argument('--ema_beta', type=float, default=0.0, help='decay of the averaged generator (e.g. 0.999); 0: off')
+    p.add_argument('--swd_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the '
+                                                             'sliced Wasserstein distance (metrics.py); 0: off')
+    p.add_argument('--swd_images', type=int, default=8192, help='images per side of one SWD evaluation')
+    p.add_argument('--swd_seed', type=int, default=0, help='seed of the SWD patch corners, directions, latents and augmentations')
     p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
                                                         'launch.py); batch_size stays the global batch')
     return p

@@ -44,7 +44,9 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # by either side load in the other.  One optional extra key, 'optimizer_state', carries the fused Adam's moments and
 # per-tensor step counts (the reference does not save optimiser state at all).  A trainer that keeps an averaged generator
 # (train.py, `ema_beta`) adds 'Generator_ema_state': the averaged weights under the keys of 'Generator_state', tensors only.  The
-# reference's loaders read the keys they know and ignore the rest.
+# reference's loaders read the keys they know and ignore the rest (utils.py:185-199 index five series keys and the two attribute
+# dictionaries, models.py the state dictionaries).  A run that scores its checkpoints (train.py, `swd_period`) adds 'SWD': a list of
+# {epoch, image_size, levels, swd, swd_ema} -- plain Python numbers and lists, which the weights-only unpickler accepts as it is.
 # ---------------------------------------------------------------------------------------------------------------------
 import os  # noqa: E402
 
@@ -85,6 +87,7 @@ def load_checkpoint_dict(filename, device=torch.device('cpu')):
 
 
 EMA_KEY = 'Generator_ema_state'
+SWD_KEY = 'SWD'
 
 
 class Checkpointer:
@@ -103,6 +106,7 @@ class Checkpointer:
         self.device = device
         self.extra_checkpoint_period = extra_checkpoint_period
         self.trainer = trainer      # optional PGGANTrainer: adds / restores 'optimizer_state' (and 'Generator_ema_state')
+        self.SWD = []               # one entry per scored checkpoint (train.py, `swd_period`); saved only when it holds any
 
     def save_state(self, epoch):
         self.epoch = epoch
@@ -121,6 +125,8 @@ class Checkpointer:
             checkpoint_dict['optimizer_state'] = self.trainer.optimizer_state()
             if getattr(self.trainer, 'ema_enabled', False):
                 checkpoint_dict[EMA_KEY] = cpu(self.trainer.ema_state())
+        if self.SWD:
+            checkpoint_dict[SWD_KEY] = [dict(entry) for entry in self.SWD]
         torch.save(checkpoint_dict, self.filename)
         if epoch % self.extra_checkpoint_period == 0:
             base, ext = os.path.splitext(self.filename)
@@ -140,6 +146,7 @@ class Checkpointer:
             self.Loss_fake[:self.epoch] = checkpoint_dict['Loss_fake']
             self.Loss_G[:self.epoch] = checkpoint_dict['Loss_G']
             self.Loss_D[:self.epoch] = checkpoint_dict['Loss_D']
+            self.SWD = [dict(entry) for entry in checkpoint_dict.get(SWD_KEY, [])]      # a resumed run continues the list
         if 'Generator_attrs' in checkpoint_dict and 'Discriminator_attrs' in checkpoint_dict:
             # (the WGAN nets list no saved_attrs: the reference fails there, utils.py:194-198; here they count as empty)
             gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in getattr(self.Generator_net, 'saved_attrs', [])}
