@@ -598,6 +598,26 @@ int ngan_swd_sort_columns(float* cols, int n_dirs, int n_pad, void* stream);
 size_t ngan_swd_l1_workspace_bytes(int n, int n_dirs);
 int ngan_swd_l1(const float* a, const float* b, double* out, void* workspace, int n, int n_pad, int n_dirs, void* stream);
 
+/* ---- sample diversity: multi-scale structural similarity between pairs of images (Wang, Simoncelli and Bovik 2003, as reported by
+ * Odena et al. 2017 and Karras et al. 2018; an addition of this implementation, off by default; neuron-gan_amd/metrics.py drives it) --
+ * Images are channels-last (P, H, H, C) fp32, H a power of two, C = 1 or 3 (NGAN_ERR_SHAPE otherwise); pair p is (a[p], b[p]).
+ * window:  the 11 taps of the separable Gaussian, sigma = 1.5: g[i] = exp(-(i - 5)^2 / 4.5), normalised to sum 1 in double and then
+ *          rounded to float, written to host memory.  The scale kernel filters with exactly these values.
+ * scale:   out[p] = {mean cs, mean ssim} (two doubles per pair) of one scale, the means over the (H - 10)^2 C entries of the "valid"
+ *          filtering (no padding), H >= 16.  With the Gaussian-weighted moments mu_a, mu_b, E[a a], E[b b], E[a b] of a window,
+ *          var_a = E[a a] - mu_a^2, cov = E[a b] - mu_a mu_b, C1 = (0.01 data_range)^2 and C2 = (0.03 data_range)^2:
+ *              cs = (2 cov + C2) / (var_a + var_b + C2),   l = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1),   ssim = l cs
+ *          in fp32: each 11-tap sum is acc = fmaf(g[k], x[k], acc) for k = 0 .. 10 from acc = 0, rows first, then columns, the
+ *          products a a, b b, a b rounded before the row pass; var and cov are one fmaf each (the difference is rounded once).  The
+ *          per-pixel values are summed in fp64 in a fixed order through `workspace` (the bytes ngan_msssim_workspace_bytes names; no
+ *          floating-point atomics): the result is bit-reproducible and a pair's value does not depend on the rest of the batch.
+ *          P < 65536 pairs per call.
+ * pool2:   the next scale: a_out, b_out (P, H/2, H/2, C) = the 2 x 2 averages of a, b, summed in double and rounded once. */
+int ngan_msssim_window(float* window11);
+size_t ngan_msssim_workspace_bytes(int P, int H);
+int ngan_msssim_scale(const float* a, const float* b, double* out, void* workspace, int P, int H, int C, double data_range, void* stream);
+int ngan_msssim_pool2(const float* a, const float* b, float* a_out, float* b_out, int P, int H, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NGAN_LIB_PATH") or os.path.join(_HERE, "libngan_hip.so")      # (override: A/B runs of kernel variants)
 
 _P, _I, _L, _F, _Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_size_t
+_D = ctypes.c_double
 CONV_SKIP_BORDER = 1     # NGAN_CONV_SKIP_BORDER (include/ngan.h): per-call flag of ngan_conv3x3_fwd / _fwd_ex
 
 # name -> argument types (the trailing void* stream included), mirroring include/ngan.h
@@ -105,6 +106,9 @@ SIGNATURES = {
     "ngan_swd_project": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "ngan_swd_sort_columns": [_P, _I, _I, _P],
     "ngan_swd_l1": [_P, _P, _P, _P, _I, _I, _I, _P],
+    # multi-scale structural similarity (include/ngan.h, last section; metrics.py)
+    "ngan_msssim_scale": [_P, _P, _P, _P, _I, _I, _I, _D, _P],
+    "ngan_msssim_pool2": [_P, _P, _P, _P, _I, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -141,6 +145,8 @@ NON_STATUS = {
     "ngan_swd_descriptors_workspace_bytes": ([_I, _I], _Z),
     "ngan_swd_l1_workspace_bytes": ([_I, _I], _Z),
     "ngan_swd_sort_block_elements": ([], _I),
+    "ngan_msssim_window": ([_P], _I),
+    "ngan_msssim_workspace_bytes": ([_I, _I], _Z),
 }
 
 _lib = None

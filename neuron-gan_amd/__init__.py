@@ -14,7 +14,8 @@ The directory name carries a hyphen, so it is loaded under the module name `neur
     eval.py            sample grid from a checkpoint (the reference's eval.py), optionally from the averaged generator
     launch.py          sharding rule of a data-parallel run and the `--gpus N` rank launcher (standard library only)
     data.py            device-resident dataset with the reference's augmentation chain as one launch per batch
-    metrics.py         sample quality: sliced Wasserstein distance on Laplacian-pyramid patches (csrc/swd.hip), `evaluate_swd`
+    metrics.py         sample quality: sliced Wasserstein distance on Laplacian-pyramid patches (csrc/swd.hip), `evaluate_swd`;
+                       sample diversity: MS-SSIM between pairs of samples (csrc/msssim.hip), `evaluate_msssim`
     workmodel.py       algorithmic FLOP / byte model of an iteration (what bench.py's roofline figures divide by)
 """
 from . import _C, launch, ops, wgan_ops, utils, models, loss_functions, train, data, workmodel, metrics, eval  # noqa: F401, A004

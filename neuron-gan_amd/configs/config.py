@@ -30,6 +30,7 @@ _DEFAULTS = dict(
     beta1=0.5, sim_loss_lambda=0.0, sim_loss_lambda_decay_rate=0.0, drift_epsilon=0.001, resume=False, N_workers=2,
     seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
     swd_period=0, swd_images=8192, swd_seed=0,
+    msssim_period=0, msssim_pairs=10000, msssim_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -92,6 +93,11 @@ def validate_configs(create_dirs=False):
     # the sliced Wasserstein distance at checkpoints (an addition of this implementation): swd_period 0 is off, otherwise every
     # checkpoint whose epoch is a multiple of it is scored on swd_images images per side
     for name, lowest in (('swd_period', 0), ('swd_images', 1), ('swd_seed', 0)):
+        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
+            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
+    # MS-SSIM between pairs of samples at checkpoints (an addition of this implementation), with the same meaning: msssim_period 0 is
+    # off, otherwise every checkpoint whose epoch is a multiple of it is scored on msssim_pairs pairs per side
+    for name, lowest in (('msssim_period', 0), ('msssim_pairs', 1), ('msssim_seed', 0)):
         if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
             raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
     if g['pggan']:

@@ -9,7 +9,13 @@ this implementation, the reference has no quality metric.  Every stage is a kern
 
 `SWD` feeds minibatches of real and generated images and reports one value (x 1e3) per pyramid level R, R/2, ..., 16;
 `evaluate_swd` drives it from a generator and a dataset.  All randomness (patch corners, directions, augmentation draws) comes from
-private host generators seeded by `seed`: torch's global generator is never consumed, so a run trains the same with the metric on."""
+private host generators seeded by `seed`: torch's global generator is never consumed, so a run trains the same with the metric on.
+
+Sample diversity, the other half of that paper's evaluation: the mean multi-scale structural similarity (MS-SSIM, Wang, Simoncelli
+and Bovik 2003) between random pairs of samples, which rises towards 1 when the generator collapses -- kernels of csrc/msssim.hip:
+
+    msssim_scale / msssim_pool2 / msssim       per-pair (cs, ssim) of one scale, the next scale, the whole metric
+    MSSSIM, evaluate_msssim                    accumulation over minibatches of pairs; generated pairs next to pairs of augmented reals"""
 import torch
 
 from . import _C
@@ -305,7 +311,211 @@ def evaluate_swd(generator, dataset, n_images=8192, batch_size=64, seed=0, nhood
     return metric.result()
 
 
+# ---- sample diversity: multi-scale structural similarity between pairs (csrc/msssim.hip; include/ngan.h, last section) -----------------
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)     # Wang, Simoncelli and Bovik 2003
+MSSSIM_WINDOW = 11                                              # taps of the Gaussian window, sigma = 1.5
+DATA_RANGE = 2.0              # width of [-1, 1]: data.py's batches ("augmented images in [-1, 1]") and ToImage's tanh live there
+
+
+def msssim_scales(image_size):
+    """S = min(5, 1 + floor(log2(R / 11))): 16 -> 1, 32 -> 2, 64 -> 3, 128 -> 4, 256 and above -> 5, below 16 -> 0"""
+    s, r = 0, int(image_size)
+    while r >= 16 and s < len(MSSSIM_WEIGHTS):
+        s, r = s + 1, r // 2
+    return s
+
+
+def msssim_weights(scales):
+    """the first `scales` of the published exponents, renormalised to sum 1"""
+    w = MSSSIM_WEIGHTS[:scales]
+    return [v / sum(w) for v in w]
+
+
+def msssim_window():
+    """the 11 fp32 taps the kernel filters with (normalised in fp64, then rounded)"""
+    import ctypes
+    buf = (ctypes.c_float * MSSSIM_WINDOW)()
+    if _C.lib().ngan_msssim_window(ctypes.cast(buf, ctypes.c_void_p)) != 0:
+        raise RuntimeError(_C.lib().ngan_last_error().decode())
+    return torch.tensor(list(buf), dtype=torch.float32)
+
+
+def _pair(a, b):
+    a, b = _images(a), _images(b)
+    if a.shape != b.shape or a.shape[1] != a.shape[2]:
+        raise ValueError(f"two equal stacks of square images (P, R, R, C) expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape[0] == 0:
+        raise ValueError("no pair to score")
+    return a, b
+
+
+def msssim_scale(a, b, data_range=DATA_RANGE):
+    """(P, 2) fp64 on the device: the mean cs and the mean ssim of one scale for every pair (a[p], b[p]); channels-last fp32 images
+    at least 16 pixels wide; the means run over the (R - 10)^2 C entries of the unpadded 11 x 11 Gaussian filtering"""
+    a, b = _pair(a, b)
+    p, r, _, c = a.shape
+    out = torch.empty(p, 2, device=a.device, dtype=torch.float64)
+    ws = torch.empty(max(1, _C.lib().ngan_msssim_workspace_bytes(p, r) // 8), device=a.device, dtype=torch.float64)
+    _C.call("ngan_msssim_scale", a, b, out, ws, p, r, c, float(data_range))
+    return out
+
+
+def msssim_pool2(a, b):
+    """the next scale of both stacks: 2 x 2 averages, (P, R, R, C) -> (P, R/2, R/2, C)"""
+    a, b = _pair(a, b)
+    p, r, _, c = a.shape
+    ao = torch.empty(p, r // 2, r // 2, c, device=a.device, dtype=torch.float32)
+    bo = torch.empty_like(ao)
+    _C.call("ngan_msssim_pool2", a, b, ao, bo, p, r, c)
+    return ao, bo
+
+
+def msssim(a, b, data_range=DATA_RANGE):
+    """(P,) fp64 on the device: MS-SSIM of every pair (a[p], b[p]) of channels-last fp32 images (P, R, R, C), R a power of two >= 16,
+    C in (1, 3).  S = msssim_scales(R) scales, each the 2 x 2 average of the one before; with w = msssim_weights(S)
+
+        MS-SSIM = prod_{s < S} max(cs_s, 0)^w_s * max(ssim_S, 0)^w_S        (combined in fp64)
+
+    data_range: the width of the interval the images live in, 2 by default ([-1, 1], the data set loader's and the generator's range);
+    C1 = (0.01 data_range)^2 and C2 = (0.03 data_range)^2."""
+    a, b = _pair(a, b)
+    scales = msssim_scales(a.shape[1])
+    if scales == 0:
+        raise ValueError(f"{a.shape[1]} x {a.shape[1]} images are below 16 x 16: the 11 x 11 window has no scale to score")
+    w = msssim_weights(scales)
+    value = None
+    for s in range(scales):
+        v = msssim_scale(a, b, data_range)[:, 1 if s == scales - 1 else 0].clamp_min(0.0).pow(w[s])
+        value = v if value is None else value * v
+        if s < scales - 1:
+            a, b = msssim_pool2(a, b)
+    return value
+
+
+class MSSSIM:
+    """Accumulates MS-SSIM over pairs of generated and, optionally, of real images and reports the means.
+
+        m = MSSSIM(image_size=64); m.feed('fake', G(z0), G(z1)); m.feed('real', x0, x1); m.result()
+
+    A collapsed generator shows as a 'fake' mean clearly above the 'real' one (the data's own pair similarity under its augmentations).
+    data_range: see msssim().  A stage below 16 x 16 has no scale: feed() does nothing and result() says so."""
+
+    def __init__(self, image_size, n_colors=1, data_range=DATA_RANGE, device="cuda"):
+        if n_colors not in (1, 3):
+            raise ValueError(f"n_colors={n_colors}: 1 or 3")
+        if image_size < 1 or image_size & (image_size - 1):
+            raise ValueError(f"image_size={image_size} must be a power of two")
+        if not data_range > 0:
+            raise ValueError(f"data_range={data_range!r} must be positive")
+        self.image_size, self.n_colors, self.data_range = int(image_size), int(n_colors), float(data_range)
+        self.device = torch.device(device)
+        self.scales = msssim_scales(self.image_size)
+        self.weights = msssim_weights(self.scales) if self.scales else []
+        self.values = {"fake": [], "real": []}
+
+    def feed(self, which, a, b):
+        if which not in self.values:
+            raise ValueError(f"which={which!r}: 'fake' or 'real'")
+        a, b = channels_last(a.to(self.device)), channels_last(b.to(self.device))
+        want = (self.image_size, self.image_size, self.n_colors)
+        if tuple(a.shape[1:]) != want or a.shape != b.shape:
+            raise ValueError(f"two equal stacks of {self.image_size} pixel wide images with {self.n_colors} colours expected, "
+                             f"got {tuple(a.shape)} and {tuple(b.shape)}")
+        if self.scales:
+            self.values[which].append(msssim(a, b, self.data_range))
+
+    def per_pair(self, which):
+        """(n,) fp64: every value fed so far, in feeding order"""
+        v = self.values[which]
+        return torch.cat(v) if v else torch.empty(0, dtype=torch.float64, device=self.device)
+
+    @staticmethod
+    def _mean_sem(v):
+        n = v.numel()
+        mean = float(v.mean())
+        return mean, (float(v.std(unbiased=True)) / n ** 0.5 if n > 1 else None)
+
+    def result(self):
+        """{'scales': S, 'weights': [...], 'fake': mean, 'fake_sem': standard error of the mean (None for one pair), 'real': mean or
+        None, 'real_sem': ..., 'pairs': generated pairs}; a stage below 16 x 16: scales 0, no number and a 'note'"""
+        if not self.scales:
+            return {"scales": 0, "weights": [], "fake": None, "fake_sem": None, "real": None, "real_sem": None, "pairs": 0,
+                    "note": f"{self.image_size} x {self.image_size} images are below 16 x 16: the 11 x 11 window has no scale to score"}
+        fake, real = self.per_pair("fake"), self.per_pair("real")
+        if fake.numel() == 0:
+            raise ValueError("no generated pair was fed")
+        out = {"scales": self.scales, "weights": list(self.weights), "real": None, "real_sem": None, "pairs": int(fake.numel())}
+        out["fake"], out["fake_sem"] = self._mean_sem(fake)
+        if real.numel():
+            out["real"], out["real_sem"] = self._mean_sem(real)
+        return out
+
+
+def evaluate_msssim(generator, dataset=None, n_pairs=10000, batch_size=64, seed=0, data_range=DATA_RANGE):
+    """Mean MS-SSIM over n_pairs pairs of samples of `generator` at its current resolution and, with a data set, over n_pairs pairs
+    of its images for comparison.  2 n_pairs images are generated under no_grad, pair i = images (2 i, 2 i + 1); the latents follow
+    the sampler's distribution (normal draws clamped to [-5, 5], projected on the unit sphere) and come from a private generator, as
+    in evaluate_swd.  The reals are 2 n_pairs draws through the data set's own augmentation chain (indices cycled, paired the same
+    way), its generator swapped for a private one and its image size set for the duration, both restored afterwards.  batch_size
+    pairs per side are alive at a time; torch's global and device generators are never consumed."""
+    device = next(generator.parameters()).device
+    size = int(generator.image_size)
+    metric = MSSSIM(size, n_colors=int(getattr(generator, "N_colors", 1)), data_range=data_range, device=device)
+    if not metric.scales:
+        return metric.result()
+    n_pairs, batch_size = int(n_pairs), int(batch_size)
+    if n_pairs < 1 or batch_size < 1:
+        raise ValueError(f"n_pairs={n_pairs} and batch_size={batch_size} must be positive")
+    lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
+    for i in range(0, n_pairs, batch_size):
+        n = 2 * min(batch_size, n_pairs - i)
+        z = torch.randn(n, generator.latent_dim, generator=lat).clamp(-5, 5)
+        z = (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
+        with torch.no_grad():
+            fakes = channels_last(generator(z).detach())
+        metric.feed("fake", fakes[0::2].contiguous(), fakes[1::2].contiguous())
+        del fakes
+    if dataset is not None:
+        aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
+        old_size = dataset.image_size
+        own_gen = getattr(dataset, "gen", None)
+        dataset.set_image_size(size)
+        if own_gen is not None:
+            dataset.gen = aug
+        try:
+            n_data = len(dataset)
+            for i in range(0, n_pairs, batch_size):
+                n = 2 * min(batch_size, n_pairs - i)
+                idx = [(2 * i + j) % n_data for j in range(n)]
+                if hasattr(dataset, "batch"):
+                    reals = dataset.batch(idx)
+                else:
+                    reals = torch.stack([dataset[j] for j in idx]).to(device)
+                reals = channels_last(reals)
+                metric.feed("real", reals[0::2].contiguous(), reals[1::2].contiguous())
+                del reals
+        finally:
+            if own_gen is not None:
+                dataset.gen = own_gen
+            dataset.set_image_size(old_size)
+    return metric.result()
+
+
+def format_msssim(result, title="MS-SSIM between pairs"):
+    """the table eval.py prints: one row per side, mean +- standard error"""
+    if not result["scales"]:
+        return f"{title}: {result['note']}"
+    pm = lambda m, s: f"{m:9.5f}" + (f" +- {s:.5f}" if s is not None else "")   # noqa: E731
+    rows = [f"{title} ({result['scales']} scale{'s' if result['scales'] > 1 else ''}, {result['pairs']} pairs)",
+            f"{'generated':>10s} {pm(result['fake'], result['fake_sem'])}"]
+    if result["real"] is not None:
+        rows.append(f"{'data':>10s} {pm(result['real'], result['real_sem'])}")
+    return "\n".join(rows)
+
+
 def format_table(result, title="SWD x 1e3"):
+    if "scales" in result:
+        return format_msssim(result) if title == "SWD x 1e3" else format_msssim(result, title)
     if not result["levels"]:
         return f"{title}: {result['note']}"
     head = " ".join(f"{r:>9d}" for r in result["levels"]) + "      mean"

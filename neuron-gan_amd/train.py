@@ -1384,6 +1384,33 @@ def score_swd(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
     return entry
 
 
+def score_msssim(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
+    """One MS-SSIM evaluation between pairs of samples (metrics.evaluate_msssim with cfg.msssim_pairs pairs per side in minibatches of
+    cfg.batch_size, seed cfg.msssim_seed) of the training generator -- with the data set's own pair similarity next to it -- and, when
+    the trainer averages, of the averaged one: logged in one line and appended to checkpoint.MSSSIM as {epoch, image_size, scales,
+    fake, fake_ema, real, pairs}.  Eager, outside any captured graph, no collective; it draws from private generators only, so the
+    run trains on as if it had not happened."""
+    from .metrics import evaluate_msssim
+    G = trainer.G
+    kw = dict(n_pairs=int(getattr(cfg, 'msssim_pairs', 10000)), batch_size=int(cfg.batch_size), seed=int(getattr(cfg, 'msssim_seed', 0)))
+    res = evaluate_msssim(G, dataset, **kw)
+    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "scales": int(res["scales"]), "fake": res["fake"], "fake_ema": None,
+             "real": res["real"], "pairs": int(res["pairs"])}
+    if res["scales"] and getattr(trainer, "ema_enabled", False):
+        with trainer.averaged_generator():
+            entry["fake_ema"] = evaluate_msssim(G, None, **kw)["fake"]       # (the data's side is the same: not scored twice)
+    if not res["scales"]:
+        log("Epoch:{}, MS-SSIM: {}".format(epoch, res["note"]))
+    else:
+        log("Epoch:{}, MS-SSIM over {} pairs, {} scales: generated {:.5f}{}{}".format(
+            epoch, entry["pairs"], entry["scales"], entry["fake"],
+            "" if entry["fake_ema"] is None else ", averaged generator {:.5f}".format(entry["fake_ema"]),
+            "" if entry["real"] is None else ", data {:.5f}".format(entry["real"])))
+    if checkpoint is not None:
+        checkpoint.MSSSIM.append(entry)
+    return entry
+
+
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
                 samples_dir=None, on_epoch=None, process_group=None, draws=None):
     """The reference's epoch loop (train.py:298-451) over a PGGANTrainer.
@@ -1400,7 +1427,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     the monitor sums are all-reduced once per epoch, so the series, the adaptive critic schedule and the NaN check are the same on
     every rank; rank 0 alone logs, saves and plots.  With one rank nothing of this is active.
     cfg.swd_period > 0: rank 0 scores every checkpoint whose epoch is a multiple of it (`score_swd`) before it is written; the other
-    ranks wait at the checkpoint's barrier.
+    ranks wait at the checkpoint's barrier.  cfg.msssim_period > 0: the same with `score_msssim`.
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
     (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
@@ -1410,6 +1437,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     sim_decay = float(getattr(cfg, 'sim_loss_lambda_decay_rate', 0.0))
     adapt_critic = bool(getattr(cfg, 'adapt_critic', False))
     swd_period = int(getattr(cfg, 'swd_period', 0) or 0)
+    msssim_period = int(getattr(cfg, 'msssim_period', 0) or 0)
     G, D = trainer.G, trainer.D
     dev = trainer.device
     epoch_final = epoch_final if epoch_final is not None else cfg.N_epochs + 1
@@ -1516,6 +1544,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
             if ranks.rank == 0:                                        # replicas are identical: rank 0's state is everyone's
                 if swd_period > 0 and epoch % swd_period == 0:
                     score_swd(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
+                if msssim_period > 0 and epoch % msssim_period == 0:
+                    score_msssim(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 checkpoint.save_state(epoch)
                 if samples_dir is not None:
                     from .utils import plot_gen_samples
@@ -1693,6 +1723,10 @@ def build_arg_parser():
                                                              'sliced Wasserstein distance (metrics.py); 0: off')
     p.add_argument('--swd_images', type=int, default=8192, help='images per side of one SWD evaluation')
     p.add_argument('--swd_seed', type=int, default=0, help='seed of the SWD patch corners, directions, latents and augmentations')
+    p.add_argument('--msssim_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the mean '
+                                                                'MS-SSIM between pairs of samples (metrics.py); 0: off')
+    p.add_argument('--msssim_pairs', type=int, default=10000, help='pairs per side of one MS-SSIM evaluation')
+    p.add_argument('--msssim_seed', type=int, default=0, help='seed of the MS-SSIM latents and augmentations')
     p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
                                                         'launch.py); batch_size stays the global batch')
     return p
