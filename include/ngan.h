@@ -618,6 +618,40 @@ size_t ngan_msssim_workspace_bytes(int P, int H);
 int ngan_msssim_scale(const float* a, const float* b, double* out, void* workspace, int P, int H, int C, double data_range, void* stream);
 int ngan_msssim_pool2(const float* a, const float* b, float* a_out, float* b_out, int P, int H, int C, void* stream);
 
+/* ---- differentiable augmentation of the critic's inputs (Zhao et al. 2020; an addition of this implementation, off by default;
+ * ops.DiffAugment and PGGANTrainer(diffaug=...) drive it) -----------------------------------------------------
+ * Images here are contiguous fp32 (B, C, R, R) -- the reference's own layout, the same bytes as channels-last for C = 1 -- with
+ * square images, R a multiple of 4 (NGAN_ERR_SHAPE otherwise), starting on a 16-byte boundary.  N = C R R.  Images and their
+ * gradients are fp32 in every arithmetic mode.  Sample n has one parameter row of 32 bytes in `table`,
+ *     struct { float b, c; int tx, ty, i0, i1, j0, j1; }
+ * and `table_rows`, the rows the table holds, must be at least B (NGAN_ERR_ARG otherwise).
+ * fwd:     m_n = (sum x[n]) / N                       (fp64 sum, fixed order)
+ *          k_n = fp32(c b + (1 - c)(m_n + b))         (brightness x + b, then contrast c about the new mean; formed in double)
+ *          u   = fmaf(c, x, k_n)
+ *          y[n, ch, i, j] = u[n, ch, i + tx, j + ty]  if (i + tx, j + ty) lies inside the image and (i, j) outside [i0, i1) x [j0, j1),
+ *                           `fill` otherwise (a finite constant: 0 is DiffAugment's own; its derivative is 0, so bwd does not take it)
+ * bwd:     gu[q] = gy[q - t] where q - t lies inside the image and outside the cutout, else 0
+ *          r_n = fp32((1 - c) / N * sum_q gu[q])      (fp64, fixed order: a masked sum of gy)
+ *          gx  = fmaf(c, gu, r_n)
+ *          The identity row {0, 1, 0, 0, 0, 0, 0, 0} reproduces x and gy bit for bit, whatever fill is.
+ * colour:  0 -- the caller states that every row has b = 0, c = 1: the two columns are not read, the sum pass is not launched (one
+ *          launch instead of two) and workspace may be NULL; otherwise workspace holds ngan_diffaug_workspace_bytes(B, C, R) bytes.
+ *          y / gx may be a row range of a larger batch buffer (the pointer of its first row).  No atomics: bit-reproducible.
+ * params:  uniforms (B, 8) in [0, 1) -> rows 0 .. B-1 of table, for R x R images.  policy: bits 1 colour, 2 translation, 4 cutout;
+ *          a group outside the policy, or whose gate is closed, gets its identity values.  With S = int(R 0.125 + 0.5),
+ *          K = int(R 0.5 + 0.5) and draw(u, n) = min(n - 1, floor(u n)) in fp32:
+ *              colour       open if u0 < p:  b = u1 - 0.5, c = u2 + 0.5
+ *              translation  open if u3 < p:  d = draw(u4, (2S + 1)^2), tx = d / (2S + 1) - S, ty = d % (2S + 1) - S
+ *              cutout       open if u5 < p:  oi = draw(u6, R + 1 - K % 2), oj = draw(u7, R + 1 - K % 2),
+ *                                            [i0, i1) = [oi - K/2, oi - K/2 + K) cut to [0, R), [j0, j1) likewise from oj
+ *          (saturation, DiffAugment's third colour operation, is left out: the data are greyscale) */
+size_t ngan_diffaug_workspace_bytes(int B, int C, int R);
+int ngan_diffaug_params(const float* uniforms, void* table, int B, int H, int W, int table_rows, int policy, float p, void* stream);
+int ngan_diffaug_fwd(const float* x, const void* table, float* y, void* workspace, int B, int C, int H, int W, int table_rows,
+                     int colour, float fill, void* stream);
+int ngan_diffaug_bwd(const float* gy, const void* table, float* gx, void* workspace, int B, int C, int H, int W, int table_rows,
+                     int colour, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

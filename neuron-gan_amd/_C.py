@@ -109,6 +109,10 @@ SIGNATURES = {
     # multi-scale structural similarity (include/ngan.h, last section; metrics.py)
     "ngan_msssim_scale": [_P, _P, _P, _P, _I, _I, _I, _D, _P],
     "ngan_msssim_pool2": [_P, _P, _P, _P, _I, _I, _I, _P],
+    # differentiable augmentation (include/ngan.h, last section; ops.DiffAugment)
+    "ngan_diffaug_params": [_P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "ngan_diffaug_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
+    "ngan_diffaug_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -147,6 +151,7 @@ NON_STATUS = {
     "ngan_swd_sort_block_elements": ([], _I),
     "ngan_msssim_window": ([_P], _I),
     "ngan_msssim_workspace_bytes": ([_I, _I], _Z),
+    "ngan_diffaug_workspace_bytes": ([_I, _I, _I], _Z),
 }
 
 _lib = None

@@ -31,6 +31,7 @@ _DEFAULTS = dict(
     seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
     swd_period=0, swd_images=8192, swd_seed=0,
     msssim_period=0, msssim_pairs=10000, msssim_seed=0,
+    diffaug='', diffaug_p=1.0, diffaug_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -100,6 +101,17 @@ def validate_configs(create_dirs=False):
     for name, lowest in (('msssim_period', 0), ('msssim_pairs', 1), ('msssim_seed', 0)):
         if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
             raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
+    # differentiable augmentation of the critic's inputs (an addition of this implementation): diffaug '' is off, otherwise a comma
+    # list of groups, each applied to each sample with probability diffaug_p; diffaug_seed seeds the parameters' private stream
+    groups = [s.strip() for s in g['diffaug'].split(',')] if isinstance(g['diffaug'], str) else None
+    if groups is None or any(s not in ('', 'color', 'translation', 'cutout') for s in groups):
+        raise ValueError(f"diffaug={g['diffaug']!r} must be a comma list from color, translation, cutout (empty: off)")
+    if isinstance(g['diffaug_p'], bool) or not (isinstance(g['diffaug_p'], (int, float)) and 0 <= g['diffaug_p'] <= 1):
+        raise ValueError(f"diffaug_p={g['diffaug_p']!r} must lie in [0, 1]")
+    if not (isinstance(g['diffaug_seed'], int) and not isinstance(g['diffaug_seed'], bool) and g['diffaug_seed'] >= 0):
+        raise ValueError(f"diffaug_seed={g['diffaug_seed']!r} must be an integer >= 0")
+    if any(groups) and g['wgan'] and not g['pggan']:
+        raise ValueError(f"diffaug={g['diffaug']!r} is not available for the WGAN nets (wgan=True, pggan=False)")
     if g['pggan']:
         err_msg = 'The number of layers in the generator and discriminator must match.'
         assert len(g['N_gen_features']) == len(g['N_dis_features']), err_msg

@@ -5,7 +5,8 @@
     D_grad_pen_loss(G, D, Lambda)(real)      -> loss   (create_graph double-backward through the critic)
 
 Latents come from `utils.sample_latent_vec` unless a tensor is passed through the optional `z=` / `epsilon=`
-keywords (how the parity tests inject the reference's draws).  NaN handling: the reference dumps locals and
+keywords (how the parity tests inject the reference's draws).  Every loss takes an optional `augment=` hook (`DiffAugmentHook`, an
+addition of this implementation: differentiable augmentation of everything the critic sees); None is the reference's path.  NaN handling: the reference dumps locals and
 raises `ValueError` (loss_functions.py:35-41, 70-72); here the check is optional (`check_nan`) because
 `torch.isnan(...)` in an `if` is a host sync on the GPU -- the training loop checks once per epoch instead.
 """
@@ -22,6 +23,42 @@ def _latents(net, batch, device, z):
     return sample_latent_vec((batch, net.latent_dim), device=device)
 
 
+# What a shifted-out or cut pixel holds.  DiffAugment writes 0; here that is fatal: the critic's biases start at zero and each of its
+# blocks ends in PixelNorm with eps 1e-8, so a pixel whose whole neighbourhood is exactly 0 has an all-zero feature vector, where
+# PixelNorm's derivative is rsqrt(eps) = 1e4 -- per block.  On a six-block critic a 64 x 64 zero patch takes the input-gradient norm
+# from 1e-2 to 1e9 and the gradient penalty overflows (tests/test_diffaug_cpu.py pins both figures on the CPU oracle).  -1 is the
+# images' black, what the reference's own RandomAffine fill becomes after Renormalize (data/NeuronDataset.py:112-126).
+DIFFAUG_FILL = -1.0
+
+
+class DiffAugmentHook:
+    """The `augment=` hook of the three losses: differentiable augmentation (ops.DiffAugment) of every image the
+    critic sees, each kind of image with a parameter table of its own (int32 (rows, 8), `ops.diffaug_table` / `ops.diffaug_params`):
+        real   the real images                        fake   the W-loss's generated images
+        tilde  the penalty's generated images         gen    the generator step's images (the only differentiated use)
+    The critic-step images carry no gradient and are augmented without an autograd node; the penalty interpolates between images
+    that are already augmented, so its double-backward graph is the un-augmented one.  colour=False: no table opens the colour
+    group (b = 0, c = 1 everywhere), which saves the sum pass of every call.  fill: what shifted-out and cut pixels hold
+    (`DIFFAUG_FILL`)."""
+
+    def __init__(self, real=None, fake=None, tilde=None, gen=None, colour=True, fill=DIFFAUG_FILL):
+        self.real, self.fake, self.tilde, self.gen, self.colour, self.fill = real, fake, tilde, gen, bool(colour), float(fill)
+
+    def critic_batch(self, real, fake):
+        """[T(real) | T(fake)], the W-loss's one critic batch: both halves are written straight into it"""
+        b = real.size(0)
+        out = torch.empty((b + fake.size(0),) + tuple(real.shape[1:]), device=real.device, dtype=real.dtype)
+        ops.diffaug(real, self.real, self.colour, out=out[:b], fill=self.fill)
+        ops.diffaug(fake, self.fake, self.colour, out=out[b:], fill=self.fill)
+        return out
+
+    def penalty_pair(self, real, x_tilde):
+        return ops.diffaug(real, self.real, self.colour, fill=self.fill), ops.diffaug(x_tilde, self.tilde, self.colour, fill=self.fill)
+
+    def generated(self, fake):
+        return ops.DiffAugment.apply(fake, self.gen, self.colour, self.fill)
+
+
 class D_W_loss(nn.Module):
     def __init__(self, generator_net, discriminator_net, drift_epsilon=0.0, check_nan=True):
         super().__init__()
@@ -30,7 +67,7 @@ class D_W_loss(nn.Module):
         self.drift_epsilon = drift_epsilon
         self.check_nan = check_nan
 
-    def forward(self, real_images, z=None, fake_images=None):
+    def forward(self, real_images, z=None, fake_images=None, augment=None):
         batch_size, device = real_images.size(0), real_images.device
         if fake_images is None:
             z = _latents(self.generator_net, batch_size, device, z)
@@ -39,7 +76,8 @@ class D_W_loss(nn.Module):
         # D(real) and D(fake) share the weights and no op couples samples, so they run as ONE critic pass over the
         # concatenated batch (the reference makes two calls, loss_functions.py:21, 29; per-sample results are identical)
         with ops.first_order_only():      # differentiated once (train.py:365): fused PixelNorm-backward epilogues apply
-            scores = self.discriminator_net(torch.cat([real_images, fake_images], dim=0))
+            both = torch.cat([real_images, fake_images], dim=0) if augment is None else augment.critic_batch(real_images, fake_images)
+            scores = self.discriminator_net(both)
         # -mean(real) + mean(fake) + drift * mean(real^2) (loss_functions.py:22, 29, 33, 45) as one launch each way
         D_loss, score_real, score_fake = ops.WLossHead.apply(scores, batch_size, float(self.drift_epsilon) if self.drift_epsilon > 0 else 0.0)
         if self.check_nan:
@@ -57,10 +95,12 @@ class G_W_loss(nn.Module):
         self.discriminator_net = discriminator_net
         self.check_nan = check_nan
 
-    def forward(self, real_images_batch, z=None):
+    def forward(self, real_images_batch, z=None, augment=None):
         batch_size, device = real_images_batch.size(0), real_images_batch.device
         z_latent = _latents(self.generator_net, batch_size, device, z)
         fake_images = self.generator_net(z_latent)
+        if augment is not None:
+            fake_images = augment.generated(fake_images)      # D(T(G(z))): the generator is trained through the transform
         with ops.first_order_only():      # differentiated once (train.py:384)
             G_loss = ops.WLossHead.apply(self.discriminator_net(fake_images), batch_size, 0.0)[0]       # -mean(D(G(z)))
         if self.check_nan and torch.isnan(G_loss):
@@ -82,7 +122,7 @@ class D_grad_pen_loss(nn.Module):
             self._ones_cache = torch.ones_like(like)
         return self._ones_cache
 
-    def forward(self, real_images, z=None, epsilon=None, x_tilde=None):
+    def forward(self, real_images, z=None, epsilon=None, x_tilde=None, augment=None):
         if not self.Lambda > 0:
             # the reference returns the integer CPU scalar torch.tensor(0) here (loss_functions.py:179), which only survives being
             # stacked / accumulated with device tensors by accident; same value, on the images' device
@@ -94,6 +134,8 @@ class D_grad_pen_loss(nn.Module):
                 x_tilde = self.generator_net(z_latent)
         if epsilon is None:
             epsilon = torch.rand((batch_size, 1, 1, 1), device=device)
+        if augment is not None:
+            real_images, x_tilde = augment.penalty_pair(real_images, x_tilde)
         x_hat = ops.xhat(real_images, x_tilde, epsilon)
         x_hat.requires_grad_()
         output = self.discriminator_net(x_hat)

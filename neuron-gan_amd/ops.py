@@ -1420,3 +1420,105 @@ def latent_normalize_(z, clamp=5.0):
     """in place: rows of normal draws -> clamp(-5, 5) -> unit L2 norm (reference utils.py:77-78); one launch"""
     _C.call("ngan_latent_normalize", z, z.shape[0], z.shape[1], float(clamp))
     return z
+
+
+# ---------------------------------------------------------------------------------------------------------
+# differentiable augmentation of the critic's inputs (include/ngan.h, last section; DESIGN.md section 7)
+# ---------------------------------------------------------------------------------------------------------
+DIFFAUG_GROUPS = {"color": 1, "translation": 2, "cutout": 4}      # policy names -> bits of ngan_diffaug_params' mask
+DIFFAUG_IDENTITY = (0.0, 1.0, 0, 0, 0, 0, 0, 0)                  # {b, c, tx, ty, i0, i1, j0, j1}
+
+
+def diffaug_policy_mask(policy):
+    """"" / "color,translation,cutout" (any subset, any order) -> the mask; an unknown name raises ValueError"""
+    if policy is None:
+        return 0
+    if not isinstance(policy, str):
+        raise ValueError(f"diffaug must be a comma list from {sorted(DIFFAUG_GROUPS)}, got {policy!r}")
+    mask = 0
+    for name in (s.strip() for s in policy.split(",")):
+        if name == "":
+            continue
+        if name not in DIFFAUG_GROUPS:
+            raise ValueError(f"diffaug: unknown group {name!r} (a comma list from {sorted(DIFFAUG_GROUPS)})")
+        mask |= DIFFAUG_GROUPS[name]
+    return mask
+
+
+def diffaug_table(rows, device=None):
+    """A parameter table from rows {b, c, tx, ty, i0, i1, j0, j1}: an int32 (B, 8) tensor whose first two columns hold the bits of
+    the two floats -- the 32-byte records of include/ngan.h."""
+    rec = np.zeros(len(rows), dtype=[("b", "<f4"), ("c", "<f4")] + [(n, "<i4") for n in ("tx", "ty", "i0", "i1", "j0", "j1")])
+    for i, row in enumerate(rows):
+        rec[i] = tuple(row)
+    t = torch.from_numpy(rec.view("<i4").reshape(len(rows), 8).copy())
+    return t if device is None else t.to(device)
+
+
+def diffaug_table_rows(table):
+    """inverse of diffaug_table: a list of tuples (b, c, tx, ty, i0, i1, j0, j1)"""
+    raw = np.ascontiguousarray(table.detach().cpu().numpy().astype("<i4"))
+    rec = raw.view([("b", "<f4"), ("c", "<f4")] + [(n, "<i4") for n in ("tx", "ty", "i0", "i1", "j0", "j1")]).reshape(-1)
+    return [tuple(v.item() for v in r) for r in rec]
+
+
+def _diffaug_check(x, table):
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"diffaug: images must be fp32 (B, C, R, R), got {x.dtype} {tuple(x.shape)}")
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 8:
+        raise ValueError(f"diffaug: the table must be int32 (rows, 8), got {table.dtype} {tuple(table.shape)}")
+
+
+def _diffaug_ws(x, colour):
+    if not colour:
+        return None
+    b, c, r, _ = x.shape
+    return torch.empty(int(_C.lib().ngan_diffaug_workspace_bytes(b, c, r)) // 8, device=x.device, dtype=torch.float64)
+
+
+def diffaug_params(uniforms, table, image_size, policy_mask, p):
+    """rows 0 .. B-1 of `table` from the (B, 8) uniforms, on the device (ngan_diffaug_params)"""
+    _C.call("ngan_diffaug_params", _c(uniforms), table, uniforms.shape[0], int(image_size), int(image_size), table.shape[0],
+            int(policy_mask), float(p))
+    return table
+
+
+def diffaug(x, table, colour=True, out=None, fill=0.0):
+    """T(x) with no autograd node, for images that carry no gradient (the critic step): `out` may be a row range of a larger batch
+    buffer, so the critic's concatenated input is written in place."""
+    x = _c(x.detach())
+    _diffaug_check(x, table)
+    b, c, h, w = x.shape
+    y = torch.empty_like(x) if out is None else out
+    if y.shape != x.shape or y.dtype != x.dtype:
+        raise ValueError(f"diffaug: out is {y.dtype} {tuple(y.shape)}, the images {x.dtype} {tuple(x.shape)}")
+    _C.call("ngan_diffaug_fwd", x, table, y, _diffaug_ws(x, colour), b, c, h, w, table.shape[0], int(bool(colour)), float(fill))
+    return y
+
+
+class DiffAugment(Function):
+    """y = T(x) for the parameter table `table` (one row per sample; `diffaug_table`, or rows `diffaug_params` wrote), differentiable
+    once in x: brightness, contrast about the mean, integer translation with zero fill, one cutout.  colour=False states that every
+    row has b = 0, c = 1 and saves the sum pass each way.  fill: the constant stored where the shift or the cutout leaves nothing
+    (0: DiffAugment's; the trainer passes -1)."""
+
+    @staticmethod
+    def forward(ctx, x, table, colour=True, fill=0.0):
+        x = _c(x)
+        _diffaug_check(x, table)
+        b, c, h, w = x.shape
+        y = torch.empty_like(x)
+        _C.call("ngan_diffaug_fwd", x, table, y, _diffaug_ws(x, colour), b, c, h, w, table.shape[0], int(bool(colour)), float(fill))
+        ctx.save_for_backward(table)
+        ctx.colour = bool(colour)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        (table,) = ctx.saved_tensors
+        gy = _c(gy)
+        b, c, h, w = gy.shape
+        gx = torch.empty_like(gy)
+        _C.call("ngan_diffaug_bwd", gy, table, gx, _diffaug_ws(gy, ctx.colour), b, c, h, w, table.shape[0], int(ctx.colour))
+        return gx, None, None, None

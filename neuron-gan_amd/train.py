@@ -24,7 +24,7 @@ import torch.distributed as dist
 
 from . import _C, ops, wgan_ops
 from .launch import check_sharding, longest_share, shard_bounds
-from .loss_functions import D_W_loss, D_grad_pen_loss, G_W_loss
+from .loss_functions import D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_W_loss
 from .utils import sample_latent_vec, sample_latent_vec_device
 
 ADAM_CHUNK = 4096  # elements per work item of ngan_adam_step / ngan_rmsprop_step (must match csrc/adam.hip)
@@ -410,6 +410,92 @@ def _check_ema_beta(ema_beta):
     return float(ema_beta)
 
 
+DIFFAUG_ROWS = 16384   # rows of a trainer's parameter tables (512 KB, and as much again for the uniforms): n_critic x 3 b + b of them serve an iteration
+
+
+def _check_diffaug(policy, p, seed):
+    """(policy mask, p, seed) of the trainer arguments; mask 0 is off -- also for p = 0, which closes every gate"""
+    mask = ops.diffaug_policy_mask(policy)
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"diffaug_p must lie in [0, 1], got {p!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError(f"diffaug_seed must be an integer >= 0, got {seed!r}")
+    return (mask if float(p) > 0.0 else 0), float(p), int(seed)
+
+
+def diffaug_stream_seed(seed, epoch, rank):
+    """the seed of a rank's private uniform stream at the start of `epoch` (0: construction)"""
+    return ((int(seed) * 1000003 + int(epoch)) * 1000003 + int(rank)) % (2 ** 63 - 1)
+
+
+class _CriticAugment(DiffAugmentHook):
+    """The hook of a trainer's critic step: `prepare` augments the reals (table `real`) and all generated images of the step (table
+    `fake`: the W-loss's b rows, then the penalty's b) once, into one batch buffer; the W-loss reads its first 2 b rows as they lie
+    -- no concatenation -- and the penalty interpolates between the first and the last b."""
+
+    def prepare(self, real, fakes):
+        b = real.size(0)
+        self._buf = torch.empty((b + fakes.size(0),) + tuple(real.shape[1:]), device=real.device, dtype=real.dtype)
+        ops.diffaug(real, self.real, self.colour, out=self._buf[:b], fill=self.fill)
+        ops.diffaug(fakes, self.fake, self.colour, out=self._buf[b:], fill=self.fill)
+
+    def critic_batch(self, real, fake):
+        return self._buf[:real.size(0) + fake.size(0)]
+
+    def penalty_pair(self, real, x_tilde):
+        b = real.size(0)
+        return self._buf[:b], self._buf[2 * b:3 * b]
+
+
+class _DiffAugTables:
+    """A trainer's differentiable augmentation (`diffaug`; an addition of this implementation, the reference has none): the policy, one
+    persistent table buffer and one persistent uniform buffer -- captured graphs hold their addresses, so neither is ever
+    reallocated -- and a private generator on the trainer's device, so that neither the global nor the latent stream is touched.
+    Rows of an iteration on b samples: critic step s has [s 3b, s 3b + b) for the reals and the 2 b after them for its generated
+    images; the generator step's b rows follow the last critic step's."""
+
+    def __init__(self, mask, p, seed, device, rank):
+        self.mask, self.p, self.seed, self.rank = mask, p, seed, rank
+        self.colour = bool(mask & ops.DIFFAUG_GROUPS["color"])
+        self.table = ops.diffaug_table([ops.DIFFAUG_IDENTITY], device).repeat(DIFFAUG_ROWS, 1).contiguous()
+        self.uniforms = torch.zeros((DIFFAUG_ROWS, 8), device=device, dtype=torch.float32)
+        self.generator = torch.Generator(device=device)
+        self.reseed(0)
+
+    def reseed(self, epoch, rank=None):
+        self.generator.manual_seed(diffaug_stream_seed(self.seed, epoch, self.rank if rank is None else rank))
+
+    def rows(self, b, n_critic):
+        return max(int(n_critic), 1) * 3 * b + b
+
+    def prepare(self, b, n_critic, image_size, tables=None):
+        """the tables of one iteration: drawn from the private stream and mapped on the device, or copied from `tables`
+        ({"real": (b, 8), "fake": (2 b, 8), "gen": (b, 8)} int32, any subset; every critic step of the iteration gets the same)"""
+        n = self.rows(b, n_critic)
+        if n > DIFFAUG_ROWS:
+            raise ValueError(f"diffaug: batch {b} with n_critic {n_critic} needs {n} table rows, the buffer holds {DIFFAUG_ROWS}")
+        if tables is None:
+            torch.rand((n, 8), generator=self.generator, out=self.uniforms[:n])
+            ops.diffaug_params(self.uniforms[:n], self.table, image_size, self.mask, self.p)
+            return
+        for s in range(max(int(n_critic), 1)):
+            for name, view in (("real", self.real(s, b)), ("fake", self.fake(s, b))):
+                if tables.get(name) is not None:
+                    view.copy_(tables[name], non_blocking=True)
+        if tables.get("gen") is not None:
+            self.gen(b, n_critic).copy_(tables["gen"], non_blocking=True)
+
+    def real(self, s, b):
+        return self.table[s * 3 * b:s * 3 * b + b]
+
+    def fake(self, s, b):
+        return self.table[s * 3 * b + b:(s + 1) * 3 * b]
+
+    def gen(self, b, n_critic):
+        o = max(int(n_critic), 1) * 3 * b
+        return self.table[o:o + b]
+
+
 class _AveragedGenerator:
     """The averaged generator of a trainer (`ema_beta`; an addition of this implementation, the reference has none): an exponential
     moving average of the generator's parameters, e' = e + (1 - beta)(p' - e) once per generator step, kept by the generator's
@@ -482,15 +568,23 @@ class PGGANTrainer(_AveragedGenerator):
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
-                 rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0):
+                 rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0):
         """optimizer: "adam" -- optim.Adam(params, lr, betas=(beta1, 0.999)), the reference's default -- or "rmsprop" --
         optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps), what the reference's RMSprop switch selects (train.py:220-225);
         beta1 only matters for Adam
         ema_beta: 0 or None -- off (no buffer, no launch: the code path of a build without the feature); 0 < ema_beta < 1 -- keep the
-        averaged generator with this decay (`_AveragedGenerator`)"""
+        averaged generator with this decay (`_AveragedGenerator`)
+        diffaug: "" -- off (no buffer, no launch, no random draw: the code path of a build without the feature); a comma list from
+        color, translation, cutout -- every image the critic sees, real and generated, goes through the same random differentiable
+        transform (Zhao et al. 2020) and the generator is trained through it; shifted-out and cut pixels hold
+        -1, the images' black, not DiffAugment's 0 (loss_functions.DIFFAUG_FILL says why).  diffaug_p: the probability with
+        which each group is applied to each sample (1: DiffAugment proper; 0: off).  diffaug_seed: of the private uniform stream
+        (`reseed_diffaug`).  train_iteration, replay and step draw an iteration's tables; d_step / g_step on their own read the
+        tables as they stand (`draw_diffaug_tables`)."""
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
         ema_beta = _check_ema_beta(ema_beta)
+        aug_mask, aug_p, aug_seed = _check_diffaug(diffaug, diffaug_p, diffaug_seed)
         self.G, self.D = generator, discriminator
         self.device = next(generator.parameters()).device
         self.n_critic = n_critic
@@ -531,8 +625,36 @@ class PGGANTrainer(_AveragedGenerator):
             self._comm_stream = torch.cuda.Stream(device=self.device)
         self._graphs = {}          # input shape -> captured graphs of this stage (capture / replay)
         self._graph = self._entry = None
+        self._aug = None
+        self._aug_step = 0         # which critic step of the iteration d_compute serves (train_iteration counts)
+        if aug_mask:
+            rank = dist.get_rank(process_group) if self.world > 1 else 0     # every rank draws a stream of its own
+            self._aug = _DiffAugTables(aug_mask, aug_p, aug_seed, self.device, rank)
         self.refresh_stage()
         ops.bump_weight_epoch()
+
+    # ---- differentiable augmentation ---------------------------------------------------------------------------
+    @property
+    def diffaug_enabled(self):
+        return self._aug is not None
+
+    def reseed_diffaug(self, epoch, rank=None):
+        """restart the private uniform stream from (diffaug_seed, epoch, rank) -- the epoch drivers do at every epoch start, so a
+        resumed run draws what the uninterrupted one draws from that epoch on"""
+        if self._aug is not None:
+            self._aug.reseed(epoch, rank)
+
+    def draw_diffaug_tables(self, b, tables=None):
+        """The tables of one iteration on b samples: fresh draws from the private stream, or `tables` ({"real": (b, 8), "fake":
+        (2 b, 8), "gen": (b, 8)}, int32: `ops.diffaug_table`).  Eager by design -- inside a stream capture this is a no-op, the
+        captured launches read the persistent buffer and replay() refills it first."""
+        if self._aug is None:
+            if tables is not None:
+                raise ValueError("tables were passed to a trainer without a diffaug policy")
+            return
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            return
+        self._aug.prepare(b, self.n_critic, self.G.image_size, tables)
 
     def enable_stem_exchange(self, for_exchange=True):
         """Exchange the stem's gradient as gathered factors; the all-reduce then skips its segment of the flat buffer."""
@@ -651,8 +773,14 @@ class PGGANTrainer(_AveragedGenerator):
                 zs = [self._latent(b, z_d)] + ([self._latent(b, z_gp)] if with_gp else [])
                 zz = torch.cat(zs, dim=0) if with_gp else zs[0]
             fakes = self.G(zz)
-        loss, s_real, s_fake = self.d_loss(real, fake_images=fakes[:b])  # train.py:358
-        gp = self.gp_loss(real, x_tilde=fakes[b:] if with_gp else None, epsilon=eps)  # train.py:361
+        hook = None
+        if self._aug is not None:
+            # reals and all generated images of the step are augmented once, detached; the W-loss and the penalty read views
+            hook = _CriticAugment(real=self._aug.real(self._aug_step, b), fake=self._aug.fake(self._aug_step, b)[:fakes.size(0)],
+                                  colour=self._aug.colour)
+            hook.prepare(real, fakes)
+        loss, s_real, s_fake = self.d_loss(real, fake_images=fakes[:b], augment=hook)  # train.py:358
+        gp = self.gp_loss(real, x_tilde=fakes[b:] if with_gp else None, epsilon=eps, augment=hook if with_gp else None)  # train.py:361
         # train.py:362, 365: D_loss += gp; D_loss.backward().  The two terms share no graph node (separate critic passes), so the sum's
         # backward is the two backwards; they run one after the other so that every critic parameter receives its contributions in
         # a fixed order (penalty terms, then the W-loss term): autograd's node order inside ONE run over both graphs is not
@@ -684,7 +812,10 @@ class PGGANTrainer(_AveragedGenerator):
         for p in d_params:  # the reference also back-propagates into the critic's weights here and discards the result
             p.requires_grad_(False)
         try:
-            loss, self.last_z_g = self.g_loss(real, z=self._latent(b, z))  # train.py:376
+            hook = None
+            if self._aug is not None:
+                hook = DiffAugmentHook(gen=self._aug.gen(b, self.n_critic), colour=self._aug.colour)
+            loss, self.last_z_g = self.g_loss(real, z=self._latent(b, z), augment=hook)  # train.py:376
             # the stem hands over factors instead of a gradient when they are exchanged (data parallel) or go straight to Adam
             self._stem_sink_active = self.stem is not None and (self._stem_for_exchange or self._stem_grad_skipped)
             ops.linear_grad_sink = self.stem.sink if self._stem_sink_active else None
@@ -726,11 +857,17 @@ class PGGANTrainer(_AveragedGenerator):
         self.g_adam()
         return stats
 
-    def train_iteration(self, real, z_d=None, z_gp=None, eps=None, z_g=None, global_batch=None):
-        """global_batch: the size of the whole batch this rank's `real` is a share of (None: world * real.size(0))"""
+    def train_iteration(self, real, z_d=None, z_gp=None, eps=None, z_g=None, global_batch=None, tables=None):
+        """global_batch: the size of the whole batch this rank's `real` is a share of (None: world * real.size(0))
+        tables: injected augmentation tables (`draw_diffaug_tables`), the way z_d .. z_g inject the latents"""
+        if self._aug is not None or tables is not None:
+            self.draw_diffaug_tables(real.size(0), tables)
         stats = {}
-        for _ in range(self.n_critic):  # train.py:356
+        self._aug_step = 0
+        for s in range(self.n_critic):  # train.py:356
+            self._aug_step = s
             stats.update(self.d_step(real, z_d, z_gp, eps, global_batch))
+        self._aug_step = 0
         if self.n_critic == 0:          # adaptive critic schedule chose no critic step: losses for monitoring only (train.py:369-372)
             stats.update(self.d_compute(real, z_d, z_gp, eps, global_batch))
         stats.update(self.g_step(real, z_g, global_batch))
@@ -796,7 +933,7 @@ class PGGANTrainer(_AveragedGenerator):
             return tuple(shape)
         return tuple(shape) + ("global", tuple(global_batch) if isinstance(global_batch, (tuple, list)) else int(global_batch))
 
-    def capture(self, real_example, warmup=1, draws=None, global_batch=None):
+    def capture(self, real_example, warmup=1, draws=None, global_batch=None, tables=None):
         """Capture `train_iteration` for this batch shape into HIP graphs (latents and epsilon drawn on the GPU inside
         the graph).  Afterwards `replay(real)` copies `real` into the static input of the graphs captured for its shape and
         launches them.  One GPU: one graph for the whole iteration.  Data parallel: three graphs -- [D forward/backward],
@@ -811,6 +948,8 @@ class PGGANTrainer(_AveragedGenerator):
 
         draws: optional dict of STATIC device tensors {"z_d", "z_gp", "eps", "z_g"} used instead of drawing inside the graph; the
         caller refills them before each replay (how the parity tests replay an eager trajectory exactly).
+        tables: injected augmentation tables for the warm-up iterations (train_iteration); the graphs read the trainer's persistent
+        table buffer, which replay() refills -- from its own `tables` or from the private stream, whose state capture() restores.
         global_batch: as in train_iteration.  The share weight is read from device memory by the captured backward passes, so the
         graphs serve every global batch with the same longest share (`_graph_key`)."""
         if draws is None and not self.device_latents:
@@ -827,18 +966,21 @@ class PGGANTrainer(_AveragedGenerator):
         state = self._training_state()
         saved = [t.clone() for t in state]
         rng = torch.cuda.get_rng_state(self.device)
+        aug_rng = self._aug.generator.get_state() if self._aug is not None else None
         lr_g, lr_d = self.opt_g.param_groups[0]["lr"], self.opt_d.param_groups[0]["lr"]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
-                self.train_iteration(static_real, *d_args, z_g, global_batch)
+                self.train_iteration(static_real, *d_args, z_g, global_batch, tables)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         for t, v in zip(state, saved):
             t.copy_(v)
         del saved
         torch.cuda.set_rng_state(rng, self.device)
+        if aug_rng is not None:
+            self._aug.generator.set_state(aug_rng)
         assert (lr_g, lr_d) == (self.opt_g.param_groups[0]["lr"], self.opt_d.param_groups[0]["lr"])
         ops.bump_weight_epoch()   # the warm-up registered every packed weight (persistent buffers, allocated outside capture):
         self.opt_d.repack()       # rebuild both re-pack tables now (from the restored parameters), so that the captured Adam
@@ -922,9 +1064,10 @@ class PGGANTrainer(_AveragedGenerator):
     def has_graph(self, shape, global_batch=None):
         return self._graph_key(shape, global_batch) in self._graphs
 
-    def replay(self, real=None, global_batch=None):
+    def replay(self, real=None, global_batch=None, tables=None):
         """One training iteration from the captured graphs.  `real` selects the graphs by its shape (capture() them first);
-        without an argument the most recently captured graphs run on their static input as it stands."""
+        without an argument the most recently captured graphs run on their static input as it stands.
+        With a diffaug policy the iteration's tables are drawn (or copied from `tables`) first, eagerly."""
         if real is not None:
             entry = self._graphs.get(self._graph_key(real.shape, global_batch))
             if entry is None:
@@ -938,6 +1081,8 @@ class PGGANTrainer(_AveragedGenerator):
             entry = self._entry
         graphs, static_real, stats, stem_factors, _, stem_flags = entry
         _set_share(self, static_real.size(0), global_batch)
+        if self._aug is not None or tables is not None:
+            self.draw_diffaug_tables(static_real.size(0), tables)
         if self.stem is not None:
             self.stem.captured = stem_factors     # the factors THESE graphs fill (see capture())
         self._stem_grad_skipped, self._stem_sink_active = stem_flags
@@ -1000,8 +1145,11 @@ class WGANTrainer(_AveragedGenerator):
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, drift_epsilon=0.001, n_critic=1, clip=0.01,
                  optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None, sync_batchnorm=False,
-                 ema_beta=0.0):
-        """ema_beta: as PGGANTrainer's -- the averaged generator's parameters; its BatchNorm buffers stay the live ones"""
+                 ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0):
+        """ema_beta: as PGGANTrainer's -- the averaged generator's parameters; its BatchNorm buffers stay the live ones
+        diffaug: must be empty -- differentiable augmentation is built for the PGGAN trainer only"""
+        if ops.diffaug_policy_mask(diffaug):
+            raise ValueError(f"diffaug={diffaug!r}: differentiable augmentation is not available for the WGAN nets (PGGANTrainer only)")
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
         ema_beta = _check_ema_beta(ema_beta)
@@ -1484,6 +1632,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
             ranks.assert_same(G.image_size, "the image size after a growth event")
         if on_epoch is not None:
             on_epoch(epoch, trainer)
+        if getattr(trainer, "diffaug_enabled", False):                # the private stream restarts from (seed, epoch, rank): resumable
+            trainer.reseed_diffaug(epoch, ranks.rank)
         # number of critic steps this epoch (train.py:336-340); the score series lags one epoch here (deferred read-back)
         if adapt_critic and len(series["score_real"]) > adapt_period:
             n_d_steps = Calculate_D_steps(series["score_real"], series["score_fake"], 0, cfg.n_critic, Period=adapt_period)
@@ -1719,6 +1869,10 @@ def build_arg_parser():
                                                           'synthetic uniform images when omitted')
     p.add_argument('--N_epochs_session', type=int, default=None)
     p.add_argument('--ema_beta', type=float, default=0.0, help='decay of the averaged generator (e.g. 0.999); 0: off')
+    p.add_argument('--diffaug', type=str, default='', help='differentiable augmentation of every image the critic sees: a comma list '
+                                                           'from color,translation,cutout; empty: off')
+    p.add_argument('--diffaug_p', type=float, default=1.0, help='probability of each augmentation group per sample')
+    p.add_argument('--diffaug_seed', type=int, default=0, help='seed of the augmentation parameters\' private stream')
     p.add_argument('--swd_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the '
                                                              'sliced Wasserstein distance (metrics.py); 0: off')
     p.add_argument('--swd_images', type=int, default=8192, help='images per side of one SWD evaluation')
@@ -1763,15 +1917,17 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     if config.wgan and config.pggan:
         raise ValueError("wgan=True together with pggan=True is not a configuration the reference can train (it fails at "
                          "Generator_net.image_size); choose one")
+    aug = dict(diffaug=getattr(config, 'diffaug', ''), diffaug_p=getattr(config, 'diffaug_p', 1.0),
+               diffaug_seed=getattr(config, 'diffaug_seed', 0))
     if config.wgan:
         kw = dict(learning_rate=config.learning_rate, drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, device_latents=True,
-                  process_group=process_group, sync_batchnorm=bool(distributed), ema_beta=getattr(config, 'ema_beta', 0.0))
+                  process_group=process_group, sync_batchnorm=bool(distributed), ema_beta=getattr(config, 'ema_beta', 0.0), **aug)
         if config.RMSprop:
             return WGANTrainer(G, D, optimizer="rmsprop", **kw)
         return WGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
     kw = dict(learning_rate=config.learning_rate, grad_pen_lambda=config.grad_pen_lambda, drift_epsilon=config.drift_epsilon,
               n_critic=config.n_critic, alpha_step=config.alpha_step, device_latents=True, process_group=process_group,
-              ema_beta=getattr(config, 'ema_beta', 0.0))
+              ema_beta=getattr(config, 'ema_beta', 0.0), **aug)
     if config.RMSprop:
         return PGGANTrainer(G, D, optimizer="rmsprop", **kw)
     return PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
