@@ -652,6 +652,27 @@ int ngan_diffaug_fwd(const float* x, const void* table, float* y, void* workspac
 int ngan_diffaug_bwd(const float* gy, const void* table, float* gx, void* workspace, int B, int C, int H, int W, int table_rows,
                      int colour, void* stream);
 
+/* ---- spectral fidelity: the radial power spectrum of images (Durall et al. 2020; an addition of this implementation, off by default;
+ * neuron-gan_amd/metrics.py drives it) -- a batched 2-D real transform in LDS, no vendor FFT library ------------
+ * Images are channels-last (B, R, R, C) fp32, R a power of two in 16 .. 1024, C = 1 or 3, 1 <= B <= 65535 (NGAN_ERR_SHAPE otherwise).
+ * window:       the R taps of the periodic Hann window, h[i] = 0.5 - 0.5 cos(2 pi i / R) in double, rounded to float, to host memory.
+ * ring_counts:  n_0 .. n_{R/2} to host memory: the number of signed frequencies (u, v) in [-R/2, R/2)^2 whose d = u^2 + v^2 lies in
+ *               ring k, the integer with (2k-1)^2 <= 4d < (2k+1)^2 (k = 0 for d = 0), i.e. floor(sqrt(d) + 1/2) decided in integers.
+ * radial:       per image and channel F = the 2-D DFT of x w, with w[y][x] = h[y] h[x] one fp32 product on load and x w one more
+ *               (window = 0: w = 1, no product); P = |F|^2 / norm in fp32 (two products and one addition, no contraction), norm =
+ *               (sum h^2)^2 of the taps in double (R^2 without the window);
+ *                   radial[b][k] = sum over channels and the frequencies of ring k of P / (C n_k),   k = 0 .. R/2 (corners dropped)
+ *               (B, R/2 + 1) doubles, summed in fp64 in a fixed order through `workspace` (ngan_spectrum_workspace_bytes names its
+ *               size; it also holds the row pass's half spectrum): no atomics, bit-reproducible, and an image's values do not depend
+ *               on the rest of the batch.  power_or_null: when given, P of the half plane, (B, C, R, R/2 + 1) fp32, the x frequency
+ *               0 .. R/2 last, the y frequency in DFT order; `radial` is the same bits with and without it.  images, power and
+ *               workspace start on a 16-byte boundary, radial on an 8-byte one (NGAN_ERR_ARG otherwise, as for a null pointer). */
+int ngan_spectrum_window(float* taps, int R);
+int ngan_spectrum_ring_counts(int* counts, int R);
+size_t ngan_spectrum_workspace_bytes(int B, int R, int C);
+int ngan_spectrum_radial(const float* images, double* radial, float* power_or_null, void* workspace, int B, int R, int C, int window,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,8 @@ SIGNATURES = {
     "ngan_diffaug_params": [_P, _P, _I, _I, _I, _I, _I, _F, _P],
     "ngan_diffaug_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "ngan_diffaug_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    # radial power spectrum (include/ngan.h, last section; metrics.py)
+    "ngan_spectrum_radial": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -152,6 +154,9 @@ NON_STATUS = {
     "ngan_msssim_window": ([_P], _I),
     "ngan_msssim_workspace_bytes": ([_I, _I], _Z),
     "ngan_diffaug_workspace_bytes": ([_I, _I, _I], _Z),
+    "ngan_spectrum_window": ([_P, _I], _I),
+    "ngan_spectrum_ring_counts": ([_P, _I], _I),
+    "ngan_spectrum_workspace_bytes": ([_I, _I, _I], _Z),
 }
 
 _lib = None

@@ -31,6 +31,7 @@ _DEFAULTS = dict(
     seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
     swd_period=0, swd_images=8192, swd_seed=0,
     msssim_period=0, msssim_pairs=10000, msssim_seed=0,
+    spectrum_period=0, spectrum_images=8192, spectrum_seed=0,
     diffaug='', diffaug_p=1.0, diffaug_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
@@ -99,6 +100,11 @@ def validate_configs(create_dirs=False):
     # MS-SSIM between pairs of samples at checkpoints (an addition of this implementation), with the same meaning: msssim_period 0 is
     # off, otherwise every checkpoint whose epoch is a multiple of it is scored on msssim_pairs pairs per side
     for name, lowest in (('msssim_period', 0), ('msssim_pairs', 1), ('msssim_seed', 0)):
+        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
+            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
+    # the radial power spectrum of samples against the data at checkpoints (an addition of this implementation), with the same meaning:
+    # spectrum_period 0 is off, otherwise every checkpoint whose epoch is a multiple of it is scored on spectrum_images images per side
+    for name, lowest in (('spectrum_period', 0), ('spectrum_images', 1), ('spectrum_seed', 0)):
         if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
             raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
     # differentiable augmentation of the critic's inputs (an addition of this implementation): diffaug '' is off, otherwise a comma

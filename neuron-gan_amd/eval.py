@@ -9,10 +9,13 @@ of the checkpoint's generator per pyramid level against N images (default 8192) 
 train.py reads it; default config.dataset_dir) or --images (a .pt / .npy file of (N, C, R, R) images in [-1, 1]) names; with --ema
 the table of the averaged generator follows.  --msssim [N] prints the mean MS-SSIM (metrics.py) over N pairs of samples (default
 10000) -- a collapsed generator scores near 1 -- and, when --dataset_dir or --images names a data set (or config.dataset_dir exists),
-the same statistic over N pairs of its augmented images to read it against; it combines with --swd and --ema.
+the same statistic over N pairs of its augmented images to read it against; it combines with --swd and --ema.  --spectrum [N] prints
+the radial power spectrum (metrics.py) of N samples (default 8192) against N images of the data set, named as for --swd, at the octave
+edges, with the mean distance in dB and the top octave's signed deficit; it combines with --swd, --msssim and --ema.
 
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --swd 8192 --dataset_dir data/science_2022 [--ema]
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --msssim 10000 --dataset_dir data/science_2022 [--ema]
+    python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --spectrum 8192 --dataset_dir data/science_2022 [--ema]
 
 The generator runs on the HIP kernels, so this needs a GPU, like train.py."""
 import argparse
@@ -33,13 +36,16 @@ def build_arg_parser():
     p.add_argument('--msssim', type=int, nargs='?', const=10000, default=None, metavar='N',
                    help='print the mean MS-SSIM over N pairs of samples, and of the data set when one is named (default 10000)')
     p.add_argument('--msssim_seed', type=int, default=0, help='seed of the MS-SSIM latents and augmentations')
+    p.add_argument('--spectrum', type=int, nargs='?', const=8192, default=None, metavar='N',
+                   help='print the radial power spectrum of N samples against N images of the data set (default 8192)')
+    p.add_argument('--spectrum_seed', type=int, default=0, help='seed of the spectrum latents and augmentations')
     p.add_argument('--dataset_dir', type=str, default='', help='folder of training images (default: config.dataset_dir)')
     p.add_argument('--images', type=str, default='', help='.pt / .npy file with the images (N, C, R, R) in [-1, 1]')
     return p
 
 
 def load_dataset(options, config, device):
-    """the data set `--swd` / `--msssim` score against, read the way train.py reads it"""
+    """the data set `--swd` / `--msssim` / `--spectrum` score against, read the way train.py reads it"""
     import numpy as np
     import torch
     from .data import NeuronDataset
@@ -73,6 +79,8 @@ def main(argv=None):
     device = torch.device('cuda')
     if options.msssim is not None and options.msssim < 1:
         raise ValueError('--msssim {}: at least one pair'.format(options.msssim))
+    if options.spectrum is not None and options.spectrum < 1:
+        raise ValueError('--spectrum {}: at least one image'.format(options.spectrum))
     if options.swd is not None:
         from .metrics import evaluate_swd, format_table
         if options.swd < 1:
@@ -83,7 +91,7 @@ def main(argv=None):
             res = evaluate_swd(G, dataset, n_images=options.swd, batch_size=min(options.swd, 32), seed=options.swd_seed)
             print(format_table(res, 'SWD x 1e3, {} generator of {} against {} images'.format(
                 'averaged' if use_ema else 'training', options.weights, options.swd)))
-        if options.msssim is None:
+        if options.msssim is None and options.spectrum is None:
             return 0
     if options.msssim is not None:
         from .metrics import evaluate_msssim, format_msssim
@@ -94,6 +102,17 @@ def main(argv=None):
             res = evaluate_msssim(G, dataset, n_pairs=options.msssim, batch_size=min(options.msssim, 32), seed=options.msssim_seed)
             print(format_msssim(res, 'MS-SSIM between pairs, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                        options.weights)))
+        if options.spectrum is None:
+            return 0
+    if options.spectrum is not None:
+        from .metrics import evaluate_spectrum, format_spectrum
+        dataset = load_dataset(options, config, device)
+        for use_ema in ((False, True) if options.ema else (False,)):
+            G = Generator_PG.from_state_dict(weights, device=device, use_ema=use_ema, verbose=False).to(device)
+            res = evaluate_spectrum(G, dataset, n_images=options.spectrum, batch_size=min(options.spectrum, 32),
+                                    seed=options.spectrum_seed)
+            print(format_spectrum(res, 'Radial power spectrum, {} generator of {}'.format('averaged' if use_ema else 'training',
+                                                                                          options.weights)))
         return 0
     G = Generator_PG.from_state_dict(weights, device=device, use_ema=options.ema).to(device)
     plot_gen_samples(G, N_images=options.n, filename=output)

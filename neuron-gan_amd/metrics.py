@@ -15,7 +15,15 @@ Sample diversity, the other half of that paper's evaluation: the mean multi-scal
 and Bovik 2003) between random pairs of samples, which rises towards 1 when the generator collapses -- kernels of csrc/msssim.hip:
 
     msssim_scale / msssim_pool2 / msssim       per-pair (cs, ssim) of one scale, the next scale, the whole metric
-    MSSSIM, evaluate_msssim                    accumulation over minibatches of pairs; generated pairs next to pairs of augmented reals"""
+    MSSSIM, evaluate_msssim                    accumulation over minibatches of pairs; generated pairs next to pairs of augmented reals
+
+Spectral fidelity: the radial power spectrum of samples against the data's (Durall et al. 2020: generators that upsample and convolve
+fall short at the high-frequency end, which is where this data keeps its noise texture) -- kernels of csrc/spectrum.hip:
+
+    radial_spectrum / power_spectrum           per image the ring means of |F|^2 of the (Hann-windowed) image; the half-plane power
+    Spectrum, evaluate_spectrum                accumulation over minibatches of both sets; per-bin ratio in dB, distance_db, high_db"""
+import math
+
 import torch
 
 from . import _C
@@ -510,6 +518,195 @@ def format_msssim(result, title="MS-SSIM between pairs"):
             f"{'generated':>10s} {pm(result['fake'], result['fake_sem'])}"]
     if result["real"] is not None:
         rows.append(f"{'data':>10s} {pm(result['real'], result['real_sem'])}")
+    return "\n".join(rows)
+
+
+# ---- spectral fidelity: radial power spectrum of samples against the data's (csrc/spectrum.hip; include/ngan.h, last section) ---------
+SPECTRUM_MIN, SPECTRUM_MAX = 16, 1024        # image sizes the kernels transform
+
+
+def _host_array(entry, ctype, n, *args):
+    import ctypes
+    buf = (ctype * n)()
+    if getattr(_C.lib(), entry)(ctypes.cast(buf, ctypes.c_void_p), *args) != 0:
+        raise RuntimeError(_C.lib().ngan_last_error().decode())
+    return list(buf)
+
+
+def spectrum_window(R):
+    """the R fp32 taps of the periodic Hann window the kernels apply (formed in fp64, then rounded)"""
+    import ctypes
+    return torch.tensor(_host_array("ngan_spectrum_window", ctypes.c_float, max(int(R), 1), int(R)), dtype=torch.float32)
+
+
+def spectrum_ring_counts(R):
+    """n_0 .. n_{R/2}: the number of frequencies of the R x R plane in every ring"""
+    import ctypes
+    return torch.tensor(_host_array("ngan_spectrum_ring_counts", ctypes.c_int, max(int(R) // 2 + 1, 1), int(R)), dtype=torch.int64)
+
+
+def _spectrum(images, window, want_power):
+    x = _images(images)
+    b, r, r2, c = x.shape
+    if r != r2:
+        raise ValueError(f"square images (B, R, R, C) expected, got {tuple(x.shape)}")
+    if b == 0:
+        raise ValueError("no image to transform")
+    radial = torch.empty(b, r // 2 + 1, device=x.device, dtype=torch.float64)
+    power = torch.empty(b, c, r, r // 2 + 1, device=x.device, dtype=torch.float32) if want_power else None
+    ws = torch.empty(max(1, _C.lib().ngan_spectrum_workspace_bytes(b, r, c) // 8), device=x.device, dtype=torch.float64)
+    _C.call("ngan_spectrum_radial", x, radial, power, ws, b, r, c, int(bool(window)))
+    return radial, power
+
+
+def radial_spectrum(images, window=True):
+    """(B, R/2 + 1) fp64 on the device: per image the mean over the colour channels and over ring k (signed frequencies with
+    floor(sqrt(u^2 + v^2) + 1/2) = k, decided in integers; the corners beyond R/2 are dropped) of |F|^2 / sum w^2, F the 2-D DFT of
+    the image under the periodic Hann window w (window=False: none).  Channels-last fp32 images (B, R, R, C), R a power of two in
+    16 .. 1024, C in (1, 3).  White noise of variance s^2 gives s^2 in every bin."""
+    return _spectrum(images, window, False)[0]
+
+
+def power_spectrum(images, window=True):
+    """(radial, power): radial_spectrum's result, the same bits, and the power of the half plane, (B, C, R, R/2 + 1) fp32 with the
+    x frequency 0 .. R/2 last and the y frequency in DFT order"""
+    return _spectrum(images, window, True)
+
+
+class Spectrum:
+    """Accumulates the radial power spectra of real and generated images and compares their means bin by bin.
+
+        m = Spectrum(image_size=64); m.feed('real', x); m.feed('fake', G(z)); m.result()
+
+    ratio_db[k] = 10 log10(generated / data); distance_db is the mean |ratio_db| over k = 1 .. R/2 (bin 0, the windowed mean level,
+    is reported but not scored); high_db the signed mean over the top octave R/4 < k <= R/2: negative when the samples lack fine
+    texture (the upsampling deficit), positive when they are noisier than the data.  A stage below 16 x 16 has no bins: feed() does
+    nothing and result() says so."""
+
+    def __init__(self, image_size, n_colors=1, window=True, device="cuda"):
+        if n_colors not in (1, 3):
+            raise ValueError(f"n_colors={n_colors}: 1 or 3")
+        if image_size < 1 or image_size & (image_size - 1):
+            raise ValueError(f"image_size={image_size} must be a power of two")
+        if image_size > SPECTRUM_MAX:
+            raise ValueError(f"image_size={image_size}: the kernels transform up to {SPECTRUM_MAX} x {SPECTRUM_MAX}")
+        self.image_size, self.n_colors, self.window = int(image_size), int(n_colors), bool(window)
+        self.device = torch.device(device)
+        self.bins = self.image_size // 2 + 1 if self.image_size >= SPECTRUM_MIN else 0
+        self.count = {"real": 0, "fake": 0}
+        self.sums = {"real": None, "fake": None}          # (2, bins) fp64 on the device: sum S, sum S^2
+
+    def feed(self, which, images):
+        if which not in self.count:
+            raise ValueError(f"which={which!r}: 'real' or 'fake'")
+        x = channels_last(images.to(self.device))
+        if tuple(x.shape[1:]) != (self.image_size, self.image_size, self.n_colors):
+            raise ValueError(f"images must be {self.image_size} pixels wide with {self.n_colors} colours, got {tuple(images.shape)}")
+        if not self.bins:
+            return
+        s = radial_spectrum(x, self.window)
+        both = torch.stack([s.sum(0), s.square().sum(0)])
+        self.sums[which] = both if self.sums[which] is None else self.sums[which] + both
+        self.count[which] += x.shape[0]
+
+    def _mean_sem(self, which):
+        n = self.count[which]
+        tot, sq = self.sums[which].tolist()
+        mean = [t / n for t in tot]
+        if n < 2:
+            return mean, [None] * len(mean)
+        return mean, [math.sqrt(max(q - n * m * m, 0.0) / (n - 1) / n) for q, m in zip(sq, mean)]
+
+    def result(self):
+        """{'k': [0 .. R/2], 'real': [mean S per bin], 'fake': [...], 'real_sem', 'fake_sem': standard errors of those means (None for
+        one image), 'ratio_db': [per bin; None where either mean is 0], 'distance_db', 'high_db', 'skipped_bins': scored bins left
+        out for that reason, 'images': n per side}; a stage below 16 x 16: empty lists, no number and a 'note'"""
+        if not self.bins:
+            return {"k": [], "real": [], "fake": [], "real_sem": [], "fake_sem": [], "ratio_db": [], "distance_db": None,
+                    "high_db": None, "skipped_bins": 0, "images": 0,
+                    "note": f"{self.image_size} x {self.image_size} images are below {SPECTRUM_MIN} x {SPECTRUM_MIN}: no ring to score"}
+        n = self.count["real"]
+        if n == 0 or n != self.count["fake"]:
+            raise ValueError(f"{n} real and {self.count['fake']} generated images; feed both sets equally")
+        real, real_sem = self._mean_sem("real")
+        fake, fake_sem = self._mean_sem("fake")
+        ratio = [10.0 * math.log10(f / r) if f > 0.0 and r > 0.0 else None for f, r in zip(fake, real)]
+        scored = [v for v in ratio[1:] if v is not None]
+        high = [v for v in ratio[self.image_size // 4 + 1:] if v is not None]
+        return {"k": list(range(self.bins)), "real": real, "fake": fake, "real_sem": real_sem, "fake_sem": fake_sem, "ratio_db": ratio,
+                "distance_db": sum(abs(v) for v in scored) / len(scored) if scored else None,
+                "high_db": sum(high) / len(high) if high else None,
+                "skipped_bins": len(ratio) - 1 - len(scored), "images": n}
+
+
+def evaluate_spectrum(generator, dataset, n_images=8192, batch_size=64, seed=0, window=True, real_from=None, return_metric=False):
+    """The radial power spectrum of `generator`'s samples against `dataset`'s images at the generator's current resolution, built
+    like evaluate_swd: n_images reals through the data set's own augmentation chain (its indices cycled, its generator swapped for a
+    private one and its image size set for the duration, both restored afterwards), n_images fakes under no_grad from latents of the
+    sampler's distribution (normal draws clamped to [-5, 5], projected on the unit sphere) drawn from a private generator; one
+    minibatch of images per side alive at a time; torch's global and device generators are never consumed.
+    real_from: a Spectrum that an earlier call returned (return_metric=True: the call then returns (result, metric)) with the same
+    settings -- its data side is taken over instead of being computed again, and `dataset` is not touched (it may be None)."""
+    device = next(generator.parameters()).device
+    size = int(generator.image_size)
+    metric = Spectrum(size, n_colors=int(getattr(generator, "N_colors", 1)), window=window, device=device)
+    if not metric.bins:
+        return (metric.result(), metric) if return_metric else metric.result()
+    if real_from is not None:
+        if (real_from.image_size, real_from.n_colors, real_from.window, real_from.count["real"]) != \
+                (metric.image_size, metric.n_colors, metric.window, int(n_images)):
+            raise ValueError("real_from was fed with other settings")
+        metric.count["real"], metric.sums["real"] = real_from.count["real"], real_from.sums["real"]
+    n_images, batch_size = int(n_images), int(batch_size)
+    if n_images < 1 or batch_size < 1:
+        raise ValueError(f"n_images={n_images} and batch_size={batch_size} must be positive")
+    aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
+    lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
+    if real_from is None:
+        old_size = dataset.image_size
+        own_gen = getattr(dataset, "gen", None)
+        dataset.set_image_size(size)
+        if own_gen is not None:
+            dataset.gen = aug
+    try:
+        for i in range(0, n_images, batch_size):
+            b = min(batch_size, n_images - i)
+            if real_from is None:
+                idx = [(i + j) % len(dataset) for j in range(b)]
+                if hasattr(dataset, "batch"):
+                    reals = dataset.batch(idx)
+                else:
+                    reals = torch.stack([dataset[j] for j in idx]).to(device)
+                metric.feed("real", reals)
+                del reals
+            z = torch.randn(b, generator.latent_dim, generator=lat).clamp(-5, 5)
+            z = (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
+            with torch.no_grad():
+                fakes = generator(z).detach()
+            metric.feed("fake", fakes)
+            del fakes
+    finally:
+        if real_from is None:
+            if own_gen is not None:
+                dataset.gen = own_gen
+            dataset.set_image_size(old_size)
+    return (metric.result(), metric) if return_metric else metric.result()
+
+
+def format_spectrum(result, title="Radial power spectrum"):
+    """the table eval.py prints: data, generated and their ratio in dB at the octave edges k = 1, 2, 4, ..., R/2, the two summaries
+    below it"""
+    if not result["k"]:
+        return f"{title}: {result['note']}"
+    rows = [f"{title} ({result['images']} images per side)", f"{'k':>6s} {'data':>12s} {'generated':>12s} {'dB':>8s}"]
+    k = 1
+    while k < len(result["k"]):
+        db = result["ratio_db"][k]
+        rows.append(f"{k:6d} {result['real'][k]:12.5e} {result['fake'][k]:12.5e} " + (f"{db:8.2f}" if db is not None else f"{'-':>8s}"))
+        k *= 2
+    num = lambda v: "-" if v is None else f"{v:.2f}"   # noqa: E731
+    rows.append(f"distance_db {num(result['distance_db'])}   high_db {num(result['high_db'])}"
+                + (f"   ({result['skipped_bins']} bins without power left out)" if result["skipped_bins"] else ""))
     return "\n".join(rows)
 
 

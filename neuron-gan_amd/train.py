@@ -1559,6 +1559,38 @@ def score_msssim(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
     return entry
 
 
+def score_spectrum(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
+    """One radial-power-spectrum evaluation (metrics.evaluate_spectrum with cfg.spectrum_images images per side in minibatches of
+    cfg.batch_size, seed cfg.spectrum_seed) of the training generator against the data set and, when the trainer averages, of the
+    averaged one: logged in one line and appended to checkpoint.SPECTRUM as {epoch, image_size, images, k, real, fake, ratio_db,
+    distance_db, high_db} plus {distance_db_ema, high_db_ema} with an averaged generator (the data's side is the same: it is not
+    stored twice).  Eager, outside any captured graph, no collective; it draws from private generators only, so the run trains on as
+    if it had not happened."""
+    from .metrics import evaluate_spectrum
+    G = trainer.G
+    kw = dict(n_images=int(getattr(cfg, 'spectrum_images', 8192)), batch_size=int(cfg.batch_size),
+              seed=int(getattr(cfg, 'spectrum_seed', 0)))
+    res, metric = evaluate_spectrum(G, dataset, return_metric=True, **kw)
+    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "images": int(res["images"]), "k": list(res["k"]),
+             "real": list(res["real"]), "fake": list(res["fake"]), "ratio_db": list(res["ratio_db"]),
+             "distance_db": res["distance_db"], "high_db": res["high_db"]}
+    if res["k"] and getattr(trainer, "ema_enabled", False):
+        with trainer.averaged_generator():
+            ema = evaluate_spectrum(G, None, real_from=metric, **kw)     # (the data's side is the same: not scored twice)
+        entry["distance_db_ema"], entry["high_db_ema"] = ema["distance_db"], ema["high_db"]
+    if not res["k"]:
+        log("Epoch:{}, spectrum: {}".format(epoch, res["note"]))
+    else:
+        db = lambda v: "-" if v is None else "{:+.2f} dB".format(v)   # noqa: E731
+        log("Epoch:{}, spectrum over {} images: distance {}, top octave {}{}".format(
+            epoch, entry["images"], db(entry["distance_db"]), db(entry["high_db"]),
+            "" if "high_db_ema" not in entry else ", averaged generator: distance {}, top octave {}".format(
+                db(entry["distance_db_ema"]), db(entry["high_db_ema"]))))
+    if checkpoint is not None:
+        checkpoint.SPECTRUM.append(entry)
+    return entry
+
+
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
                 samples_dir=None, on_epoch=None, process_group=None, draws=None):
     """The reference's epoch loop (train.py:298-451) over a PGGANTrainer.
@@ -1575,7 +1607,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     the monitor sums are all-reduced once per epoch, so the series, the adaptive critic schedule and the NaN check are the same on
     every rank; rank 0 alone logs, saves and plots.  With one rank nothing of this is active.
     cfg.swd_period > 0: rank 0 scores every checkpoint whose epoch is a multiple of it (`score_swd`) before it is written; the other
-    ranks wait at the checkpoint's barrier.  cfg.msssim_period > 0: the same with `score_msssim`.
+    ranks wait at the checkpoint's barrier.  cfg.msssim_period > 0: the same with `score_msssim`; cfg.spectrum_period > 0: with `score_spectrum`.
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
     (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
@@ -1586,6 +1618,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     adapt_critic = bool(getattr(cfg, 'adapt_critic', False))
     swd_period = int(getattr(cfg, 'swd_period', 0) or 0)
     msssim_period = int(getattr(cfg, 'msssim_period', 0) or 0)
+    spectrum_period = int(getattr(cfg, 'spectrum_period', 0) or 0)
     G, D = trainer.G, trainer.D
     dev = trainer.device
     epoch_final = epoch_final if epoch_final is not None else cfg.N_epochs + 1
@@ -1696,6 +1729,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
                     score_swd(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 if msssim_period > 0 and epoch % msssim_period == 0:
                     score_msssim(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
+                if spectrum_period > 0 and epoch % spectrum_period == 0:
+                    score_spectrum(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 checkpoint.save_state(epoch)
                 if samples_dir is not None:
                     from .utils import plot_gen_samples
@@ -1881,6 +1916,10 @@ def build_arg_parser():
                                                                 'MS-SSIM between pairs of samples (metrics.py); 0: off')
     p.add_argument('--msssim_pairs', type=int, default=10000, help='pairs per side of one MS-SSIM evaluation')
     p.add_argument('--msssim_seed', type=int, default=0, help='seed of the MS-SSIM latents and augmentations')
+    p.add_argument('--spectrum_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the '
+                                                                  'radial power spectrum of samples against the data (metrics.py); 0: off')
+    p.add_argument('--spectrum_images', type=int, default=8192, help='images per side of one spectrum evaluation')
+    p.add_argument('--spectrum_seed', type=int, default=0, help='seed of the spectrum latents and augmentations')
     p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
                                                         'launch.py); batch_size stays the global batch')
     return p

@@ -47,7 +47,8 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # reference's loaders read the keys they know and ignore the rest (utils.py:185-199 index five series keys and the two attribute
 # dictionaries, models.py the state dictionaries).  A run that scores its checkpoints (train.py, `swd_period`) adds 'SWD': a list of
 # {epoch, image_size, levels, swd, swd_ema} -- plain Python numbers and lists, which the weights-only unpickler accepts as it is.
-# Likewise `msssim_period` adds 'MSSSIM': a list of {epoch, image_size, scales, fake, fake_ema, real, pairs}.
+# Likewise `msssim_period` adds 'MSSSIM': a list of {epoch, image_size, scales, fake, fake_ema, real, pairs}, and `spectrum_period`
+# adds 'SPECTRUM': a list of {epoch, image_size, images, k, real, fake, ratio_db, distance_db, high_db[, distance_db_ema, high_db_ema]}.
 # ---------------------------------------------------------------------------------------------------------------------
 import os  # noqa: E402
 
@@ -90,6 +91,7 @@ def load_checkpoint_dict(filename, device=torch.device('cpu')):
 EMA_KEY = 'Generator_ema_state'
 SWD_KEY = 'SWD'
 MSSSIM_KEY = 'MSSSIM'
+SPECTRUM_KEY = 'SPECTRUM'
 
 
 class Checkpointer:
@@ -110,6 +112,7 @@ class Checkpointer:
         self.trainer = trainer      # optional PGGANTrainer: adds / restores 'optimizer_state' (and 'Generator_ema_state')
         self.SWD = []               # one entry per scored checkpoint (train.py, `swd_period`); saved only when it holds any
         self.MSSSIM = []            # the same for `msssim_period`
+        self.SPECTRUM = []          # the same for `spectrum_period`
 
     def save_state(self, epoch):
         self.epoch = epoch
@@ -132,6 +135,8 @@ class Checkpointer:
             checkpoint_dict[SWD_KEY] = [dict(entry) for entry in self.SWD]
         if self.MSSSIM:
             checkpoint_dict[MSSSIM_KEY] = [dict(entry) for entry in self.MSSSIM]
+        if self.SPECTRUM:
+            checkpoint_dict[SPECTRUM_KEY] = [dict(entry) for entry in self.SPECTRUM]
         torch.save(checkpoint_dict, self.filename)
         if epoch % self.extra_checkpoint_period == 0:
             base, ext = os.path.splitext(self.filename)
@@ -153,6 +158,7 @@ class Checkpointer:
             self.Loss_D[:self.epoch] = checkpoint_dict['Loss_D']
             self.SWD = [dict(entry) for entry in checkpoint_dict.get(SWD_KEY, [])]      # a resumed run continues the list
             self.MSSSIM = [dict(entry) for entry in checkpoint_dict.get(MSSSIM_KEY, [])]
+            self.SPECTRUM = [dict(entry) for entry in checkpoint_dict.get(SPECTRUM_KEY, [])]
         if 'Generator_attrs' in checkpoint_dict and 'Discriminator_attrs' in checkpoint_dict:
             # (the WGAN nets list no saved_attrs: the reference fails there, utils.py:194-198; here they count as empty)
             gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in getattr(self.Generator_net, 'saved_attrs', [])}
