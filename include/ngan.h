@@ -673,6 +673,30 @@ size_t ngan_spectrum_workspace_bytes(int B, int R, int C);
 int ngan_spectrum_radial(const float* images, double* radial, float* power_or_null, void* workspace, int B, int R, int C, int window,
                          void* stream);
 
+/* ---- arbor morphology: connectivity and box counts of the thresholded image (an addition of this implementation, off by default;
+ * neuron-gan_amd/metrics.py drives it) ------------------------------------------------------------------------------
+ * Images are channels-last (B, R, R, C) fp32, R a power of two in 16 .. 1024, C = 1 or 3, 1 <= B <= 65535 (NGAN_ERR_SHAPE otherwise).
+ * Every result is an integer, the only atomics are integer ones: every output is bit-reproducible, and an image's values do not
+ * depend on the rest of the batch.  Pointers to images, levels, mask, labels, kept and workspace start on a 16-byte boundary, the
+ * others on a 4-byte one (NGAN_ERR_ARG otherwise, as for a null pointer); a refused call writes nothing.
+ * levels:    levels (B, R, R) bytes: (int) min(max(fmaf(g, 127.5f, 128.0f), 0), 255), truncated -- the 8-bit level of [-1, 1] rounded
+ *            to nearest; g is the pixel for C = 1 and (x0 + x1 + x2) * (1.0f / 3.0f), summed left to right in fp32, for C = 3.
+ *            hist (B, 256) counts of those levels, overwritten: what ngan_multiotsu4_noise_stats takes.
+ * mask:      mask (B, R, R) bytes 0 / 1: level > cut[b]; cut (B) int32 on the device (255: an empty mask).
+ * label:     8-connected components.  labels (B, R, R) int32: -1 on background, otherwise the smallest linear index row * R + col of
+ *            the pixel's component.  stats (B, 4) int32 { area: foreground pixels, components: those of at least min_size pixels
+ *            (min_size >= 1), largest: pixels of the largest component, kept_area: pixels in the counted components }.
+ *            kept_or_null (B, R, R) bytes: the mask restricted to the counted components; labels and stats are the same bits with
+ *            and without it.  workspace: ngan_morph_workspace_bytes(B, R) bytes (0 for an unsupported shape).
+ * boxcount:  counts (B, log2 R + 1) int32, overwritten: counts[b][k] = aligned 2^k x 2^k boxes holding a foreground (non-zero) pixel;
+ *            counts[b][0] is the area, counts[b][log2 R] is 0 or 1. */
+size_t ngan_morph_workspace_bytes(int B, int R);
+int ngan_morph_levels(const float* images, unsigned char* levels, unsigned int* hist, int B, int R, int C, void* stream);
+int ngan_morph_mask(const unsigned char* levels, const int* cut, unsigned char* mask, int B, int R, void* stream);
+int ngan_morph_label(const unsigned char* mask, int* labels, int* stats, unsigned char* kept_or_null, void* workspace, int B, int R,
+                     int min_size, void* stream);
+int ngan_morph_boxcount(const unsigned char* mask, int* counts, int B, int R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,11 @@ SIGNATURES = {
     "ngan_diffaug_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     # radial power spectrum (include/ngan.h, last section; metrics.py)
     "ngan_spectrum_radial": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    # arbor morphology (include/ngan.h, last section; metrics.py)
+    "ngan_morph_levels": [_P, _P, _P, _I, _I, _I, _P],
+    "ngan_morph_mask": [_P, _P, _P, _I, _I, _P],
+    "ngan_morph_label": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "ngan_morph_boxcount": [_P, _P, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -157,6 +162,7 @@ NON_STATUS = {
     "ngan_spectrum_window": ([_P, _I], _I),
     "ngan_spectrum_ring_counts": ([_P, _I], _I),
     "ngan_spectrum_workspace_bytes": ([_I, _I, _I], _Z),
+    "ngan_morph_workspace_bytes": ([_I, _I], _Z),
 }
 
 _lib = None

@@ -16,7 +16,9 @@ The directory name carries a hyphen, so it is loaded under the module name `neur
     data.py            device-resident dataset with the reference's augmentation chain as one launch per batch
     metrics.py         sample quality: sliced Wasserstein distance on Laplacian-pyramid patches (csrc/swd.hip), `evaluate_swd`;
                        sample diversity: MS-SSIM between pairs of samples (csrc/msssim.hip), `evaluate_msssim`;
-                       spectral fidelity: radial power spectrum of samples against the data (csrc/spectrum.hip), `evaluate_spectrum`
+                       spectral fidelity: radial power spectrum of samples against the data (csrc/spectrum.hip), `evaluate_spectrum`;
+                       arbor morphology: connected components and box-counting dimension of the thresholded image (csrc/morph.hip),
+                       `evaluate_morphology`
     workmodel.py       algorithmic FLOP / byte model of an iteration (what bench.py's roofline figures divide by)
 """
 from . import _C, launch, ops, wgan_ops, utils, models, loss_functions, train, data, workmodel, metrics, eval  # noqa: F401, A004

@@ -21,7 +21,18 @@ Spectral fidelity: the radial power spectrum of samples against the data's (Dura
 fall short at the high-frequency end, which is where this data keeps its noise texture) -- kernels of csrc/spectrum.hip:
 
     radial_spectrum / power_spectrum           per image the ring means of |F|^2 of the (Hann-windowed) image; the half-plane power
-    Spectrum, evaluate_spectrum                accumulation over minibatches of both sets; per-bin ratio in dB, distance_db, high_db"""
+    Spectrum, evaluate_spectrum                accumulation over minibatches of both sets; per-bin ratio in dB, distance_db, high_db
+
+Arbor morphology, the statistics people take from these micrographs: is the dendrite one connected tree, how much of the field does it
+cover, how does it fill space across scales -- integer kernels of csrc/morph.hip on the image thresholded at the data loader's own
+multi-Otsu level (csrc/dataset.hip):
+
+    morph_levels / morph_mask                  8-bit levels with their histogram; the mask level > cut
+    connected_components                       8-connected labels (smallest pixel index of the component), {area, components, largest,
+                                               kept_area}, the mask of the components of at least min_size pixels
+    box_counts / box_dimension                 occupied aligned boxes of side 1, 2, ..., R; the least-squares slope over 1 .. R/4
+    arbor_statistics                           per image: fill, components, largest_share, dimension, scored
+    Morphology, evaluate_morphology            per-image values of both sets; means, standard errors and the Kolmogorov-Smirnov distance"""
 import math
 
 import torch
@@ -707,6 +718,269 @@ def format_spectrum(result, title="Radial power spectrum"):
     num = lambda v: "-" if v is None else f"{v:.2f}"   # noqa: E731
     rows.append(f"distance_db {num(result['distance_db'])}   high_db {num(result['high_db'])}"
                 + (f"   ({result['skipped_bins']} bins without power left out)" if result["skipped_bins"] else ""))
+    return "\n".join(rows)
+
+
+# ---- arbor morphology: connectivity and box-counting dimension (csrc/morph.hip; include/ngan.h, last section) ---------------------------
+MORPH_MIN, MORPH_MAX = 16, 1024              # image sizes the kernels take
+MORPH_STATISTICS = ("fill", "components", "largest_share", "dimension")
+
+
+def _square_bytes(t, what):
+    if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.uint8 and t.shape[1] == t.shape[2] and t.shape[0] > 0):
+        raise TypeError(f"{what}: expected a uint8 tensor (B, R, R) with B >= 1")
+    return t.contiguous()
+
+
+def morph_levels(images):
+    """(levels, hist): the 8-bit level of every pixel of channels-last fp32 images (B, R, R, C) in [-1, 1] -- trunc(clamp(fmaf(g, 127.5,
+    128), 0, 255)) with g the pixel or, for C = 3, (x0 + x1 + x2) * (1 / 3) in fp32 -- as (B, R, R) uint8, and their (B, 256) int32
+    histograms"""
+    x = _images(images)
+    b, r, r2, c = x.shape
+    if r != r2 or b == 0:
+        raise ValueError(f"square images (B, R, R, C) with B >= 1 expected, got {tuple(x.shape)}")
+    levels = torch.empty(b, r, r, device=x.device, dtype=torch.uint8)
+    hist = torch.empty(b, 256, device=x.device, dtype=torch.int32)
+    _C.call("ngan_morph_levels", x, levels, hist, b, r, c)
+    return levels, hist
+
+
+def otsu_thresholds(hist):
+    """(thresholds (B, 3) int32, status (B) int32) of (B, 256) int32 histograms: the data loader's 4-class multi-Otsu search
+    (ngan_multiotsu4_noise_stats); status 0 ok, otherwise the thresholds are zeros"""
+    n = hist.shape[0]
+    dev = hist.device
+    ws = torch.empty(_C.lib().ngan_multiotsu_workspace_bytes(n), device=dev, dtype=torch.uint8)
+    thresholds = torch.empty(n, 3, device=dev, dtype=torch.int32)
+    record = torch.empty(n, 3, device=dev, dtype=torch.float64)
+    status = torch.empty(n, device=dev, dtype=torch.int32)
+    _C.call("ngan_multiotsu4_noise_stats", hist.contiguous(), ws, thresholds, record, status, n)
+    return thresholds, status
+
+
+def morph_mask(levels, cut):
+    """(B, R, R) uint8 0 / 1: level > cut; cut one level for all images or a (B) integer tensor (255: an empty mask)"""
+    levels = _square_bytes(levels, "levels")
+    b, r, _ = levels.shape
+    if not isinstance(cut, torch.Tensor):
+        cut = torch.full((b,), int(cut), dtype=torch.int32)
+    if cut.numel() != b:
+        raise ValueError(f"cut must hold one level per image ({b}), got {tuple(cut.shape)}")
+    cut = cut.to(device=levels.device, dtype=torch.int32).contiguous()
+    mask = torch.empty_like(levels)
+    _C.call("ngan_morph_mask", levels, cut, mask, b, r)
+    return mask
+
+
+def connected_components(mask, min_size=1, want_kept=True):
+    """(labels, stats, kept) of (B, R, R) uint8 masks (non-zero: foreground) under 8-connectivity.  labels (B, R, R) int32: -1 on the
+    background, otherwise the smallest linear index row * R + col of the pixel's component.  stats (B, 4) int32: {area, components of
+    at least min_size pixels, pixels of the largest component, pixels in the counted components}.  kept (B, R, R) uint8: the mask
+    restricted to the counted components (None with want_kept=False; labels and stats are the same bits either way)."""
+    mask = _square_bytes(mask, "mask")
+    b, r, _ = mask.shape
+    labels = torch.empty(b, r, r, device=mask.device, dtype=torch.int32)
+    stats = torch.empty(b, 4, device=mask.device, dtype=torch.int32)
+    kept = torch.empty_like(mask) if want_kept else None
+    ws = torch.empty(max(1, _C.lib().ngan_morph_workspace_bytes(b, r) // 4), device=mask.device, dtype=torch.int32)
+    _C.call("ngan_morph_label", mask, labels, stats, kept, ws, b, r, int(min_size))
+    return labels, stats, kept
+
+
+def box_counts(mask):
+    """(B, log2 R + 1) int32: the number of aligned 2^k x 2^k boxes that hold a foreground pixel, k = 0 (the area) .. log2 R (0 or 1)"""
+    mask = _square_bytes(mask, "mask")
+    b, r, _ = mask.shape
+    counts = torch.empty(b, max(r.bit_length(), 1), device=mask.device, dtype=torch.int32)
+    _C.call("ngan_morph_boxcount", mask, counts, b, r)
+    return counts
+
+
+def box_dimension(counts, R):
+    """(B) fp64: the box-counting dimension, the least-squares slope of ln N(s) against ln(1 / s) over the box sides s = 1, 2, ...,
+    R / 4, in closed form from the integer counts of `box_counts`; NaN for an empty mask"""
+    n = int(R).bit_length() - 2                      # sides 2^0 .. 2^(n-1) = R / 4
+    if n < 2 or counts.dim() != 2 or counts.shape[1] < n:
+        raise ValueError(f"R={R} with counts {tuple(counts.shape)}: at least two box sides up to R / 4 are needed")
+    c = counts[:, :n].to(torch.float64)
+    y = torch.where(c > 0, c, torch.full_like(c, float("nan"))).log()
+    x = -math.log(2.0) * torch.arange(n, device=counts.device, dtype=torch.float64)
+    xc = x - x.mean()
+    return (y * xc).sum(1) / (xc * xc).sum()
+
+
+def arbor_statistics(images, otsu_class=1, min_size=1, threshold=None):
+    """Per-image morphology of channels-last fp32 images (B, R, R, C) in [-1, 1], fp64 tensors on the device (no host read-back):
+    the foreground is level > t, t the upper end of multi-Otsu class otsu_class - 1 of the image's own histogram (otsu_class=1: above
+    t0, the data loader's signal / noise split) or the fixed level `threshold`; components below min_size pixels are dropped.
+        fill            kept pixels / R^2                         components      counted components
+        largest_share   largest component / kept pixels           dimension       box-counting dimension of the kept mask
+        scored          False where the threshold search failed (fewer than four grey levels, no noise floor) or nothing is kept:
+                        the other four are then not to be used (fill 0, the ratios NaN)"""
+    if otsu_class not in (1, 2, 3):
+        raise ValueError(f"otsu_class={otsu_class}: 1, 2 or 3 (the classes above t0, t1, t2)")
+    if int(min_size) < 1:
+        raise ValueError(f"min_size={min_size} must be at least 1")
+    levels, hist = morph_levels(images)
+    b, r, _ = levels.shape
+    if threshold is None:
+        thresholds, status = otsu_thresholds(hist)
+        ok = status == 0
+        cut = torch.where(ok, thresholds[:, otsu_class - 1], torch.full_like(status, 255))
+    else:
+        if not 0 <= int(threshold) <= 255:
+            raise ValueError(f"threshold={threshold}: a level in 0 .. 255")
+        cut = torch.full((b,), int(threshold), device=levels.device, dtype=torch.int32)
+        ok = torch.ones(b, device=levels.device, dtype=torch.bool)
+    mask = morph_mask(levels, cut)
+    _, stats, kept = connected_components(mask, min_size)
+    counts = box_counts(kept)
+    s = stats.to(torch.float64)
+    return {"fill": s[:, 3] / float(r * r), "components": s[:, 1], "largest_share": s[:, 2] / s[:, 3],
+            "dimension": box_dimension(counts, r), "scored": ok & (stats[:, 3] > 0)}
+
+
+def ks_distance(a, b):
+    """two-sample Kolmogorov-Smirnov distance sup |F_a - F_b| of two 1-d fp64 tensors, by sorting"""
+    a, b = a.to(torch.float64).sort().values, b.to(torch.float64).sort().values
+    at = torch.cat([a, b])
+    fa = torch.searchsorted(a, at, right=True).to(torch.float64) / a.numel()
+    fb = torch.searchsorted(b, at, right=True).to(torch.float64) / b.numel()
+    return float((fa - fb).abs().max())
+
+
+class Morphology:
+    """Collects the per-image arbor statistics of real and generated images and compares their distributions.
+
+        m = Morphology(image_size=64); m.feed('real', x); m.feed('fake', G(z)); m.result()
+
+    A stage below 16 x 16 has nothing to label: feed() does nothing and result() says so."""
+
+    def __init__(self, image_size, n_colors=1, otsu_class=1, min_size=1, device="cuda"):
+        if n_colors not in (1, 3):
+            raise ValueError(f"n_colors={n_colors}: 1 or 3")
+        if image_size < 1 or image_size & (image_size - 1):
+            raise ValueError(f"image_size={image_size} must be a power of two")
+        if image_size > MORPH_MAX:
+            raise ValueError(f"image_size={image_size}: the kernels take up to {MORPH_MAX} x {MORPH_MAX}")
+        if otsu_class not in (1, 2, 3):
+            raise ValueError(f"otsu_class={otsu_class}: 1, 2 or 3")
+        if isinstance(min_size, bool) or int(min_size) != min_size or min_size < 1:
+            raise ValueError(f"min_size={min_size!r} must be an integer >= 1")
+        self.image_size, self.n_colors, self.otsu_class, self.min_size = int(image_size), int(n_colors), int(otsu_class), int(min_size)
+        self.device = torch.device(device)
+        self.active = self.image_size >= MORPH_MIN
+        self.count = {"real": 0, "fake": 0}
+        self.values = {"real": [], "fake": []}        # per feed a (5, b) fp64 tensor: the four statistics and `scored`
+
+    def feed(self, which, images):
+        if which not in self.count:
+            raise ValueError(f"which={which!r}: 'real' or 'fake'")
+        x = channels_last(images.to(self.device))
+        if tuple(x.shape[1:]) != (self.image_size, self.image_size, self.n_colors):
+            raise ValueError(f"images must be {self.image_size} pixels wide with {self.n_colors} colours, got {tuple(images.shape)}")
+        if not self.active:
+            return
+        s = arbor_statistics(x, self.otsu_class, self.min_size)
+        self.values[which].append(torch.stack([s[name] for name in MORPH_STATISTICS] + [s["scored"].to(torch.float64)]))
+        self.count[which] += x.shape[0]
+
+    def result(self):
+        """{'fill' | 'components' | 'largest_share' | 'dimension': {'real', 'real_sem', 'fake', 'fake_sem': mean and its standard
+        error over the scored images of a side (None for one image), 'ks': the two-sample Kolmogorov-Smirnov distance of the
+        per-image values}, 'images': n fed per side, 'skipped_real', 'skipped_fake': images not scored}; when a side has no scored
+        image, or the stage is below 16 x 16: no statistic and a 'note'"""
+        if not self.active:
+            return {"images": 0, "skipped_real": 0, "skipped_fake": 0,
+                    "note": f"{self.image_size} x {self.image_size} images are below {MORPH_MIN} x {MORPH_MIN}: nothing to label"}
+        n = self.count["real"]
+        if n == 0 or n != self.count["fake"]:
+            raise ValueError(f"{n} real and {self.count['fake']} generated images; feed both sets equally")
+        side = {}
+        for which in ("real", "fake"):
+            v = torch.cat(self.values[which], dim=1).cpu()
+            side[which] = v[:4][:, v[4] > 0.5]
+        out = {"images": n, "skipped_real": n - side["real"].shape[1], "skipped_fake": n - side["fake"].shape[1]}
+        if side["real"].shape[1] == 0 or side["fake"].shape[1] == 0:
+            out["note"] = "no scored image on the {} side: every image there lacks four grey levels, a noise floor or a kept pixel".format(
+                "data" if side["real"].shape[1] == 0 else "generated")
+            return out
+        for i, name in enumerate(MORPH_STATISTICS):
+            row = {"ks": ks_distance(side["real"][i], side["fake"][i])}
+            for which in ("real", "fake"):
+                v = side[which][i]
+                row[which] = float(v.mean())
+                row[which + "_sem"] = float(v.std(unbiased=True)) / math.sqrt(v.numel()) if v.numel() > 1 else None
+            out[name] = row
+        return out
+
+
+def evaluate_morphology(generator, dataset, n_images=8192, batch_size=64, seed=0, otsu_class=1, min_size=1, real_from=None,
+                        return_metric=False):
+    """The arbor statistics of `generator`'s samples against `dataset`'s images at the generator's current resolution, built like
+    evaluate_spectrum: n_images reals through the data set's own augmentation chain (its indices cycled, its generator swapped for a
+    private one seeded seed + 1 and its image size set for the duration, both restored afterwards), n_images fakes under no_grad from
+    latents of the sampler's distribution drawn from a private generator seeded seed + 2; one minibatch of images per side alive at
+    a time; torch's global and device generators are never consumed.
+    real_from: a Morphology that an earlier call returned (return_metric=True: the call then returns (result, metric)) with the same
+    settings -- its data side is taken over instead of being computed again, and `dataset` is not touched (it may be None)."""
+    device = next(generator.parameters()).device
+    size = int(generator.image_size)
+    metric = Morphology(size, n_colors=int(getattr(generator, "N_colors", 1)), otsu_class=otsu_class, min_size=min_size, device=device)
+    if not metric.active:
+        return (metric.result(), metric) if return_metric else metric.result()
+    if real_from is not None:
+        if (real_from.image_size, real_from.n_colors, real_from.otsu_class, real_from.min_size, real_from.count["real"]) != \
+                (metric.image_size, metric.n_colors, metric.otsu_class, metric.min_size, int(n_images)):
+            raise ValueError("real_from was fed with other settings")
+        metric.count["real"], metric.values["real"] = real_from.count["real"], list(real_from.values["real"])
+    n_images, batch_size = int(n_images), int(batch_size)
+    if n_images < 1 or batch_size < 1:
+        raise ValueError(f"n_images={n_images} and batch_size={batch_size} must be positive")
+    aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
+    lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
+    if real_from is None:
+        old_size = dataset.image_size
+        own_gen = getattr(dataset, "gen", None)
+        dataset.set_image_size(size)
+        if own_gen is not None:
+            dataset.gen = aug
+    try:
+        for i in range(0, n_images, batch_size):
+            b = min(batch_size, n_images - i)
+            if real_from is None:
+                idx = [(i + j) % len(dataset) for j in range(b)]
+                if hasattr(dataset, "batch"):
+                    reals = dataset.batch(idx)
+                else:
+                    reals = torch.stack([dataset[j] for j in idx]).to(device)
+                metric.feed("real", reals)
+                del reals
+            z = torch.randn(b, generator.latent_dim, generator=lat).clamp(-5, 5)
+            z = (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
+            with torch.no_grad():
+                fakes = generator(z).detach()
+            metric.feed("fake", fakes)
+            del fakes
+    finally:
+        if real_from is None:
+            if own_gen is not None:
+                dataset.gen = own_gen
+            dataset.set_image_size(old_size)
+    return (metric.result(), metric) if return_metric else metric.result()
+
+
+def format_morphology(result, title="Arbor morphology"):
+    """the table eval.py prints: one row per statistic -- data, generated (mean +- standard error) and the KS distance"""
+    if "fill" not in result:
+        return f"{title}: {result['note']}"
+    pm = lambda v, e: f"{v:10.4f} +- {e:8.4f}" if e is not None else f"{v:10.4f}" + " " * 12   # noqa: E731
+    rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
+            f"{result['skipped_fake']} generated)", f"{'':>14s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
+    for name in MORPH_STATISTICS:
+        r = result[name]
+        rows.append(f"{name:>14s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
     return "\n".join(rows)
 
 

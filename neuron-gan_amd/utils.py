@@ -48,7 +48,9 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # dictionaries, models.py the state dictionaries).  A run that scores its checkpoints (train.py, `swd_period`) adds 'SWD': a list of
 # {epoch, image_size, levels, swd, swd_ema} -- plain Python numbers and lists, which the weights-only unpickler accepts as it is.
 # Likewise `msssim_period` adds 'MSSSIM': a list of {epoch, image_size, scales, fake, fake_ema, real, pairs}, and `spectrum_period`
-# adds 'SPECTRUM': a list of {epoch, image_size, images, k, real, fake, ratio_db, distance_db, high_db[, distance_db_ema, high_db_ema]}.
+# adds 'SPECTRUM': a list of {epoch, image_size, images, k, real, fake, ratio_db, distance_db, high_db[, distance_db_ema, high_db_ema]},
+# and `morph_period` adds 'MORPH': a list of {epoch, image_size, images, min_size, skipped_real, skipped_fake[, note], fill, components,
+# largest_share, dimension: {real, real_sem, fake, fake_sem, ks}[, skipped_fake_ema, <statistic>_ema: {fake, fake_sem, ks}]}.
 # ---------------------------------------------------------------------------------------------------------------------
 import os  # noqa: E402
 
@@ -92,6 +94,7 @@ EMA_KEY = 'Generator_ema_state'
 SWD_KEY = 'SWD'
 MSSSIM_KEY = 'MSSSIM'
 SPECTRUM_KEY = 'SPECTRUM'
+MORPH_KEY = 'MORPH'
 
 
 class Checkpointer:
@@ -113,6 +116,7 @@ class Checkpointer:
         self.SWD = []               # one entry per scored checkpoint (train.py, `swd_period`); saved only when it holds any
         self.MSSSIM = []            # the same for `msssim_period`
         self.SPECTRUM = []          # the same for `spectrum_period`
+        self.MORPH = []             # the same for `morph_period`
 
     def save_state(self, epoch):
         self.epoch = epoch
@@ -137,6 +141,8 @@ class Checkpointer:
             checkpoint_dict[MSSSIM_KEY] = [dict(entry) for entry in self.MSSSIM]
         if self.SPECTRUM:
             checkpoint_dict[SPECTRUM_KEY] = [dict(entry) for entry in self.SPECTRUM]
+        if self.MORPH:
+            checkpoint_dict[MORPH_KEY] = [dict(entry) for entry in self.MORPH]
         torch.save(checkpoint_dict, self.filename)
         if epoch % self.extra_checkpoint_period == 0:
             base, ext = os.path.splitext(self.filename)
@@ -159,6 +165,7 @@ class Checkpointer:
             self.SWD = [dict(entry) for entry in checkpoint_dict.get(SWD_KEY, [])]      # a resumed run continues the list
             self.MSSSIM = [dict(entry) for entry in checkpoint_dict.get(MSSSIM_KEY, [])]
             self.SPECTRUM = [dict(entry) for entry in checkpoint_dict.get(SPECTRUM_KEY, [])]
+            self.MORPH = [dict(entry) for entry in checkpoint_dict.get(MORPH_KEY, [])]
         if 'Generator_attrs' in checkpoint_dict and 'Discriminator_attrs' in checkpoint_dict:
             # (the WGAN nets list no saved_attrs: the reference fails there, utils.py:194-198; here they count as empty)
             gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in getattr(self.Generator_net, 'saved_attrs', [])}
