@@ -697,6 +697,31 @@ int ngan_morph_label(const unsigned char* mask, int* labels, int* stats, unsigne
                      int min_size, void* stream);
 int ngan_morph_boxcount(const unsigned char* mask, int* counts, int B, int R, void* stream);
 
+/* ---- arbor skeleton: thinning, tips, junctions and length of a mask (an addition of this implementation, off by default;
+ * neuron-gan_amd/metrics.py drives it) ------------------------------------------------------------------------------
+ * Masks are (B, R, R) bytes, any non-zero byte is foreground; R a power of two in 16 .. 512 (the bit rows of an image, 32 KiB at 512,
+ * stay in one workgroup's LDS; 1024 is refused), 1 <= B <= 65535 (NGAN_ERR_SHAPE otherwise).  One workgroup per image, integers only,
+ * no atomics: every output is bit-reproducible, and an image's values do not depend on the rest of the batch.  mask and skeleton start
+ * on a 16-byte boundary, stats on a 4-byte one (NGAN_ERR_ARG otherwise, as for a null mask or stats); a refused call writes nothing.
+ * Pixels outside the image are background.  The neighbours of a pixel P are named clockwise from north: P2 N (y-1, x), P3 NE, P4 E,
+ * P5 SE, P6 S, P7 SW, P8 W, P9 NW.
+ * thinning:  Guo and Hall 1989, algorithm A1.  With
+ *                C  = [!P2 & (P3|P4)] + [!P4 & (P5|P6)] + [!P6 & (P7|P8)] + [!P8 & (P9|P2)]
+ *                N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8),  N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9),  N = min(N1, N2)
+ *            a foreground pixel is deleted in a sub-iteration when C == 1, 2 <= N <= 3 and, in sub-iteration 0, (P2|P3|!P5) & P4 == 0,
+ *            in sub-iteration 1, (P6|P7|!P9) & P8 == 0; every deletion of a sub-iteration is decided on the state before it.
+ *            Sub-iterations 0 and 1 alternate; the loop stops after the first pair in which neither deleted a pixel.  `passes` counts
+ *            the sub-iterations run, that last pair included: it is even, and 2 for an already thin mask.
+ * counts:    on any mask, with B the number of set neighbours and X the number of 0 -> 1 steps round the ring P2, P3, ..., P9, P2:
+ *            pixels (set pixels), tips (X == 1 and B <= 2), junctions (X >= 3), isolated (B == 0), orth (pairs of set pixels that are
+ *            horizontal or vertical neighbours), diag (pairs of set diagonal neighbours for which neither of the two pixels 4-adjacent
+ *            to both is set: a staircase corner is not counted twice).  The length of a skeleton is orth + sqrt(2) diag pixels.
+ * skel_thin:   skeleton_or_null (B, R, R) bytes 0 / 1; stats (B, 8) int32, overwritten: { pixels, tips, junctions, isolated, orth,
+ *              diag: of the skeleton; passes; area: the mask's foreground pixels }; the same stats with and without the skeleton.
+ * skel_counts: the six counts of the mask as it is; passes is 0 and area equals pixels. */
+int ngan_skel_thin(const unsigned char* mask, unsigned char* skeleton_or_null, int* stats, int B, int R, void* stream);
+int ngan_skel_counts(const unsigned char* mask, int* stats, int B, int R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,9 @@ SIGNATURES = {
     "ngan_morph_mask": [_P, _P, _P, _I, _I, _P],
     "ngan_morph_label": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "ngan_morph_boxcount": [_P, _P, _I, _I, _P],
+    # arbor skeleton (include/ngan.h, last section; metrics.py)
+    "ngan_skel_thin": [_P, _P, _P, _I, _I, _P],
+    "ngan_skel_counts": [_P, _P, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments

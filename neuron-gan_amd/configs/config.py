@@ -33,6 +33,7 @@ _DEFAULTS = dict(
     msssim_period=0, msssim_pairs=10000, msssim_seed=0,
     spectrum_period=0, spectrum_images=8192, spectrum_seed=0,
     morph_period=0, morph_images=8192, morph_seed=0, morph_min_size=1,
+    skeleton_period=0, skeleton_images=8192, skeleton_seed=0, skeleton_min_size=1,
     diffaug='', diffaug_p=1.0, diffaug_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
@@ -112,6 +113,11 @@ def validate_configs(create_dirs=False):
     # implementation), with the same meaning: morph_period 0 is off, otherwise every checkpoint whose epoch is a multiple of it is scored
     # on morph_images images per side; components below morph_min_size pixels are dropped (1 drops none)
     for name, lowest in (('morph_period', 0), ('morph_images', 1), ('morph_seed', 0), ('morph_min_size', 1)):
+        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
+            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
+    # arbor skeleton (thinning: length, tips, junctions, width) of samples against the data at checkpoints (an addition of this
+    # implementation), with the same meaning as the morph_* names; stages above 512 x 512 are noted, not scored
+    for name, lowest in (('skeleton_period', 0), ('skeleton_images', 1), ('skeleton_seed', 0), ('skeleton_min_size', 1)):
         if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
             raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
     # differentiable augmentation of the critic's inputs (an addition of this implementation): diffaug '' is off, otherwise a comma

@@ -32,7 +32,15 @@ multi-Otsu level (csrc/dataset.hip):
                                                kept_area}, the mask of the components of at least min_size pixels
     box_counts / box_dimension                 occupied aligned boxes of side 1, 2, ..., R; the least-squares slope over 1 .. R/4
     arbor_statistics                           per image: fill, components, largest_share, dimension, scored
-    Morphology, evaluate_morphology            per-image values of both sets; means, standard errors and the Kolmogorov-Smirnov distance"""
+    Morphology, evaluate_morphology            per-image values of both sets; means, standard errors and the Kolmogorov-Smirnov distance
+
+Arbor skeleton, what a neuroscientist reads off an arbor -- how much cable, how many endings and branch points, how thick the
+processes are -- on the same kept mask, thinned in one launch of csrc/skeleton.hip (Guo and Hall 1989, the whole iteration in LDS):
+
+    thin / skeleton_counts                     the skeleton and {pixels, tips, junctions, isolated, orth, diag, passes, area}; the
+                                               six counts of any mask
+    skeleton_statistics                        per image: length, tips, junctions, width, scored
+    Skeleton, evaluate_skeleton                per-image values of both sets, summarised as Morphology does"""
 import math
 
 import torch
@@ -810,14 +818,9 @@ def box_dimension(counts, R):
     return (y * xc).sum(1) / (xc * xc).sum()
 
 
-def arbor_statistics(images, otsu_class=1, min_size=1, threshold=None):
-    """Per-image morphology of channels-last fp32 images (B, R, R, C) in [-1, 1], fp64 tensors on the device (no host read-back):
-    the foreground is level > t, t the upper end of multi-Otsu class otsu_class - 1 of the image's own histogram (otsu_class=1: above
-    t0, the data loader's signal / noise split) or the fixed level `threshold`; components below min_size pixels are dropped.
-        fill            kept pixels / R^2                         components      counted components
-        largest_share   largest component / kept pixels           dimension       box-counting dimension of the kept mask
-        scored          False where the threshold search failed (fewer than four grey levels, no noise floor) or nothing is kept:
-                        the other four are then not to be used (fill 0, the ratios NaN)"""
+def _kept_mask(images, otsu_class, min_size, threshold):
+    """the front end arbor_statistics and skeleton_statistics share: levels -> cut -> mask -> components -> kept mask.  Returns
+    (R, ok (B) bool: the threshold search succeeded, stats (B, 4) int32 of connected_components, kept (B, R, R) uint8)"""
     if otsu_class not in (1, 2, 3):
         raise ValueError(f"otsu_class={otsu_class}: 1, 2 or 3 (the classes above t0, t1, t2)")
     if int(min_size) < 1:
@@ -835,6 +838,18 @@ def arbor_statistics(images, otsu_class=1, min_size=1, threshold=None):
         ok = torch.ones(b, device=levels.device, dtype=torch.bool)
     mask = morph_mask(levels, cut)
     _, stats, kept = connected_components(mask, min_size)
+    return r, ok, stats, kept
+
+
+def arbor_statistics(images, otsu_class=1, min_size=1, threshold=None):
+    """Per-image morphology of channels-last fp32 images (B, R, R, C) in [-1, 1], fp64 tensors on the device (no host read-back):
+    the foreground is level > t, t the upper end of multi-Otsu class otsu_class - 1 of the image's own histogram (otsu_class=1: above
+    t0, the data loader's signal / noise split) or the fixed level `threshold`; components below min_size pixels are dropped.
+        fill            kept pixels / R^2                         components      counted components
+        largest_share   largest component / kept pixels           dimension       box-counting dimension of the kept mask
+        scored          False where the threshold search failed (fewer than four grey levels, no noise floor) or nothing is kept:
+                        the other four are then not to be used (fill 0, the ratios NaN)"""
+    r, ok, stats, kept = _kept_mask(images, otsu_class, min_size, threshold)
     counts = box_counts(kept)
     s = stats.to(torch.float64)
     return {"fill": s[:, 3] / float(r * r), "components": s[:, 1], "largest_share": s[:, 2] / s[:, 3],
@@ -856,6 +871,13 @@ class Morphology:
         m = Morphology(image_size=64); m.feed('real', x); m.feed('fake', G(z)); m.result()
 
     A stage below 16 x 16 has nothing to label: feed() does nothing and result() says so."""
+    STATISTICS = MORPH_STATISTICS
+
+    def _statistics(self, x):
+        return arbor_statistics(x, self.otsu_class, self.min_size)
+
+    def _inactive_note(self):
+        return f"{self.image_size} x {self.image_size} images are below {MORPH_MIN} x {MORPH_MIN}: nothing to label"
 
     def __init__(self, image_size, n_colors=1, otsu_class=1, min_size=1, device="cuda"):
         if n_colors not in (1, 3):
@@ -882,8 +904,8 @@ class Morphology:
             raise ValueError(f"images must be {self.image_size} pixels wide with {self.n_colors} colours, got {tuple(images.shape)}")
         if not self.active:
             return
-        s = arbor_statistics(x, self.otsu_class, self.min_size)
-        self.values[which].append(torch.stack([s[name] for name in MORPH_STATISTICS] + [s["scored"].to(torch.float64)]))
+        s = self._statistics(x)
+        self.values[which].append(torch.stack([s[name] for name in self.STATISTICS] + [s["scored"].to(torch.float64)]))
         self.count[which] += x.shape[0]
 
     def result(self):
@@ -892,8 +914,7 @@ class Morphology:
         per-image values}, 'images': n fed per side, 'skipped_real', 'skipped_fake': images not scored}; when a side has no scored
         image, or the stage is below 16 x 16: no statistic and a 'note'"""
         if not self.active:
-            return {"images": 0, "skipped_real": 0, "skipped_fake": 0,
-                    "note": f"{self.image_size} x {self.image_size} images are below {MORPH_MIN} x {MORPH_MIN}: nothing to label"}
+            return {"images": 0, "skipped_real": 0, "skipped_fake": 0, "note": self._inactive_note()}
         n = self.count["real"]
         if n == 0 or n != self.count["fake"]:
             raise ValueError(f"{n} real and {self.count['fake']} generated images; feed both sets equally")
@@ -906,7 +927,7 @@ class Morphology:
             out["note"] = "no scored image on the {} side: every image there lacks four grey levels, a noise floor or a kept pixel".format(
                 "data" if side["real"].shape[1] == 0 else "generated")
             return out
-        for i, name in enumerate(MORPH_STATISTICS):
+        for i, name in enumerate(self.STATISTICS):
             row = {"ks": ks_distance(side["real"][i], side["fake"][i])}
             for which in ("real", "fake"):
                 v = side[which][i]
@@ -925,9 +946,14 @@ def evaluate_morphology(generator, dataset, n_images=8192, batch_size=64, seed=0
     a time; torch's global and device generators are never consumed.
     real_from: a Morphology that an earlier call returned (return_metric=True: the call then returns (result, metric)) with the same
     settings -- its data side is taken over instead of being computed again, and `dataset` is not touched (it may be None)."""
+    return _evaluate_two_sets(Morphology, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric)
+
+
+def _evaluate_two_sets(metric_class, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric):
+    """the body of evaluate_morphology and evaluate_skeleton: metric_class is Morphology or Skeleton"""
     device = next(generator.parameters()).device
     size = int(generator.image_size)
-    metric = Morphology(size, n_colors=int(getattr(generator, "N_colors", 1)), otsu_class=otsu_class, min_size=min_size, device=device)
+    metric = metric_class(size, n_colors=int(getattr(generator, "N_colors", 1)), otsu_class=otsu_class, min_size=min_size, device=device)
     if not metric.active:
         return (metric.result(), metric) if return_metric else metric.result()
     if real_from is not None:
@@ -979,6 +1005,89 @@ def format_morphology(result, title="Arbor morphology"):
     rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
             f"{result['skipped_fake']} generated)", f"{'':>14s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
     for name in MORPH_STATISTICS:
+        r = result[name]
+        rows.append(f"{name:>14s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
+    return "\n".join(rows)
+
+
+# ---- arbor skeleton: thinning, tips, junctions and length (csrc/skeleton.hip; include/ngan.h, last section) ------------------------------
+SKEL_MAX = 512                               # the largest image whose bit rows the thinning kernel holds in one workgroup's LDS
+SKELETON_STATISTICS = ("length", "tips", "junctions", "width")
+SKEL_STATS = ("pixels", "tips", "junctions", "isolated", "orth", "diag", "passes", "area")     # the columns of `stats`
+
+
+def thin(mask, want_skeleton=True):
+    """(skeleton, stats) of (B, R, R) uint8 masks (non-zero: foreground), R a power of two in 16 .. 512: the Guo-Hall thinning of every
+    mask as (B, R, R) uint8 0 / 1 (None with want_skeleton=False; the stats are the same bits either way) and stats (B, 8) int32:
+    {pixels, tips, junctions, isolated, orth, diag} of the skeleton, the sub-iterations run, the mask's area (include/ngan.h)"""
+    mask = _square_bytes(mask, "mask")
+    b, r, _ = mask.shape
+    skeleton = torch.empty_like(mask) if want_skeleton else None
+    stats = torch.empty(b, 8, device=mask.device, dtype=torch.int32)
+    _C.call("ngan_skel_thin", mask, skeleton, stats, b, r)
+    return skeleton, stats
+
+
+def skeleton_counts(mask):
+    """(B, 8) int32: {pixels, tips, junctions, isolated, orth, diag, 0, area} of (B, R, R) uint8 masks as they are, not thinned"""
+    mask = _square_bytes(mask, "mask")
+    b, r, _ = mask.shape
+    stats = torch.empty(b, 8, device=mask.device, dtype=torch.int32)
+    _C.call("ngan_skel_counts", mask, stats, b, r)
+    return stats
+
+
+def skeleton_statistics(images, otsu_class=1, min_size=1, threshold=None):
+    """Per-image skeleton statistics of channels-last fp32 images (B, R, R, C) in [-1, 1], R up to 512, fp64 tensors on the device (no
+    host read-back): the kept mask of `arbor_statistics` (same otsu_class, min_size, threshold) is thinned, and
+        length      (orth + sqrt(2) diag) / R: skeleton length in image widths    tips        skeleton pixels with one neighbour run
+        width       kept pixels / skeleton pixels: the mean thickness             junctions   skeleton pixels where three or more meet
+        scored      as in arbor_statistics, and False when the skeleton is empty: the others are then not to be used"""
+    r, ok, stats, kept = _kept_mask(images, otsu_class, min_size, threshold)
+    _, sk = thin(kept, want_skeleton=False)
+    s, k = sk.to(torch.float64), stats.to(torch.float64)
+    return {"length": (s[:, 4] + math.sqrt(2.0) * s[:, 5]) / float(r), "tips": s[:, 1], "junctions": s[:, 2], "width": k[:, 3] / s[:, 0],
+            "scored": ok & (stats[:, 3] > 0) & (sk[:, 0] > 0)}
+
+
+class Skeleton(Morphology):
+    """Collects the per-image skeleton statistics of real and generated images and compares their distributions, as Morphology does:
+
+        m = Skeleton(image_size=64); m.feed('real', x); m.feed('fake', G(z)); m.result()
+
+    A stage below 16 x 16 has nothing to thin and one above 512 x 512 does not fit the kernel: feed() does nothing and result() says so."""
+    STATISTICS = SKELETON_STATISTICS
+
+    def __init__(self, image_size, n_colors=1, otsu_class=1, min_size=1, device="cuda"):
+        super().__init__(image_size, n_colors=n_colors, otsu_class=otsu_class, min_size=min_size, device=device)
+        self.active = MORPH_MIN <= self.image_size <= SKEL_MAX
+
+    def _statistics(self, x):
+        return skeleton_statistics(x, self.otsu_class, self.min_size)
+
+    def _inactive_note(self):
+        if self.image_size > SKEL_MAX:
+            return f"{self.image_size} x {self.image_size} images are above {SKEL_MAX} x {SKEL_MAX}: the thinning kernel does not take them"
+        return f"{self.image_size} x {self.image_size} images are below {MORPH_MIN} x {MORPH_MIN}: nothing to thin"
+
+
+def evaluate_skeleton(generator, dataset, n_images=8192, batch_size=64, seed=0, otsu_class=1, min_size=1, real_from=None,
+                      return_metric=False):
+    """The skeleton statistics of `generator`'s samples against `dataset`'s images at the generator's current resolution, with the
+    contract of evaluate_morphology: private generators seeded seed + 1 (augmentation) and seed + 2 (latents), the data set's generator
+    and image size restored afterwards, torch's global and device generators never consumed; real_from: a Skeleton that an earlier
+    call returned (return_metric=True) with the same settings, whose data side is taken over."""
+    return _evaluate_two_sets(Skeleton, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric)
+
+
+def format_skeleton(result, title="Arbor skeleton"):
+    """the table eval.py prints: one row per statistic -- data, generated (mean +- standard error) and the KS distance"""
+    if "length" not in result:
+        return f"{title}: {result['note']}"
+    pm = lambda v, e: f"{v:10.4f} +- {e:8.4f}" if e is not None else f"{v:10.4f}" + " " * 12   # noqa: E731
+    rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
+            f"{result['skipped_fake']} generated)", f"{'':>14s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
+    for name in SKELETON_STATISTICS:
         r = result[name]
         rows.append(f"{name:>14s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
     return "\n".join(rows)

@@ -1629,6 +1629,43 @@ def score_morph(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
     return entry
 
 
+def score_skeleton(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
+    """One arbor-skeleton evaluation (metrics.evaluate_skeleton with cfg.skeleton_images images per side in minibatches of
+    cfg.batch_size, seed cfg.skeleton_seed, components below cfg.skeleton_min_size pixels dropped) of the training generator against
+    the data set and, when the trainer averages, of the averaged one: logged in one line and appended to checkpoint.SKELETON as {epoch,
+    image_size, images, min_size, skipped_real, skipped_fake[, note]} plus, per statistic (length, tips, junctions, width), {real,
+    real_sem, fake, fake_sem, ks}; with an averaged generator also skipped_fake_ema and <statistic>_ema: {fake, fake_sem, ks} (the
+    data's side is the same: it is not stored twice).  Eager, outside any captured graph, no collective; it draws from private
+    generators only, so the run trains on as if it had not happened."""
+    from .metrics import SKELETON_STATISTICS, evaluate_skeleton
+    G = trainer.G
+    kw = dict(n_images=int(getattr(cfg, 'skeleton_images', 8192)), batch_size=int(cfg.batch_size),
+              seed=int(getattr(cfg, 'skeleton_seed', 0)), min_size=int(getattr(cfg, 'skeleton_min_size', 1)))
+    res, metric = evaluate_skeleton(G, dataset, return_metric=True, **kw)
+    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "min_size": kw["min_size"]}
+    entry.update({k: (dict(v) if isinstance(v, dict) else v) for k, v in res.items()})
+    if metric.active and getattr(trainer, "ema_enabled", False):
+        with trainer.averaged_generator():
+            ema = evaluate_skeleton(G, None, real_from=metric, **kw)   # (the data's side is the same: not scored twice)
+        entry["skipped_fake_ema"] = ema["skipped_fake"]
+        for name in SKELETON_STATISTICS:
+            if name in ema:
+                entry[name + "_ema"] = {k: ema[name][k] for k in ("fake", "fake_sem", "ks")}
+    if "length" not in res:
+        log("Epoch:{}, skeleton: {}".format(epoch, res["note"]))
+    else:
+        one = lambda r: "length {:.3f}, tips {:.2f} (KS {:.3f}), junctions {:.2f}, width {:.3f}".format(   # noqa: E731
+            r["length"]["fake"], r["tips"]["fake"], r["tips"]["ks"], r["junctions"]["fake"], r["width"]["fake"])
+        line = "Epoch:{}, skeleton over {} images: {}; data: length {:.3f}, tips {:.2f}, junctions {:.2f}, width {:.3f}".format(
+            epoch, res["images"], one(res), res["length"]["real"], res["tips"]["real"], res["junctions"]["real"], res["width"]["real"])
+        if "length_ema" in entry:
+            line += "; averaged generator: " + one({n: entry[n + "_ema"] for n in SKELETON_STATISTICS})
+        log(line)
+    if checkpoint is not None:
+        checkpoint.SKELETON.append(entry)
+    return entry
+
+
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
                 samples_dir=None, on_epoch=None, process_group=None, draws=None):
     """The reference's epoch loop (train.py:298-451) over a PGGANTrainer.
@@ -1646,7 +1683,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     every rank; rank 0 alone logs, saves and plots.  With one rank nothing of this is active.
     cfg.swd_period > 0: rank 0 scores every checkpoint whose epoch is a multiple of it (`score_swd`) before it is written; the other
     ranks wait at the checkpoint's barrier.  cfg.msssim_period > 0: the same with `score_msssim`; cfg.spectrum_period > 0: with `score_spectrum`;
-    cfg.morph_period > 0: with `score_morph`.
+    cfg.morph_period > 0: with `score_morph`; cfg.skeleton_period > 0: with `score_skeleton`.
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
     (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
@@ -1659,6 +1696,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     msssim_period = int(getattr(cfg, 'msssim_period', 0) or 0)
     spectrum_period = int(getattr(cfg, 'spectrum_period', 0) or 0)
     morph_period = int(getattr(cfg, 'morph_period', 0) or 0)
+    skeleton_period = int(getattr(cfg, 'skeleton_period', 0) or 0)
     G, D = trainer.G, trainer.D
     dev = trainer.device
     epoch_final = epoch_final if epoch_final is not None else cfg.N_epochs + 1
@@ -1773,6 +1811,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
                     score_spectrum(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 if morph_period > 0 and epoch % morph_period == 0:
                     score_morph(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
+                if skeleton_period > 0 and epoch % skeleton_period == 0:
+                    score_skeleton(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 checkpoint.save_state(epoch)
                 if samples_dir is not None:
                     from .utils import plot_gen_samples
@@ -1967,6 +2007,11 @@ def build_arg_parser():
     p.add_argument('--morph_images', type=int, default=8192, help='images per side of one morphology evaluation')
     p.add_argument('--morph_seed', type=int, default=0, help='seed of the morphology latents and augmentations')
     p.add_argument('--morph_min_size', type=int, default=1, help='components below this many pixels are dropped (1 drops none)')
+    p.add_argument('--skeleton_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the arbor '
+                                                                  'skeleton of samples against the data (metrics.py); 0: off')
+    p.add_argument('--skeleton_images', type=int, default=8192, help='images per side of one skeleton evaluation')
+    p.add_argument('--skeleton_seed', type=int, default=0, help='seed of the skeleton latents and augmentations')
+    p.add_argument('--skeleton_min_size', type=int, default=1, help='components below this many pixels are not thinned (1 drops none)')
     p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
                                                         'launch.py); batch_size stays the global batch')
     return p

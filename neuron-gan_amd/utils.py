@@ -50,7 +50,8 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # Likewise `msssim_period` adds 'MSSSIM': a list of {epoch, image_size, scales, fake, fake_ema, real, pairs}, and `spectrum_period`
 # adds 'SPECTRUM': a list of {epoch, image_size, images, k, real, fake, ratio_db, distance_db, high_db[, distance_db_ema, high_db_ema]},
 # and `morph_period` adds 'MORPH': a list of {epoch, image_size, images, min_size, skipped_real, skipped_fake[, note], fill, components,
-# largest_share, dimension: {real, real_sem, fake, fake_sem, ks}[, skipped_fake_ema, <statistic>_ema: {fake, fake_sem, ks}]}.
+# largest_share, dimension: {real, real_sem, fake, fake_sem, ks}[, skipped_fake_ema, <statistic>_ema: {fake, fake_sem, ks}]}, and
+# `skeleton_period` adds 'SKELETON': a list of the same shape with the statistics length, tips, junctions, width.
 # ---------------------------------------------------------------------------------------------------------------------
 import os  # noqa: E402
 
@@ -95,6 +96,7 @@ SWD_KEY = 'SWD'
 MSSSIM_KEY = 'MSSSIM'
 SPECTRUM_KEY = 'SPECTRUM'
 MORPH_KEY = 'MORPH'
+SKELETON_KEY = 'SKELETON'
 
 
 class Checkpointer:
@@ -117,6 +119,7 @@ class Checkpointer:
         self.MSSSIM = []            # the same for `msssim_period`
         self.SPECTRUM = []          # the same for `spectrum_period`
         self.MORPH = []             # the same for `morph_period`
+        self.SKELETON = []          # the same for `skeleton_period`
 
     def save_state(self, epoch):
         self.epoch = epoch
@@ -143,6 +146,8 @@ class Checkpointer:
             checkpoint_dict[SPECTRUM_KEY] = [dict(entry) for entry in self.SPECTRUM]
         if self.MORPH:
             checkpoint_dict[MORPH_KEY] = [dict(entry) for entry in self.MORPH]
+        if self.SKELETON:
+            checkpoint_dict[SKELETON_KEY] = [dict(entry) for entry in self.SKELETON]
         torch.save(checkpoint_dict, self.filename)
         if epoch % self.extra_checkpoint_period == 0:
             base, ext = os.path.splitext(self.filename)
@@ -166,6 +171,7 @@ class Checkpointer:
             self.MSSSIM = [dict(entry) for entry in checkpoint_dict.get(MSSSIM_KEY, [])]
             self.SPECTRUM = [dict(entry) for entry in checkpoint_dict.get(SPECTRUM_KEY, [])]
             self.MORPH = [dict(entry) for entry in checkpoint_dict.get(MORPH_KEY, [])]
+            self.SKELETON = [dict(entry) for entry in checkpoint_dict.get(SKELETON_KEY, [])]
         if 'Generator_attrs' in checkpoint_dict and 'Discriminator_attrs' in checkpoint_dict:
             # (the WGAN nets list no saved_attrs: the reference fails there, utils.py:194-198; here they count as empty)
             gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in getattr(self.Generator_net, 'saved_attrs', [])}
