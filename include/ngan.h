@@ -506,7 +506,10 @@ int ngan_rmsprop_step_clip(float* p, const float* g, float* v, const long* seg_o
  *     ngan_s2_wgrad_workspace_floats(...) floats.  Conv2d: half = output gradient, full = input.  ConvTranspose2d: the reverse.
  * ngan_bn_stats: batch statistics of y (npix, C): mean, rstd = 1/sqrt(biased var + eps), the on-load transform scale = gamma*rstd,
  *     shift = beta - mean*scale; run_mean / run_var (may both be null) get the momentum update with the unbiased variance; *nbt += 1
- *     (nbt may be null).  work: ngan_chan_reduce_workspace_floats(npix, C) floats.
+ *     (nbt may be null).  The sums of the pixels (shifted by the channel's first) and of their squares are formed in fp32 and in
+ *     fp64; the fp32 moments stand where the fp64 ones confirm them, so the variance does not depend on where the first pixel lies.
+ *     work: ngan_chan_reduce_workspace_floats(npix, C) floats, 8-byte aligned (fp64 and fp32 partials; the fp32 reductions use a
+ *     third of it).
  * ngan_bn_fold_eval: eval-mode BatchNorm as the on-load transform: scale = gamma/sqrt(run_var + eps), shift = beta - run_mean*scale.
  * ngan_bn_act_bwd: g is the gradient w.r.t. act(scale*y + shift); writes gy w.r.t. y.  gamma non-null: training-mode BatchNorm
  *     backward with its batch statistics (mean, rstd); dgamma / dbeta (each may be null) = sum gz*xhat, sum gz.  gamma null: only the

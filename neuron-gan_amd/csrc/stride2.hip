@@ -258,7 +258,8 @@ void wgrad_plan(int B, int Hh, int Wh, int CH, int CF, int& HB, int& FB, int& ns
 // ---------------------------------------------------------------------------------------------------------------------------------
 // per-channel reductions over an (npix, C) channels-last tensor, in two fixed-order stages.
 // Stage 1: workgroup g sums pixels [g*chunk, (g+1)*chunk); thread tid owns one channel and one pixel lane (see the kernel).
-//   mode 0 (BN statistics):   s0 = sum (y - y[0,c]),  s1 = sum (y - y[0,c])^2        (shifted by the first pixel: no cancellation)
+//   mode 0 (BN moments of the synchronised path; ngan_bn_stats has its own fp64 stage 1, bn_stats_stage1):
+//                             s0 = sum (y - y[0,c]),  s1 = sum (y - y[0,c])^2        (shifted by the first pixel)
 //   mode 1 (BN backward):     gz = g * act'(z),  z = scale*y + shift;  s0 = sum gz,  s1 = sum gz * xhat,  xhat = (y - mean) * rstd
 //   mode 2 (plain sum):       s0 = sum g
 // Partials: part[g][2][C].  Stage 2 (one thread per channel) sums the chunks in order.
@@ -325,23 +326,91 @@ __global__ __launch_bounds__(256) void chan_reduce_stage1(RedArgs a) {
     }
 }
 
+// BN statistics of the single-GPU path, stage 1: chan_reduce_stage1<0>'s partition, order and fp32 sums of d = y - y[0,c] and d^2
+// (part32[g][2][C], the same bits), and beside them the same two sums in fp64 (part[g][2][C] doubles).  The variance is
+// s1/n - (s0/n)^2, which cancels by a factor 1 + 2 (s0/n)^2 / var: in fp32 a first pixel six sigma from its channel's mean costs 73
+// roundings' worth of the variance, in fp64 nothing that an fp32 result can show.  bn_stats_finish keeps the fp32 moments where the
+// fp64 ones confirm them and takes the fp64 ones elsewhere.
+__global__ __launch_bounds__(256) void bn_stats_stage1(RedArgs a, double* __restrict__ part) {
+    __shared__ double sm[2][256];
+    __shared__ float sm32[2][256];
+    const int tid = threadIdx.x;
+    const bool split = a.C <= 256;
+    const int L = split ? 256 / a.C : 1;
+    const int CW = split ? a.C : 256;
+    const long p0 = (long)blockIdx.x * a.chunk;
+    const long p1 = min(a.npix, p0 + a.chunk);
+    for (int cbase = 0; cbase < a.C; cbase += CW) {
+        const int c = split ? tid % a.C : cbase + tid;
+        const int lane = split ? tid / a.C : 0;
+        double s0 = 0.0, s1 = 0.0;
+        float f0 = 0.f, f1 = 0.f;
+        if (c < a.C && lane < L) {
+            const float piv = a.y[c];
+            for (long pix = p0 + lane; pix < p1; pix += L) {
+                const float yv = a.y[pix * a.C + c];
+                const float df = yv - piv;
+                f0 += df;
+                f1 = fmaf(df, df, f1);
+                const double d = (double)yv - (double)piv;
+                s0 += d;
+                s1 = fma(d, d, s1);
+            }
+        }
+        sm[0][tid] = s0;
+        sm[1][tid] = s1;
+        sm32[0][tid] = f0;
+        sm32[1][tid] = f1;
+        __syncthreads();
+        if (tid < CW && cbase + tid < a.C) {
+            double t0 = 0.0, t1 = 0.0;
+            float u0 = 0.f, u1 = 0.f;
+            for (int l = 0; l < L; ++l) {       // l*C + tid < 256, as in chan_reduce_stage1
+                const int j = tid + l * (split ? a.C : 0);
+                t0 += sm[0][j];
+                t1 += sm[1][j];
+                u0 += sm32[0][j];
+                u1 += sm32[1][j];
+            }
+            const int cc = split ? tid : cbase + tid;
+            part[((long)blockIdx.x * 2 + 0) * a.C + cc] = t0;
+            part[((long)blockIdx.x * 2 + 1) * a.C + cc] = t1;
+            a.part[((long)blockIdx.x * 2 + 0) * a.C + cc] = u0;
+            a.part[((long)blockIdx.x * 2 + 1) * a.C + cc] = u1;
+        }
+        __syncthreads();
+    }
+}
+
 // BN statistics finish: mean, rstd (biased variance), (scale, shift), running-statistics update (unbiased variance, momentum),
-// num_batches_tracked += 1 (channel 0's thread)
-__global__ void bn_stats_finish(const float* __restrict__ part, int nparts, const float* __restrict__ y, long npix, int C,
-                                const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ mean,
+// num_batches_tracked += 1 (channel 0's thread).  The chunks are summed in order, in fp32 and in fp64.  The fp32 moments stand where
+// they agree with the fp64 ones (the variance within 2^-22 of it, the mean within 2^-23 of |mean| + sigma), which is everywhere the
+// first pixel is an ordinary one: there the results are, bit for bit, those of the one-pass fp32 form.  Elsewhere the fp64 moments,
+// rounded once, take their place.  Everything after the moments is fp32.
+__global__ void bn_stats_finish(const double* __restrict__ part, const float* __restrict__ part32, int nparts, const float* __restrict__ y,
+                                long npix, int C, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ mean,
                                 float* __restrict__ rstd, float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ run_mean,
                                 float* __restrict__ run_var, long long* __restrict__ nbt, float momentum, float eps) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    float s0 = 0.f, s1 = 0.f;
+    double s0 = 0.0, s1 = 0.0;
+    float f0 = 0.f, f1 = 0.f;
     for (int k = 0; k < nparts; ++k) {
         s0 += part[((long)k * 2 + 0) * C + c];
         s1 += part[((long)k * 2 + 1) * C + c];
+        f0 += part32[((long)k * 2 + 0) * C + c];
+        f1 += part32[((long)k * 2 + 1) * C + c];
     }
+    const double nd = (double)npix;
+    const double dd = s0 / nd;
+    const double var64 = fmax(s1 / nd - dd * dd, 0.0);
+    const double mu64 = (double)y[c] + dd;
     const float n = (float)npix;
-    const float d = s0 / n;
-    const float var = fmaxf(s1 / n - d * d, 0.f);
-    const float mu = y[c] + d;
+    const float d32 = f0 / n;
+    const float var32 = fmaxf(f1 / n - d32 * d32, 0.f);
+    const float mu32 = y[c] + d32;
+    const float var = fabs((double)var32 - var64) <= 0x1p-22 * var64 ? var32 : (float)var64;
+    const float mu = fabs((double)mu32 - mu64) <= 0x1p-23 * (fabs(mu64) + sqrt(var64)) ? mu32 : (float)mu64;
     const float r = 1.0f / sqrtf(var + eps);
     mean[c] = mu;
     rstd[c] = r;
@@ -650,7 +719,7 @@ int ngan_s2_wgrad(const float* half, const float* full, const float* h_scale, co
 long ngan_chan_reduce_workspace_floats(long npix, int C) {
     int np;
     red_chunk(npix, C, np);
-    return 2L * np * C;
+    return 6L * np * C;      // ngan_bn_stats: part[np][2][C] as doubles, then as floats; the fp32 reductions use the first third
 }
 
 int ngan_bn_stats(const float* y, long npix, int C, const float* gamma, const float* beta, float* mean, float* rstd, float* scale,
@@ -658,14 +727,17 @@ int ngan_bn_stats(const float* y, long npix, int C, const float* gamma, const fl
     NGAN_REQUIRE(y && gamma && beta && mean && rstd && scale && shift && work, NGAN_ERR_ARG, "bn_stats: null pointer");
     NGAN_REQUIRE((run_mean == nullptr) == (run_var == nullptr), NGAN_ERR_ARG, "bn_stats: running mean and variance go together");
     NGAN_REQUIRE(npix > 0 && C > 0, NGAN_ERR_SHAPE, "bn_stats: npix=%ld C=%d", npix, C);
+    NGAN_REQUIRE(reinterpret_cast<uintptr_t>(work) % sizeof(double) == 0, NGAN_ERR_ARG, "bn_stats: work must be 8-byte aligned");
     int np;
     RedArgs a{y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, npix, C, red_chunk(npix, C, np), work};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(chan_reduce_stage1<0>, dim3(np), dim3(256), 0, s, a);
+    double* part = reinterpret_cast<double*>(work);       // 2 np C doubles, then the 2 np C floats of the fp32 sums
+    a.part = work + 4L * np * C;
+    hipLaunchKernelGGL(bn_stats_stage1, dim3(np), dim3(256), 0, s, a, part);
     int st = ngan::launch_status("ngan_bn_stats");
     if (st) return st;
-    hipLaunchKernelGGL(bn_stats_finish, dim3(ngan::ceil_div(C, 256)), dim3(256), 0, s, work, np, y, npix, C, gamma, beta, mean, rstd, scale,
-                       shift, run_mean, run_var, nbt, momentum, eps);
+    hipLaunchKernelGGL(bn_stats_finish, dim3(ngan::ceil_div(C, 256)), dim3(256), 0, s, part, a.part, np, y, npix, C, gamma, beta, mean, rstd,
+                       scale, shift, run_mean, run_var, nbt, momentum, eps);
     return ngan::launch_status("ngan_bn_stats(finish)");
 }
 

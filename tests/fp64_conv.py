@@ -7,7 +7,9 @@ reference takes well under a second).  A 3x3 pad-1 convolution is nine shifted (
     resample codes (ops.RES_*):  0 plain, 1 2x2 average pool on load, 2 bilinear x2 on load (align_corners=False)
     3x3:        conv3x3 / conv3x3_dgrad / conv3x3_wgrad, lrelu_pixelnorm (epilogue 1), pixelnorm_bwd (epilogue 2), pool2 (side output)
     stride 2:   s2_down (Conv2d k4 s2 p1), s2_up (ConvTranspose2d k4 s2 p1), s2_wgrad, act_on_load (BatchNorm -> LeakyReLU on load)
-    BatchNorm:  bn_stats (batch statistics, folded transform, running buffers), bn_act_backward
+    BatchNorm:  bn_stats (batch statistics, folded transform, running buffers), bn_fold_eval, bn_act_backward (with / without the
+                activation), act_backward (no BatchNorm), each with its absolute-value twin (*_abs) for tests/wgan_cases.py
+    stem:       stem, stem_grads (Generator_wgan's Linear, outputs in NHWC order)
     adjoint identities: identity_margins (the noise-scaled statistic of test_full_size_layers_satisfy_the_adjoint_identities)
 """
 import torch
@@ -174,20 +176,79 @@ def bn_stats(y, gamma, beta, eps=1e-5, momentum=0.1, running_mean=None, running_
     out = dict(mean=mean, var=var, rstd=rstd, scale=gamma * rstd, shift=beta - mean * gamma * rstd)
     if running_mean is not None:
         out["running_mean"] = (1 - momentum) * running_mean + momentum * mean
-        out["running_var"] = (1 - momentum) * running_var + momentum * var * n / (n - 1)
+        # one pixel per channel has no unbiased variance (torch refuses the batch): the kernels keep the biased one, 0
+        out["running_var"] = (1 - momentum) * running_var + momentum * var * n / max(n - 1, 1)
     return out
 
 
-def bn_act_backward(y, ga, gamma, beta, mean, rstd, slope):
-    """gradient of LeakyReLU(BatchNorm(y)) in training mode: (gy, dgamma, dbeta) given ga w.r.t. the activation"""
+def bn_stats_abs(y, gamma, beta, eps=1e-5, momentum=0.1, running_mean=None, running_var=None):
+    """absolute-value twin of bn_stats: the mean's is mean|y|; the variance is a sum of squares about the mean, so it, rstd and scale are
+    their own twins; shift and the running buffers add the magnitudes of their terms"""
+    c = y.shape[-1]
+    n = y.reshape(-1, c).shape[0]
+    s = bn_stats(y, gamma, beta, eps)
+    amean = y.reshape(-1, c).abs().mean(0)
+    out = dict(mean=amean, var=s["var"], rstd=s["rstd"], scale=s["scale"].abs(), shift=beta.abs() + amean * s["scale"].abs())
+    if running_mean is not None:
+        out["running_mean"] = abs(1 - momentum) * running_mean.abs() + momentum * amean
+        out["running_var"] = abs(1 - momentum) * running_var.abs() + momentum * s["var"] * n / max(n - 1, 1)
+    return out
+
+
+def bn_fold_eval(gamma, beta, running_mean, running_var, eps=1e-5):
+    """eval-mode BatchNorm2d as an on-load transform: (scale, shift) = (gamma / sqrt(running_var + eps), beta - running_mean * scale)"""
+    scale = gamma / torch.sqrt(running_var + eps)
+    return scale, beta - running_mean * scale
+
+
+def bn_fold_eval_abs(gamma, beta, running_mean, running_var, eps=1e-5):
+    scale = gamma.abs() / torch.sqrt(running_var + eps)
+    return scale, beta.abs() + running_mean.abs() * scale
+
+
+def bn_act_backward(y, ga, gamma, beta, mean, rstd, slope, act=True, mask=None):
+    """gradient of act(BatchNorm(y)) in training mode, act = LeakyReLU(slope) or (act=False) the identity: (gy, dgamma, dbeta) given ga
+    w.r.t. the activation.  mask, when given, is act' per element (1 or slope) and replaces the sign of z computed here."""
     c = y.shape[-1]
     xhat = (y - mean) * rstd
-    z = xhat * gamma + beta
-    gz = ga * torch.where(z > 0, torch.ones_like(z), torch.full_like(z, slope))
+    if mask is None:
+        z = xhat * gamma + beta
+        mask = torch.where(z > 0, torch.ones_like(z), torch.full_like(z, slope)) if act else torch.ones_like(z)
+    gz = ga * mask
     g2, x2 = gz.reshape(-1, c), xhat.reshape(-1, c)
     dbeta, dgamma = g2.sum(0), (g2 * x2).sum(0)
     gy = gamma * rstd * (gz - g2.mean(0) - xhat * (g2 * x2).mean(0))
     return gy, dgamma, dbeta
+
+
+def bn_act_backward_abs(y, ga, gamma, mean, rstd, mask):
+    """absolute-value twin of bn_act_backward: |gz|, |xhat| and the sums of absolute values through the same formula, every term added"""
+    c = y.shape[-1]
+    xhat = ((y - mean) * rstd).abs()
+    gz = (ga * mask).abs()
+    g2, x2 = gz.reshape(-1, c), xhat.reshape(-1, c)
+    dbeta, dgamma = g2.sum(0), (g2 * x2).sum(0)
+    gy = (gamma * rstd).abs() * (gz + g2.mean(0) + xhat * (g2 * x2).mean(0))
+    return gy, dgamma, dbeta
+
+
+def act_backward(y, ga, slope):
+    """gradient of LeakyReLU(y) without BatchNorm; a single product, so its absolute-value twin is |result|"""
+    return ga * torch.where(y > 0, torch.ones_like(y), torch.full_like(y, slope))
+
+
+# ---- the stem Linear of Generator_wgan, outputs permuted NCHW -> NHWC (csrc/stride2.hip) ------------------------------------------
+def stem(z, w, bias, s, c):
+    """y[b, p, c] = bias[c S + p] + sum_k z[b, k] w[c S + p, k]: z (B, K), w (C S, K) -> (B, S, C).  Linear in every operand with
+    non-negative coefficients: its absolute-value twin is stem(|z|, |w|, |bias|)."""
+    return (z @ w.t() + bias).view(z.shape[0], c, s).permute(0, 2, 1).contiguous()
+
+
+def stem_grads(z, g, s, c):
+    """(gW, gb) of stem for the output gradient g (B, S, C): gW[c S + p, k] = sum_b g[b, p, c] z[b, k], gb[c S + p] = sum_b g[b, p, c];
+    twin: stem_grads(|z|, |g|)"""
+    g2 = g.permute(0, 2, 1).reshape(g.shape[0], c * s)
+    return g2.t() @ z, g2.sum(0)
 
 
 # ---- adjoint identities -------------------------------------------------------------------------------------------------------

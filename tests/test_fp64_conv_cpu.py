@@ -143,6 +143,89 @@ def test_batchnorm_matches_torch(C):
     assert close(nchw(gy), yr.grad) and close(dgam, bn.weight.grad) and close(dbet, bn.bias.grad)
 
 
+@pytest.mark.parametrize("case", [(3, 7, 2, 3, 5), (1, 1, 1, 1, 1), (4, 10, 5, 2, 3)])       # B, K, h, w, C: non-square position grids
+def test_stem_and_its_gradients_match_torch(case):
+    B, K, h, w, C = case
+    S = h * w
+    g = torch.Generator().manual_seed(sum(case))
+    lin = torch.nn.Linear(K, C * S).double()
+    z = torch.randn(B, K, generator=g, dtype=D)
+    y = lin(z).view(B, C, h, w)
+    go = torch.randn(y.shape, generator=g, dtype=D)
+    gw, gb = torch.autograd.grad(y, [lin.weight, lin.bias], go)
+    wt, b = lin.weight.detach(), lin.bias.detach()
+    got = R.stem(z, wt, b, S, C)
+    assert close(nchw(got.view(B, h, w, C)), y.detach())
+    g_nhwc = nhwc(go).reshape(B, S, C)
+    rw, rb = R.stem_grads(z, g_nhwc, S, C)
+    assert close(rw, gw) and close(rb, gb)
+    # the twins: the same operators on absolute values bound the originals
+    assert bool((R.stem(z.abs(), wt.abs(), b.abs(), S, C) >= got.abs()).all())
+    aw, ab = R.stem_grads(z.abs(), g_nhwc.abs(), S, C)
+    assert bool((aw >= rw.abs()).all()) and bool((ab >= rb.abs()).all())
+
+
+@pytest.mark.parametrize("C", [1, 5])
+def test_batchnorm_eval_fold_matches_torch(C):
+    g = torch.Generator().manual_seed(C + 21)
+    bn = torch.nn.BatchNorm2d(C, eps=1e-3).double().eval()
+    with torch.no_grad():
+        bn.weight.normal_(1.0, 0.5, generator=g)
+        bn.bias.normal_(0.0, 0.5, generator=g)
+        bn.running_mean.normal_(0.0, 2.0, generator=g)
+        bn.running_var.uniform_(0.01, 2.0, generator=g)
+    x = torch.randn(2, C, 3, 7, generator=g, dtype=D)
+    args = (bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
+    scale, shift = R.bn_fold_eval(*args)
+    assert close(nchw(nhwc(x) * scale + shift), bn(x).detach())
+    sa, ha = R.bn_fold_eval_abs(*args)
+    assert bool((sa >= scale.abs()).all()) and bool((ha >= shift.abs()).all())
+
+
+@pytest.mark.parametrize("act", [True, False])
+def test_batchnorm_backward_variants_match_torch(act):
+    """with and without the activation, with a given act' mask, and the absolute-value twins; 3 x 5 x 7 pixels"""
+    C = 5
+    g = torch.Generator().manual_seed(31 + act)
+    y = torch.randn(3, C, 5, 7, generator=g, dtype=D) * 2 + 3
+    bn = torch.nn.BatchNorm2d(C, eps=1e-3, momentum=0.37).double()
+    with torch.no_grad():
+        bn.weight.normal_(1.0, 0.1, generator=g)
+        bn.bias.normal_(0.0, 0.1, generator=g)
+    rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+    yr = y.clone().requires_grad_()
+    z = bn(yr)
+    out = F.leaky_relu(z, 0.2) if act else z
+    go = torch.randn(out.shape, generator=g, dtype=D)
+    out.backward(go)
+    gam, bet = bn.weight.detach(), bn.bias.detach()
+    s = R.bn_stats(nhwc(y), gam, bet, bn.eps, bn.momentum, rm0, rv0)
+    assert close(s["running_mean"], bn.running_mean) and close(s["running_var"], bn.running_var)
+    gy, dgam, dbet = R.bn_act_backward(nhwc(y), nhwc(go), gam, bet, s["mean"], s["rstd"], 0.2, act=act)
+    assert close(nchw(gy), yr.grad) and close(dgam, bn.weight.grad) and close(dbet, bn.bias.grad)
+    zl = nhwc(z.detach())
+    mask = torch.where(zl > 0, torch.ones_like(zl), torch.full_like(zl, 0.2)) if act else torch.ones_like(zl)
+    gy2, dgam2, dbet2 = R.bn_act_backward(nhwc(y), nhwc(go), gam, None, s["mean"], s["rstd"], 0.2, mask=mask)
+    assert close(gy2, gy) and close(dgam2, dgam) and close(dbet2, dbet)
+    ta = R.bn_act_backward_abs(nhwc(y), nhwc(go), gam, s["mean"], s["rstd"], mask)
+    assert all(bool((t >= v.abs()).all()) for t, v in zip(ta, (gy, dgam, dbet)))
+    a = R.bn_stats_abs(nhwc(y), gam, bet, bn.eps, bn.momentum, rm0, rv0)
+    assert all(bool((a[k] >= s[k].abs() * (1 - 1e-15)).all()) for k in s)
+
+
+def test_activation_backward_and_single_pixel_statistics():
+    g = torch.Generator().manual_seed(41)
+    y = torch.randn(2, 3, 5, 4, generator=g, dtype=D).requires_grad_()      # channels-last (B, H, W, C)
+    go = torch.randn(y.shape, generator=g, dtype=D)
+    (gy,) = torch.autograd.grad(F.leaky_relu(y, 0.2), y, go)
+    assert close(R.act_backward(y.detach(), go, 0.2), gy)
+    # one pixel per channel: torch refuses the batch; the variance is 0 and the running variance takes it as it is
+    one = torch.randn(1, 1, 1, 4, generator=g, dtype=D)
+    s = R.bn_stats(one, torch.ones(4, dtype=D), torch.zeros(4, dtype=D), 1e-5, 0.1, torch.zeros(4, dtype=D), torch.ones(4, dtype=D))
+    assert close(s["mean"], one.reshape(4)) and float(s["var"].abs().max()) == 0.0
+    assert close(s["running_var"], torch.full((4,), 0.9, dtype=D))
+
+
 # ---- the adjoint-identity statistic has power ---------------------------------------------------------------------------------
 def _fp32_triple(x, w, g, scale, pad_mode="zeros"):
     """clean torch fp32 results of a 3x3 layer on NCHW operands (pad_mode "circular": the wrap-around fault in all three)"""
