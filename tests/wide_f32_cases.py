@@ -76,6 +76,7 @@ def mask_of(y):
     return np.where(np.asarray(y, dtype=f64) > 0, 1.0, SLOPE)
 
 
+# (_fma, _m32, _q32, _adj_w, _pooled_img32 and _pool_adjoint_img are shared with tests/lane_group_cases.py, which imports them: keep their meaning)
 # ---- fp32 emulation helpers: the order of csrc/wide.hip -------------------------------------------------------------------------
 def _fma(a, b, c):
     return (a.astype(f64) * b.astype(f64) + c.astype(f64)).astype(f32)
