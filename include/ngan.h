@@ -725,6 +725,31 @@ int ngan_morph_boxcount(const unsigned char* mask, int* counts, int B, int R, vo
 int ngan_skel_thin(const unsigned char* mask, unsigned char* skeleton_or_null, int* stats, int B, int R, void* stream);
 int ngan_skel_counts(const unsigned char* mask, int* stats, int B, int R, void* stream);
 
+/* ---- arbor geometry: distance transform, soma and Sholl crossings of a mask (an addition of this implementation, off by default;
+ * neuron-gan_amd/metrics.py drives it) ------------------------------------------------------------------------------
+ * Masks are (B, R, R) bytes, any non-zero byte is foreground, pixels outside the image are background; R a power of two in 16 .. 1024
+ * (no image has to fit one workgroup's LDS, so there is no 512 limit), 1 <= B <= 65535 (NGAN_ERR_SHAPE otherwise).  Integers and integer
+ * atomics only, but for `roots`, which is summed in fp64 in a fixed order: every output is bit-reproducible, an image's values do not
+ * depend on the rest of the batch, and no workgroup waits on another.  mask, skeleton, dist2 and workspace start on a 16-byte boundary,
+ * roots on an 8-byte one, soma, centre and crossings on a 4-byte one (NGAN_ERR_ARG otherwise, as for a null pointer); a refused call
+ * writes nothing.
+ * edt:    dist2 (B, R, R) int32, overwritten: 0 on the background; on a foreground pixel p the smallest (py-qy)^2 + (px-qx)^2 over all
+ *         background pixels q, those of the one-pixel ring outside the image (rows and columns -1 and R) included -- the exact squared
+ *         Euclidean distance.  soma (B, 3) int32, overwritten: {y, x, dist2} of the pixel with the largest dist2, among equals the one
+ *         with the smallest linear index y * R + x; {-1, -1, 0} for an empty mask.  workspace: ngan_geom_workspace_bytes(B, R) bytes
+ *         (0 for an unsupported shape).
+ * sholl:  skeleton (B, R, R) bytes, any mask; dist2 as edt writes it; centre (B, 3) int32 of which {y, x} are read (the layout of
+ *         soma).  With the ring step s = max(2, R / 64), the ring index k(p) of a pixel is the largest integer k with
+ *         (k s)^2 <= (py-cy)^2 + (px-cx)^2, decided in integers.  The edges of the skeleton are those ngan_skel_counts counts (orth and
+ *         diag).  crossings (B, 91) int32, overwritten: for every edge (p, q) with k(p) != k(q), crossings[b][max(k(p), k(q))] += 1
+ *         (s >= 2 > sqrt 2: the two differ by one; k <= 90 for every centre inside the image; bin 0 stays 0).  roots (B) fp64,
+ *         overwritten: the sum over the set skeleton pixels of sqrt((double) dist2[p]), per-thread partial sums added by a fixed tree.
+ *         An image whose centre lies outside the image (y < 0: the soma of an empty mask) gets all-zero crossings and roots 0. */
+size_t ngan_geom_workspace_bytes(int B, int R);
+int ngan_geom_edt(const unsigned char* mask, int* dist2, int* soma, void* workspace, int B, int R, void* stream);
+int ngan_geom_sholl(const unsigned char* skeleton, const int* dist2, const int* centre, int* crossings, double* roots, int B, int R,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,9 @@ SIGNATURES = {
     # arbor skeleton (include/ngan.h, last section; metrics.py)
     "ngan_skel_thin": [_P, _P, _P, _I, _I, _P],
     "ngan_skel_counts": [_P, _P, _I, _I, _P],
+    # arbor geometry (include/ngan.h, last section; metrics.py)
+    "ngan_geom_edt": [_P, _P, _P, _P, _I, _I, _P],
+    "ngan_geom_sholl": [_P, _P, _P, _P, _P, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -166,6 +169,7 @@ NON_STATUS = {
     "ngan_spectrum_ring_counts": ([_P, _I], _I),
     "ngan_spectrum_workspace_bytes": ([_I, _I, _I], _Z),
     "ngan_morph_workspace_bytes": ([_I, _I], _Z),
+    "ngan_geom_workspace_bytes": ([_I, _I], _Z),
 }
 
 _lib = None

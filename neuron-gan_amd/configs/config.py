@@ -34,6 +34,7 @@ _DEFAULTS = dict(
     spectrum_period=0, spectrum_images=8192, spectrum_seed=0,
     morph_period=0, morph_images=8192, morph_seed=0, morph_min_size=1,
     skeleton_period=0, skeleton_images=8192, skeleton_seed=0, skeleton_min_size=1,
+    sholl_period=0, sholl_images=8192, sholl_seed=0, sholl_min_size=1,
     diffaug='', diffaug_p=1.0, diffaug_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
@@ -118,6 +119,11 @@ def validate_configs(create_dirs=False):
     # arbor skeleton (thinning: length, tips, junctions, width) of samples against the data at checkpoints (an addition of this
     # implementation), with the same meaning as the morph_* names; stages above 512 x 512 are noted, not scored
     for name, lowest in (('skeleton_period', 0), ('skeleton_images', 1), ('skeleton_seed', 0), ('skeleton_min_size', 1)):
+        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
+            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
+    # arbor geometry (distance transform, soma, Sholl profile) of samples against the data at checkpoints (an addition of this
+    # implementation), with the same meaning as the skeleton_* names; it thins, so stages above 512 x 512 are noted, not scored
+    for name, lowest in (('sholl_period', 0), ('sholl_images', 1), ('sholl_seed', 0), ('sholl_min_size', 1)):
         if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
             raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
     # differentiable augmentation of the critic's inputs (an addition of this implementation): diffaug '' is off, otherwise a comma

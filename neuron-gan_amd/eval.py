@@ -17,13 +17,18 @@ largest component's share, fill and box-counting dimension with the Kolmogorov-S
 --morph_min_size pixels are dropped; it combines with --swd, --msssim, --spectrum, --ema and --images.  --skeleton [N] prints, after
 the morphology table when both are asked for, the arbor skeleton (metrics.py) of N samples (default 8192) against N images of the
 data set: skeleton length in image widths, tips, junctions and mean process width with the Kolmogorov-Smirnov distance of each;
-components below --skeleton_min_size pixels are not thinned; it combines with every switch above.
+components below --skeleton_min_size pixels are not thinned; it combines with every switch above.  --sholl [N] prints, after the skeleton
+table when both are asked for, the arbor geometry (metrics.py) of N samples (default 8192) against N images of the data set: mean
+process calibre and soma radius in pixels, the peak of the Sholl histogram about the soma and its radius, and the enclosing radius, in
+image widths, with the Kolmogorov-Smirnov distance of each, then the mean Sholl profile of either side; components below
+--sholl_min_size pixels are not measured; it combines with every switch above.
 
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --swd 8192 --dataset_dir data/science_2022 [--ema]
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --msssim 10000 --dataset_dir data/science_2022 [--ema]
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --spectrum 8192 --dataset_dir data/science_2022 [--ema]
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --morph 8192 --dataset_dir data/science_2022 [--ema]
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --skeleton 8192 --dataset_dir data/science_2022 [--ema]
+    python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --sholl 8192 --dataset_dir data/science_2022 [--ema]
 
 The generator runs on the HIP kernels, so this needs a GPU, like train.py."""
 import argparse
@@ -55,13 +60,17 @@ def build_arg_parser():
                    help='print the arbor skeleton of N samples against N images of the data set (default 8192)')
     p.add_argument('--skeleton_seed', type=int, default=0, help='seed of the skeleton latents and augmentations')
     p.add_argument('--skeleton_min_size', type=int, default=1, help='components below this many pixels are not thinned (1 drops none)')
+    p.add_argument('--sholl', type=int, nargs='?', const=8192, default=None, metavar='N',
+                   help='print the arbor geometry (calibre, soma, Sholl profile) of N samples against N images of the data set (default 8192)')
+    p.add_argument('--sholl_seed', type=int, default=0, help='seed of the arbor-geometry latents and augmentations')
+    p.add_argument('--sholl_min_size', type=int, default=1, help='components below this many pixels are not measured (1 drops none)')
     p.add_argument('--dataset_dir', type=str, default='', help='folder of training images (default: config.dataset_dir)')
     p.add_argument('--images', type=str, default='', help='.pt / .npy file with the images (N, C, R, R) in [-1, 1]')
     return p
 
 
 def load_dataset(options, config, device):
-    """the data set `--swd` / `--msssim` / `--spectrum` / `--morph` / `--skeleton` score against, read the way train.py reads it"""
+    """the data set `--swd` / `--msssim` / `--spectrum` / `--morph` / `--skeleton` / `--sholl` score against, read the way train.py reads it"""
     import numpy as np
     import torch
     from .data import NeuronDataset
@@ -102,6 +111,8 @@ def main(argv=None):
     if options.skeleton is not None and (options.skeleton < 1 or options.skeleton_min_size < 1):
         raise ValueError('--skeleton {} --skeleton_min_size {}: at least one image and one pixel'.format(options.skeleton,
                                                                                                         options.skeleton_min_size))
+    if options.sholl is not None and (options.sholl < 1 or options.sholl_min_size < 1):
+        raise ValueError('--sholl {} --sholl_min_size {}: at least one image and one pixel'.format(options.sholl, options.sholl_min_size))
     if options.swd is not None:
         from .metrics import evaluate_swd, format_table
         if options.swd < 1:
@@ -112,7 +123,7 @@ def main(argv=None):
             res = evaluate_swd(G, dataset, n_images=options.swd, batch_size=min(options.swd, 32), seed=options.swd_seed)
             print(format_table(res, 'SWD x 1e3, {} generator of {} against {} images'.format(
                 'averaged' if use_ema else 'training', options.weights, options.swd)))
-        if options.msssim is None and options.spectrum is None and options.morph is None and options.skeleton is None:
+        if options.msssim is None and options.spectrum is None and options.morph is None and options.skeleton is None and options.sholl is None:
             return 0
     if options.msssim is not None:
         from .metrics import evaluate_msssim, format_msssim
@@ -123,7 +134,7 @@ def main(argv=None):
             res = evaluate_msssim(G, dataset, n_pairs=options.msssim, batch_size=min(options.msssim, 32), seed=options.msssim_seed)
             print(format_msssim(res, 'MS-SSIM between pairs, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                        options.weights)))
-        if options.spectrum is None and options.morph is None and options.skeleton is None:
+        if options.spectrum is None and options.morph is None and options.skeleton is None and options.sholl is None:
             return 0
     if options.spectrum is not None:
         from .metrics import evaluate_spectrum, format_spectrum
@@ -134,7 +145,7 @@ def main(argv=None):
                                     seed=options.spectrum_seed)
             print(format_spectrum(res, 'Radial power spectrum, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                           options.weights)))
-        if options.morph is None and options.skeleton is None:
+        if options.morph is None and options.skeleton is None and options.sholl is None:
             return 0
     if options.morph is not None:
         from .metrics import evaluate_morphology, format_morphology
@@ -145,7 +156,7 @@ def main(argv=None):
                                       min_size=options.morph_min_size)
             print(format_morphology(res, 'Arbor morphology, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                      options.weights)))
-        if options.skeleton is None:
+        if options.skeleton is None and options.sholl is None:
             return 0
     if options.skeleton is not None:
         from .metrics import evaluate_skeleton, format_skeleton
@@ -156,6 +167,16 @@ def main(argv=None):
                                     min_size=options.skeleton_min_size)
             print(format_skeleton(res, 'Arbor skeleton, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                  options.weights)))
+        if options.sholl is None:
+            return 0
+    if options.sholl is not None:
+        from .metrics import evaluate_sholl, format_sholl
+        dataset = load_dataset(options, config, device)
+        for use_ema in ((False, True) if options.ema else (False,)):
+            G = Generator_PG.from_state_dict(weights, device=device, use_ema=use_ema, verbose=False).to(device)
+            res = evaluate_sholl(G, dataset, n_images=options.sholl, batch_size=min(options.sholl, 32), seed=options.sholl_seed,
+                                 min_size=options.sholl_min_size)
+            print(format_sholl(res, 'Arbor geometry, {} generator of {}'.format('averaged' if use_ema else 'training', options.weights)))
         return 0
     G = Generator_PG.from_state_dict(weights, device=device, use_ema=options.ema).to(device)
     plot_gen_samples(G, N_images=options.n, filename=output)

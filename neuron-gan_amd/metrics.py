@@ -40,7 +40,17 @@ processes are -- on the same kept mask, thinned in one launch of csrc/skeleton.h
     thin / skeleton_counts                     the skeleton and {pixels, tips, junctions, isolated, orth, diag, passes, area}; the
                                                six counts of any mask
     skeleton_statistics                        per image: length, tips, junctions, width, scored
-    Skeleton, evaluate_skeleton                per-image values of both sets, summarised as Morphology does"""
+    Skeleton, evaluate_skeleton                per-image values of both sets, summarised as Morphology does
+
+Arbor geometry, where in the image the branches lie and how thick they are locally -- the exact Euclidean distance transform of the
+kept mask and the Sholl histogram of its skeleton about the soma (csrc/sholl.hip):
+
+    distance_transform                         squared distance to the nearest background pixel; the soma {y, x, dist2}, centre and
+                                               radius of the largest inscribed disc
+    sholl_crossings / sholl_step               skeleton edges that cross the circles of radius k s about a centre, 91 bins; the sum of
+                                               the skeleton's local half-calibres
+    sholl_statistics                           per image: calibre, soma, sholl_peak, sholl_radius, reach, scored, crossings
+    Sholl, evaluate_sholl                      per-image values of both sets as above, and the mean Sholl profile of each side"""
 import math
 
 import torch
@@ -879,6 +889,10 @@ class Morphology:
     def _inactive_note(self):
         return f"{self.image_size} x {self.image_size} images are below {MORPH_MIN} x {MORPH_MIN}: nothing to label"
 
+    def _rows(self, s):
+        """what feed() keeps of one minibatch's statistics: a row per statistic, then `scored`"""
+        return torch.stack([s[name] for name in self.STATISTICS] + [s["scored"].to(torch.float64)])
+
     def __init__(self, image_size, n_colors=1, otsu_class=1, min_size=1, device="cuda"):
         if n_colors not in (1, 3):
             raise ValueError(f"n_colors={n_colors}: 1 or 3")
@@ -894,7 +908,7 @@ class Morphology:
         self.device = torch.device(device)
         self.active = self.image_size >= MORPH_MIN
         self.count = {"real": 0, "fake": 0}
-        self.values = {"real": [], "fake": []}        # per feed a (5, b) fp64 tensor: the four statistics and `scored`
+        self.values = {"real": [], "fake": []}        # per feed a (k + 1, b) fp64 tensor: the k statistics and `scored`
 
     def feed(self, which, images):
         if which not in self.count:
@@ -904,8 +918,7 @@ class Morphology:
             raise ValueError(f"images must be {self.image_size} pixels wide with {self.n_colors} colours, got {tuple(images.shape)}")
         if not self.active:
             return
-        s = self._statistics(x)
-        self.values[which].append(torch.stack([s[name] for name in self.STATISTICS] + [s["scored"].to(torch.float64)]))
+        self.values[which].append(self._rows(self._statistics(x)))
         self.count[which] += x.shape[0]
 
     def result(self):
@@ -921,7 +934,8 @@ class Morphology:
         side = {}
         for which in ("real", "fake"):
             v = torch.cat(self.values[which], dim=1).cpu()
-            side[which] = v[:4][:, v[4] > 0.5]
+            k = len(self.STATISTICS)
+            side[which] = v[:k][:, v[k] > 0.5]
         out = {"images": n, "skipped_real": n - side["real"].shape[1], "skipped_fake": n - side["fake"].shape[1]}
         if side["real"].shape[1] == 0 or side["fake"].shape[1] == 0:
             out["note"] = "no scored image on the {} side: every image there lacks four grey levels, a noise floor or a kept pixel".format(
@@ -950,7 +964,7 @@ def evaluate_morphology(generator, dataset, n_images=8192, batch_size=64, seed=0
 
 
 def _evaluate_two_sets(metric_class, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric):
-    """the body of evaluate_morphology and evaluate_skeleton: metric_class is Morphology or Skeleton"""
+    """the body of evaluate_morphology, evaluate_skeleton and evaluate_sholl: metric_class is Morphology, Skeleton or Sholl"""
     device = next(generator.parameters()).device
     size = int(generator.image_size)
     metric = metric_class(size, n_colors=int(getattr(generator, "N_colors", 1)), otsu_class=otsu_class, min_size=min_size, device=device)
@@ -1090,6 +1104,135 @@ def format_skeleton(result, title="Arbor skeleton"):
     for name in SKELETON_STATISTICS:
         r = result[name]
         rows.append(f"{name:>14s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
+    return "\n".join(rows)
+
+
+# ---- arbor geometry: distance transform, soma and Sholl profile (csrc/sholl.hip; include/ngan.h, last section) ---------------------------
+SHOLL_BINS = 91                              # rings a Sholl histogram holds: k <= 90 for every size and every centre inside the image
+SHOLL_STATISTICS = ("calibre", "soma", "sholl_peak", "sholl_radius", "reach")
+
+
+def sholl_step(R):
+    """the ring step in pixels of an R x R image: max(2, R / 64)"""
+    return max(2, int(R) // 64)
+
+
+def distance_transform(mask):
+    """(dist2, soma) of (B, R, R) uint8 masks (non-zero: foreground), R a power of two in 16 .. 1024.  dist2 (B, R, R) int32: 0 on the
+    background, on a foreground pixel the exact squared Euclidean distance to the nearest background pixel, the ring of pixels just
+    outside the image included.  soma (B, 3) int32: {y, x, dist2} of the largest dist2 -- centre and squared radius of the largest
+    inscribed disc --, the smallest index y * R + x among equals; {-1, -1, 0} for an empty mask (include/ngan.h)"""
+    mask = _square_bytes(mask, "mask")
+    b, r, _ = mask.shape
+    dist2 = torch.empty(b, r, r, device=mask.device, dtype=torch.int32)
+    soma = torch.empty(b, 3, device=mask.device, dtype=torch.int32)
+    ws = torch.empty(max(16, _C.lib().ngan_geom_workspace_bytes(b, r)), device=mask.device, dtype=torch.uint8)
+    _C.call("ngan_geom_edt", mask, dist2, soma, ws, b, r)
+    return dist2, soma
+
+
+def sholl_crossings(skeleton, dist2, centre):
+    """(crossings, roots) of (B, R, R) uint8 skeletons (any mask), their masks' dist2 (B, R, R) int32 and centres (B, 3) int32 {y, x, .}
+    (`distance_transform`'s soma as it is).  crossings (B, 91) int32: the edges of the skeleton graph -- the orth and diag pairs of
+    `skeleton_counts` -- whose ends lie in different rings of width sholl_step(R) about the centre, counted in the outer ring's bin.
+    roots (B) fp64: the sum of sqrt(dist2) over the skeleton's pixels, bit-reproducible.  An image whose centre is {-1, -1, .} gets
+    zeros (include/ngan.h)"""
+    skeleton = _square_bytes(skeleton, "skeleton")
+    b, r, _ = skeleton.shape
+    if not (isinstance(dist2, torch.Tensor) and dist2.dtype == torch.int32 and tuple(dist2.shape) == (b, r, r)):
+        raise TypeError(f"dist2: expected an int32 tensor {(b, r, r)}")
+    if not (isinstance(centre, torch.Tensor) and centre.dtype == torch.int32 and tuple(centre.shape) == (b, 3)):
+        raise TypeError(f"centre: expected an int32 tensor {(b, 3)}")
+    crossings = torch.empty(b, SHOLL_BINS, device=skeleton.device, dtype=torch.int32)
+    roots = torch.empty(b, device=skeleton.device, dtype=torch.float64)
+    _C.call("ngan_geom_sholl", skeleton, dist2.contiguous(), centre.contiguous(), crossings, roots, b, r)
+    return crossings, roots
+
+
+def sholl_statistics(images, otsu_class=1, min_size=1, threshold=None):
+    """Per-image arbor geometry of channels-last fp32 images (B, R, R, C) in [-1, 1], R up to 512, fp64 tensors on the device (no host
+    read-back): the kept mask of `arbor_statistics` (same otsu_class, min_size, threshold) is thinned and distance-transformed, and the
+    skeleton's edges are counted where they cross circles about the soma, the centre of the largest inscribed disc:
+        calibre       2 roots / n - 1 with n the skeleton pixels: the mean process width in pixels (a bar of odd width w scores w)
+        soma          sqrt(soma dist2): the radius in pixels of the largest inscribed disc
+        sholl_peak    the largest number of crossings of any ring       sholl_radius   the smallest such ring's radius, in image widths
+        reach         the radius of the last ring with a crossing, in image widths (the enclosing radius); 0 without a crossing
+        scored        as in skeleton_statistics: the others are not to be used where it is False
+        crossings     (B, 91) int32, the Sholl histogram itself"""
+    r, ok, stats, kept = _kept_mask(images, otsu_class, min_size, threshold)
+    skeleton, sk = thin(kept)
+    dist2, soma = distance_transform(kept)
+    crossings, roots = sholl_crossings(skeleton, dist2, soma)
+    scale = sholl_step(r) / float(r)
+    c = crossings.to(torch.int64)
+    peak = c.max(dim=1).values
+    ring = torch.arange(SHOLL_BINS, device=c.device, dtype=torch.int64)
+    first_peak = torch.where(c == peak[:, None], ring, torch.full_like(ring, SHOLL_BINS)).min(dim=1).values
+    last = torch.where(c > 0, ring, torch.zeros_like(ring)).max(dim=1).values
+    return {"calibre": 2.0 * roots / sk[:, 0].to(torch.float64) - 1.0, "soma": soma[:, 2].to(torch.float64).sqrt(),
+            "sholl_peak": peak.to(torch.float64), "sholl_radius": torch.where(peak > 0, first_peak, torch.zeros_like(peak)).to(torch.float64) * scale,
+            "reach": last.to(torch.float64) * scale, "scored": ok & (stats[:, 3] > 0) & (sk[:, 0] > 0), "crossings": crossings}
+
+
+class Sholl(Skeleton):
+    """Collects the per-image arbor geometry of real and generated images and compares their distributions, as Skeleton does, and keeps
+    the Sholl histograms for the mean profile of each side:
+
+        m = Sholl(image_size=64); m.feed('real', x); m.feed('fake', G(z)); m.result()
+
+    It thins, so it is active for the stages the thinning kernel takes, 16 x 16 .. 512 x 512: otherwise feed() does nothing and result()
+    says so."""
+    STATISTICS = SHOLL_STATISTICS
+
+    def _statistics(self, x):
+        return sholl_statistics(x, self.otsu_class, self.min_size)
+
+    def _rows(self, s):
+        """the rows of Morphology, then the 91 crossings of every image (integers, exact in fp64)"""
+        return torch.cat([super()._rows(s), s["crossings"].to(torch.float64).t()])
+
+    def result(self):
+        """what Skeleton.result() returns, with the five statistics of SHOLL_STATISTICS, and 'profile': {'radius': ring radii k s / R in
+        image widths, 'real', 'fake': the mean crossings of that ring over the scored images of the side (exact int64 sums divided by
+        their number)}, cut after the last ring at which either side has a crossing"""
+        out = super().result()
+        if self.STATISTICS[0] not in out:
+            return out
+        k = len(self.STATISTICS)
+        mean = {}
+        for which in ("real", "fake"):
+            v = torch.cat(self.values[which], dim=1).cpu()
+            c = v[k + 1:][:, v[k] > 0.5].to(torch.int64)
+            mean[which] = [int(t) / float(c.shape[1]) for t in c.sum(dim=1)]
+        n = max([i + 1 for i in range(SHOLL_BINS) if mean["real"][i] or mean["fake"][i]], default=0)
+        scale = sholl_step(self.image_size) / float(self.image_size)
+        out["profile"] = {"radius": [i * scale for i in range(n)], "real": mean["real"][:n], "fake": mean["fake"][:n]}
+        return out
+
+
+def evaluate_sholl(generator, dataset, n_images=8192, batch_size=64, seed=0, otsu_class=1, min_size=1, real_from=None, return_metric=False):
+    """The arbor geometry of `generator`'s samples against `dataset`'s images at the generator's current resolution, with the contract
+    of evaluate_skeleton: private generators seeded seed + 1 (augmentation) and seed + 2 (latents), the data set's generator and image
+    size restored afterwards, torch's global and device generators never consumed; real_from: a Sholl that an earlier call returned
+    (return_metric=True) with the same settings, whose data side is taken over."""
+    return _evaluate_two_sets(Sholl, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric)
+
+
+def format_sholl(result, title="Arbor geometry"):
+    """the table eval.py prints: one row per statistic -- data, generated (mean +- standard error) and the KS distance --, then the mean
+    Sholl profile of either side, one number per ring"""
+    if "calibre" not in result:
+        return f"{title}: {result['note']}"
+    pm = lambda v, e: f"{v:10.4f} +- {e:8.4f}" if e is not None else f"{v:10.4f}" + " " * 12   # noqa: E731
+    rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
+            f"{result['skipped_fake']} generated)", f"{'':>14s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
+    for name in SHOLL_STATISTICS:
+        r = result[name]
+        rows.append(f"{name:>14s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
+    p = result["profile"]
+    step = p["radius"][1] if len(p["radius"]) > 1 else 0.0
+    rows.append(f"{'profile data':>14s} " + " ".join(f"{v:.2f}" for v in p["real"]) + f"   (mean crossings per ring, rings {step:.4f} image widths apart)")
+    rows.append(f"{'generated':>14s} " + " ".join(f"{v:.2f}" for v in p["fake"]))
     return "\n".join(rows)
 
 

@@ -1666,6 +1666,48 @@ def score_skeleton(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
     return entry
 
 
+def score_sholl(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
+    """One arbor-geometry evaluation (metrics.evaluate_sholl with cfg.sholl_images images per side in minibatches of cfg.batch_size,
+    seed cfg.sholl_seed, components below cfg.sholl_min_size pixels dropped) of the training generator against the data set and, when
+    the trainer averages, of the averaged one: logged in one line and appended to checkpoint.SHOLL as {epoch, image_size, images,
+    min_size, skipped_real, skipped_fake[, note]} plus, per statistic (calibre, soma, sholl_peak, sholl_radius, reach), {real, real_sem,
+    fake, fake_sem, ks} and profile: {radius, real, fake}; with an averaged generator also skipped_fake_ema, <statistic>_ema: {fake,
+    fake_sem, ks} and profile_ema: {fake} over the rings of profile (the data's side is the same: it is not stored twice).  Eager,
+    outside any captured graph, no collective; it draws from private generators only, so the run trains on as if it had not happened."""
+    from .metrics import SHOLL_STATISTICS, evaluate_sholl
+    G = trainer.G
+    kw = dict(n_images=int(getattr(cfg, 'sholl_images', 8192)), batch_size=int(cfg.batch_size),
+              seed=int(getattr(cfg, 'sholl_seed', 0)), min_size=int(getattr(cfg, 'sholl_min_size', 1)))
+    res, metric = evaluate_sholl(G, dataset, return_metric=True, **kw)
+    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "min_size": kw["min_size"]}
+    entry.update({k: ({a: (list(b) if isinstance(b, list) else b) for a, b in v.items()} if isinstance(v, dict) else v) for k, v in res.items()})
+    if metric.active and getattr(trainer, "ema_enabled", False):
+        with trainer.averaged_generator():
+            ema = evaluate_sholl(G, None, real_from=metric, **kw)      # (the data's side is the same: not scored twice)
+        entry["skipped_fake_ema"] = ema["skipped_fake"]
+        for name in SHOLL_STATISTICS:
+            if name in ema:
+                entry[name + "_ema"] = {k: ema[name][k] for k in ("fake", "fake_sem", "ks")}
+        if "profile" in ema and "profile" in entry:
+            n = len(entry["profile"]["radius"])
+            entry["profile_ema"] = {"fake": (list(ema["profile"]["fake"]) + [0.0] * n)[:n]}
+    if "calibre" not in res:
+        log("Epoch:{}, sholl: {}".format(epoch, res["note"]))
+    else:
+        one = lambda r: "calibre {:.3f} (KS {:.3f}), soma {:.2f}, peak {:.2f} at {:.3f}, reach {:.3f} (KS {:.3f})".format(   # noqa: E731
+            r["calibre"]["fake"], r["calibre"]["ks"], r["soma"]["fake"], r["sholl_peak"]["fake"], r["sholl_radius"]["fake"],
+            r["reach"]["fake"], r["reach"]["ks"])
+        line = "Epoch:{}, sholl over {} images: {}; data: calibre {:.3f}, soma {:.2f}, peak {:.2f} at {:.3f}, reach {:.3f}".format(
+            epoch, res["images"], one(res), res["calibre"]["real"], res["soma"]["real"], res["sholl_peak"]["real"],
+            res["sholl_radius"]["real"], res["reach"]["real"])
+        if "calibre_ema" in entry:
+            line += "; averaged generator: " + one({n: entry[n + "_ema"] for n in SHOLL_STATISTICS})
+        log(line)
+    if checkpoint is not None:
+        checkpoint.SHOLL.append(entry)
+    return entry
+
+
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
                 samples_dir=None, on_epoch=None, process_group=None, draws=None):
     """The reference's epoch loop (train.py:298-451) over a PGGANTrainer.
@@ -1683,7 +1725,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     every rank; rank 0 alone logs, saves and plots.  With one rank nothing of this is active.
     cfg.swd_period > 0: rank 0 scores every checkpoint whose epoch is a multiple of it (`score_swd`) before it is written; the other
     ranks wait at the checkpoint's barrier.  cfg.msssim_period > 0: the same with `score_msssim`; cfg.spectrum_period > 0: with `score_spectrum`;
-    cfg.morph_period > 0: with `score_morph`; cfg.skeleton_period > 0: with `score_skeleton`.
+    cfg.morph_period > 0: with `score_morph`; cfg.skeleton_period > 0: with `score_skeleton`; cfg.sholl_period > 0: with `score_sholl`.
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
     (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
@@ -1697,6 +1739,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     spectrum_period = int(getattr(cfg, 'spectrum_period', 0) or 0)
     morph_period = int(getattr(cfg, 'morph_period', 0) or 0)
     skeleton_period = int(getattr(cfg, 'skeleton_period', 0) or 0)
+    sholl_period = int(getattr(cfg, 'sholl_period', 0) or 0)
     G, D = trainer.G, trainer.D
     dev = trainer.device
     epoch_final = epoch_final if epoch_final is not None else cfg.N_epochs + 1
@@ -1813,6 +1856,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
                     score_morph(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 if skeleton_period > 0 and epoch % skeleton_period == 0:
                     score_skeleton(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
+                if sholl_period > 0 and epoch % sholl_period == 0:
+                    score_sholl(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 checkpoint.save_state(epoch)
                 if samples_dir is not None:
                     from .utils import plot_gen_samples
@@ -2012,6 +2057,12 @@ def build_arg_parser():
     p.add_argument('--skeleton_images', type=int, default=8192, help='images per side of one skeleton evaluation')
     p.add_argument('--skeleton_seed', type=int, default=0, help='seed of the skeleton latents and augmentations')
     p.add_argument('--skeleton_min_size', type=int, default=1, help='components below this many pixels are not thinned (1 drops none)')
+    p.add_argument('--sholl_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the arbor '
+                                                               'geometry (calibre, soma, Sholl profile) of samples against the data '
+                                                               '(metrics.py); 0: off')
+    p.add_argument('--sholl_images', type=int, default=8192, help='images per side of one arbor-geometry evaluation')
+    p.add_argument('--sholl_seed', type=int, default=0, help='seed of the arbor-geometry latents and augmentations')
+    p.add_argument('--sholl_min_size', type=int, default=1, help='components below this many pixels are not measured (1 drops none)')
     p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
                                                         'launch.py); batch_size stays the global batch')
     return p
