@@ -750,6 +750,34 @@ int ngan_geom_edt(const unsigned char* mask, int* dist2, int* soma, void* worksp
 int ngan_geom_sholl(const unsigned char* skeleton, const int* dist2, const int* centre, int* crossings, double* roots, int B, int R,
                     void* stream);
 
+/* ---- arbor branches: nodes, spur pruning and branch lengths of a skeleton (an addition of this implementation, off by default;
+ * neuron-gan_amd/metrics.py drives it) ------------------------------------------------------------------------------
+ * skeleton is (B, R, R) bytes, any mask: any non-zero byte is set, pixels outside the image are background, the linear index of a pixel
+ * is y * R + x.  R a power of two in 16 .. 512 (the thinning's range), 1 <= B <= 65535 (NGAN_ERR_SHAPE otherwise); spur >= 1
+ * (NGAN_ERR_ARG otherwise).  skeleton, labels and workspace must start on a 16-byte boundary, stats and hist on a 4-byte one; a null
+ * (but for labels) or misaligned pointer is NGAN_ERR_ARG.  A refused call writes nothing.  Integers and integer atomics only: every
+ * output is bit-reproducible and an image's values do not depend on the rest of the batch.
+ * Graph: the vertices are the set pixels, the edges those ngan_skel_counts counts (orth: horizontal and vertical neighbours; diag:
+ *         diagonal neighbours neither of whose two common 4-neighbours is set); deg(p) is the number of edges at p.  A node pixel has
+ *         deg >= 3, a branch pixel deg <= 2.  An edge is a node edge (both ends node pixels), a branch edge (both branch pixels) or an
+ *         attachment.  A node is a connected component of node pixels under node edges, a branch one of branch pixels under branch
+ *         edges: a simple path or a cycle, an isolated pixel included.
+ * Per branch: n pixels; a attachments at its pixels (0, 1 or 2); o and d its branch edges plus its attachments, orth and diag; the floor
+ *         length L = o + isqrt(2 d d), an exact integer square root.  Class: free (a = 0), spur (a = 1 and n < spur), terminal (a = 1
+ *         and n >= spur), link (a = 2).  spur = 1 prunes nothing.
+ * Per node: strong, the number of attachments whose branch is no spur; a fork is a node with strong >= 3.  Pruning is one round.
+ * labels (B, R, R) int32, optional (stats and hist are the same bits without): -1 on the background, on a branch pixel the smallest
+ *         linear index of its branch, on a node pixel -2 - the smallest linear index of its node.
+ * stats  (B, 20) int32, overwritten: {pixels, node_pixels, nodes, branches, terminal, links, free, spurs, term_orth, term_diag,
+ *         link_orth, link_diag, free_orth, free_diag, spur_orth, spur_diag (the o and d sums of the branches of a class), node_orth,
+ *         node_diag (the node edges), longest (the largest L over terminal, link and free branches, 0 without one), forks}.
+ *         branches = terminal + links + free + spurs; the four *_orth plus node_orth are ngan_skel_counts' orth, and so for diag.
+ * hist   (B, 64) int32, overwritten: every terminal and link branch adds one to bin min(63, L / max(1, R / 128)).
+ * workspace: ngan_branch_workspace_bytes(B, R) bytes, 13 per pixel (0 for an unsupported shape). */
+size_t ngan_branch_workspace_bytes(int B, int R);
+int ngan_branch_graph(const unsigned char* skeleton, int* labels_or_null, int* stats, int* hist, void* workspace, int B, int R, int spur,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

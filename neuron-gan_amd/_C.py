@@ -126,6 +126,8 @@ SIGNATURES = {
     # arbor geometry (include/ngan.h, last section; metrics.py)
     "ngan_geom_edt": [_P, _P, _P, _P, _I, _I, _P],
     "ngan_geom_sholl": [_P, _P, _P, _P, _P, _I, _I, _P],
+    # arbor branches (include/ngan.h, last section; metrics.py)
+    "ngan_branch_graph": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -170,6 +172,7 @@ NON_STATUS = {
     "ngan_spectrum_workspace_bytes": ([_I, _I, _I], _Z),
     "ngan_morph_workspace_bytes": ([_I, _I], _Z),
     "ngan_geom_workspace_bytes": ([_I, _I], _Z),
+    "ngan_branch_workspace_bytes": ([_I, _I], _Z),
 }
 
 _lib = None

@@ -22,7 +22,9 @@ The directory name carries a hyphen, so it is loaded under the module name `neur
                        arbor skeleton: thinning, tips, junctions, length and width of the same mask (csrc/skeleton.hip),
                        `evaluate_skeleton`;
                        arbor geometry: exact distance transform, soma and Sholl profile of the same mask (csrc/sholl.hip),
-                       `evaluate_sholl`
+                       `evaluate_sholl`;
+                       arbor branches: nodes, spur pruning and branch lengths of the same skeleton (csrc/branch.hip),
+                       `evaluate_branches`
     workmodel.py       algorithmic FLOP / byte model of an iteration (what bench.py's roofline figures divide by)
 """
 from . import _C, launch, ops, wgan_ops, utils, models, loss_functions, train, data, workmodel, metrics, eval  # noqa: F401, A004

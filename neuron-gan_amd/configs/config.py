@@ -35,6 +35,7 @@ _DEFAULTS = dict(
     morph_period=0, morph_images=8192, morph_seed=0, morph_min_size=1,
     skeleton_period=0, skeleton_images=8192, skeleton_seed=0, skeleton_min_size=1,
     sholl_period=0, sholl_images=8192, sholl_seed=0, sholl_min_size=1,
+    branch_period=0, branch_images=8192, branch_seed=0, branch_min_size=1, branch_spur=0,
     diffaug='', diffaug_p=1.0, diffaug_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
@@ -124,6 +125,12 @@ def validate_configs(create_dirs=False):
     # arbor geometry (distance transform, soma, Sholl profile) of samples against the data at checkpoints (an addition of this
     # implementation), with the same meaning as the skeleton_* names; it thins, so stages above 512 x 512 are noted, not scored
     for name, lowest in (('sholl_period', 0), ('sholl_images', 1), ('sholl_seed', 0), ('sholl_min_size', 1)):
+        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
+            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
+    # arbor branches (nodes, spur pruning, branch lengths) of samples against the data at checkpoints (an addition of this
+    # implementation), with the same meaning as the sholl_* names; branch_spur: terminal branches below that many pixels are pruned as
+    # thinning spurs, 0: max(2, image size / 32)
+    for name, lowest in (('branch_period', 0), ('branch_images', 1), ('branch_seed', 0), ('branch_min_size', 1), ('branch_spur', 0)):
         if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
             raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
     # differentiable augmentation of the critic's inputs (an addition of this implementation): diffaug '' is off, otherwise a comma

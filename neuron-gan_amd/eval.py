@@ -21,7 +21,12 @@ components below --skeleton_min_size pixels are not thinned; it combines with ev
 table when both are asked for, the arbor geometry (metrics.py) of N samples (default 8192) against N images of the data set: mean
 process calibre and soma radius in pixels, the peak of the Sholl histogram about the soma and its radius, and the enclosing radius, in
 image widths, with the Kolmogorov-Smirnov distance of each, then the mean Sholl profile of either side; components below
---sholl_min_size pixels are not measured; it combines with every switch above.
+--sholl_min_size pixels are not measured; it combines with every switch above.  --branches [N] prints, after the geometry table when
+both are asked for, the arbor branches (metrics.py) of N samples (default 8192) against N images of the data set: forks (branch points
+that keep three branches after spur pruning), nodes, terminal branches, spurs, the mean terminal and link branch and the longest branch
+in image widths, with the Kolmogorov-Smirnov distance of each, then the mean branch-length histogram of either side; terminal branches
+below --branch_spur pixels count as spurs (0: max(2, image size / 32)), components below --branch_min_size pixels are not measured; it
+combines with every switch above.
 
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --swd 8192 --dataset_dir data/science_2022 [--ema]
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --msssim 10000 --dataset_dir data/science_2022 [--ema]
@@ -29,6 +34,7 @@ image widths, with the Kolmogorov-Smirnov distance of each, then the mean Sholl 
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --morph 8192 --dataset_dir data/science_2022 [--ema]
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --skeleton 8192 --dataset_dir data/science_2022 [--ema]
     python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --sholl 8192 --dataset_dir data/science_2022 [--ema]
+    python neuron-gan_amd/eval.py -weights GenDisc_0010.pth --branches 8192 --dataset_dir data/science_2022 [--ema]
 
 The generator runs on the HIP kernels, so this needs a GPU, like train.py."""
 import argparse
@@ -64,13 +70,19 @@ def build_arg_parser():
                    help='print the arbor geometry (calibre, soma, Sholl profile) of N samples against N images of the data set (default 8192)')
     p.add_argument('--sholl_seed', type=int, default=0, help='seed of the arbor-geometry latents and augmentations')
     p.add_argument('--sholl_min_size', type=int, default=1, help='components below this many pixels are not measured (1 drops none)')
+    p.add_argument('--branches', type=int, nargs='?', const=8192, default=None, metavar='N',
+                   help='print the arbor branches (forks, spurs, branch lengths) of N samples against N images of the data set (default 8192)')
+    p.add_argument('--branch_seed', type=int, default=0, help='seed of the arbor-branch latents and augmentations')
+    p.add_argument('--branch_min_size', type=int, default=1, help='components below this many pixels are not measured (1 drops none)')
+    p.add_argument('--branch_spur', type=int, default=0, help='terminal branches below this many pixels are pruned as thinning spurs '
+                                                              '(0: max(2, image size / 32))')
     p.add_argument('--dataset_dir', type=str, default='', help='folder of training images (default: config.dataset_dir)')
     p.add_argument('--images', type=str, default='', help='.pt / .npy file with the images (N, C, R, R) in [-1, 1]')
     return p
 
 
 def load_dataset(options, config, device):
-    """the data set `--swd` / `--msssim` / `--spectrum` / `--morph` / `--skeleton` / `--sholl` score against, read the way train.py reads it"""
+    """the data set `--swd` / `--msssim` / `--spectrum` / `--morph` / `--skeleton` / `--sholl` / `--branches` score against, read the way train.py reads it"""
     import numpy as np
     import torch
     from .data import NeuronDataset
@@ -113,6 +125,9 @@ def main(argv=None):
                                                                                                         options.skeleton_min_size))
     if options.sholl is not None and (options.sholl < 1 or options.sholl_min_size < 1):
         raise ValueError('--sholl {} --sholl_min_size {}: at least one image and one pixel'.format(options.sholl, options.sholl_min_size))
+    if options.branches is not None and (options.branches < 1 or options.branch_min_size < 1 or options.branch_spur < 0):
+        raise ValueError('--branches {} --branch_min_size {} --branch_spur {}: at least one image and one pixel, and no negative spur'.format(
+            options.branches, options.branch_min_size, options.branch_spur))
     if options.swd is not None:
         from .metrics import evaluate_swd, format_table
         if options.swd < 1:
@@ -123,7 +138,7 @@ def main(argv=None):
             res = evaluate_swd(G, dataset, n_images=options.swd, batch_size=min(options.swd, 32), seed=options.swd_seed)
             print(format_table(res, 'SWD x 1e3, {} generator of {} against {} images'.format(
                 'averaged' if use_ema else 'training', options.weights, options.swd)))
-        if options.msssim is None and options.spectrum is None and options.morph is None and options.skeleton is None and options.sholl is None:
+        if options.msssim is None and options.spectrum is None and options.morph is None and options.skeleton is None and options.sholl is None and options.branches is None:
             return 0
     if options.msssim is not None:
         from .metrics import evaluate_msssim, format_msssim
@@ -134,7 +149,7 @@ def main(argv=None):
             res = evaluate_msssim(G, dataset, n_pairs=options.msssim, batch_size=min(options.msssim, 32), seed=options.msssim_seed)
             print(format_msssim(res, 'MS-SSIM between pairs, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                        options.weights)))
-        if options.spectrum is None and options.morph is None and options.skeleton is None and options.sholl is None:
+        if options.spectrum is None and options.morph is None and options.skeleton is None and options.sholl is None and options.branches is None:
             return 0
     if options.spectrum is not None:
         from .metrics import evaluate_spectrum, format_spectrum
@@ -145,7 +160,7 @@ def main(argv=None):
                                     seed=options.spectrum_seed)
             print(format_spectrum(res, 'Radial power spectrum, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                           options.weights)))
-        if options.morph is None and options.skeleton is None and options.sholl is None:
+        if options.morph is None and options.skeleton is None and options.sholl is None and options.branches is None:
             return 0
     if options.morph is not None:
         from .metrics import evaluate_morphology, format_morphology
@@ -156,7 +171,7 @@ def main(argv=None):
                                       min_size=options.morph_min_size)
             print(format_morphology(res, 'Arbor morphology, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                      options.weights)))
-        if options.skeleton is None and options.sholl is None:
+        if options.skeleton is None and options.sholl is None and options.branches is None:
             return 0
     if options.skeleton is not None:
         from .metrics import evaluate_skeleton, format_skeleton
@@ -167,7 +182,7 @@ def main(argv=None):
                                     min_size=options.skeleton_min_size)
             print(format_skeleton(res, 'Arbor skeleton, {} generator of {}'.format('averaged' if use_ema else 'training',
                                                                                  options.weights)))
-        if options.sholl is None:
+        if options.sholl is None and options.branches is None:
             return 0
     if options.sholl is not None:
         from .metrics import evaluate_sholl, format_sholl
@@ -177,6 +192,16 @@ def main(argv=None):
             res = evaluate_sholl(G, dataset, n_images=options.sholl, batch_size=min(options.sholl, 32), seed=options.sholl_seed,
                                  min_size=options.sholl_min_size)
             print(format_sholl(res, 'Arbor geometry, {} generator of {}'.format('averaged' if use_ema else 'training', options.weights)))
+        if options.branches is None:
+            return 0
+    if options.branches is not None:
+        from .metrics import evaluate_branches, format_branches
+        dataset = load_dataset(options, config, device)
+        for use_ema in ((False, True) if options.ema else (False,)):
+            G = Generator_PG.from_state_dict(weights, device=device, use_ema=use_ema, verbose=False).to(device)
+            res = evaluate_branches(G, dataset, n_images=options.branches, batch_size=min(options.branches, 32), seed=options.branch_seed,
+                                    min_size=options.branch_min_size, spur=options.branch_spur or None)
+            print(format_branches(res, 'Arbor branches, {} generator of {}'.format('averaged' if use_ema else 'training', options.weights)))
         return 0
     G = Generator_PG.from_state_dict(weights, device=device, use_ema=options.ema).to(device)
     plot_gen_samples(G, N_images=options.n, filename=output)

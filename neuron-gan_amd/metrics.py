@@ -50,7 +50,16 @@ kept mask and the Sholl histogram of its skeleton about the soma (csrc/sholl.hip
     sholl_crossings / sholl_step               skeleton edges that cross the circles of radius k s about a centre, 91 bins; the sum of
                                                the skeleton's local half-calibres
     sholl_statistics                           per image: calibre, soma, sholl_peak, sholl_radius, reach, scored, crossings
-    Sholl, evaluate_sholl                      per-image values of both sets as above, and the mean Sholl profile of each side"""
+    Sholl, evaluate_sholl                      per-image values of both sets as above, and the mean Sholl profile of each side
+
+Arbor branches, the skeleton cut into nodes and branches -- junction pixels merged into branch points, thinning spurs told apart from
+real endings, the lengths of terminal and internal branches (csrc/branch.hip):
+
+    branch_graph / default_spur                labels of nodes and branches, the 20 integers of BRANCH_STATS and the branch-length
+                                               histogram of any mask, for a spur length in pixels
+    branch_statistics                          per image: forks, nodes, terminals, spurs, terminal_length, link_length, longest, scored,
+                                               hist
+    Branches, evaluate_branches                per-image values of both sets as above, and the mean branch-length histogram of each side"""
 import math
 
 import torch
@@ -963,16 +972,20 @@ def evaluate_morphology(generator, dataset, n_images=8192, batch_size=64, seed=0
     return _evaluate_two_sets(Morphology, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric)
 
 
-def _evaluate_two_sets(metric_class, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric):
-    """the body of evaluate_morphology, evaluate_skeleton and evaluate_sholl: metric_class is Morphology, Skeleton or Sholl"""
+def _evaluate_two_sets(metric_class, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric,
+                       **options):
+    """the body of evaluate_morphology, evaluate_skeleton, evaluate_sholl and evaluate_branches: metric_class is Morphology, Skeleton,
+    Sholl or Branches; options: further settings of the metric's constructor, which real_from must match as well"""
     device = next(generator.parameters()).device
     size = int(generator.image_size)
-    metric = metric_class(size, n_colors=int(getattr(generator, "N_colors", 1)), otsu_class=otsu_class, min_size=min_size, device=device)
+    metric = metric_class(size, n_colors=int(getattr(generator, "N_colors", 1)), otsu_class=otsu_class, min_size=min_size, device=device,
+                          **options)
     if not metric.active:
         return (metric.result(), metric) if return_metric else metric.result()
     if real_from is not None:
         if (real_from.image_size, real_from.n_colors, real_from.otsu_class, real_from.min_size, real_from.count["real"]) != \
-                (metric.image_size, metric.n_colors, metric.otsu_class, metric.min_size, int(n_images)):
+                (metric.image_size, metric.n_colors, metric.otsu_class, metric.min_size, int(n_images)) or \
+                any(getattr(real_from, name, None) != getattr(metric, name) for name in options):
             raise ValueError("real_from was fed with other settings")
         metric.count["real"], metric.values["real"] = real_from.count["real"], list(real_from.values["real"])
     n_images, batch_size = int(n_images), int(batch_size)
@@ -1233,6 +1246,137 @@ def format_sholl(result, title="Arbor geometry"):
     step = p["radius"][1] if len(p["radius"]) > 1 else 0.0
     rows.append(f"{'profile data':>14s} " + " ".join(f"{v:.2f}" for v in p["real"]) + f"   (mean crossings per ring, rings {step:.4f} image widths apart)")
     rows.append(f"{'generated':>14s} " + " ".join(f"{v:.2f}" for v in p["fake"]))
+    return "\n".join(rows)
+
+
+# ---- arbor branches: nodes, spur pruning and branch lengths (csrc/branch.hip; include/ngan.h, last section) -------------------------------
+BRANCH_BINS = 64                             # bins of a branch-length histogram, max(1, R / 128) pixels wide; the last one is open
+BRANCH_STATISTICS = ("forks", "nodes", "terminals", "spurs", "terminal_length", "link_length", "longest")
+BRANCH_STATS = ("pixels", "node_pixels", "nodes", "branches", "terminal", "links", "free", "spurs", "term_orth", "term_diag", "link_orth",
+                "link_diag", "free_orth", "free_diag", "spur_orth", "spur_diag", "node_orth", "node_diag", "longest", "forks")
+
+
+def default_spur(R):
+    """the spur length in pixels that branch_statistics prunes below when none is given: max(2, R / 32)"""
+    return max(2, int(R) // 32)
+
+
+def _spur(spur):
+    if isinstance(spur, bool) or not isinstance(spur, int) or spur < 1:
+        raise ValueError(f"spur={spur!r} must be an integer >= 1")
+    return spur
+
+
+def branch_graph(skeleton, spur=1, want_labels=False):
+    """(labels, stats, hist) of (B, R, R) uint8 skeletons (any mask; non-zero: set), R a power of two in 16 .. 512.  The set pixels are
+    the vertices of a graph whose edges are the orth and diag pairs of `skeleton_counts`; pixels with three or more edges are node
+    pixels, their components nodes, and the components of the other pixels branches (paths and cycles).  A branch with no attachment
+    to a node is free, one with two a link, one with one a spur when it has fewer than `spur` pixels and a terminal branch otherwise; a
+    node that keeps three or more attachments of branches that are no spurs is a fork (include/ngan.h).
+    labels (B, R, R) int32 (None with want_labels=False; stats and hist are the same bits either way): -1 on the background, the
+    smallest linear index of its branch on a branch pixel, -2 - the smallest linear index of its node on a node pixel.
+    stats (B, 20) int32 in the order of BRANCH_STATS; hist (B, 64) int32: the floor lengths of the terminal and link branches"""
+    skeleton = _square_bytes(skeleton, "skeleton")
+    spur = _spur(spur)
+    b, r, _ = skeleton.shape
+    if not (MORPH_MIN <= r <= SKEL_MAX and r & (r - 1) == 0):
+        raise ValueError(f"R={r}: a power of two in {MORPH_MIN} .. {SKEL_MAX}")
+    dev = skeleton.device
+    labels = torch.empty(b, r, r, device=dev, dtype=torch.int32) if want_labels else None
+    stats = torch.empty(b, len(BRANCH_STATS), device=dev, dtype=torch.int32)
+    hist = torch.empty(b, BRANCH_BINS, device=dev, dtype=torch.int32)
+    ws = torch.empty(max(16, _C.lib().ngan_branch_workspace_bytes(b, r)), device=dev, dtype=torch.uint8)
+    _C.call("ngan_branch_graph", skeleton, labels, stats, hist, ws, b, r, spur)
+    return labels, stats, hist
+
+
+def branch_statistics(images, otsu_class=1, min_size=1, threshold=None, spur=None):
+    """Per-image branch statistics of channels-last fp32 images (B, R, R, C) in [-1, 1], R up to 512, fp64 tensors on the device (no host
+    read-back): the kept mask of `arbor_statistics` (same otsu_class, min_size, threshold) is thinned and its skeleton cut into nodes
+    and branches; terminal branches below `spur` pixels (None: default_spur(R)) are pruned as thinning spurs, in one round.
+        forks             nodes that keep three or more branches          nodes        branch points, pruned or not
+        terminals         terminal branches that are no spurs             spurs        the pruned ones
+        terminal_length   (term_orth + sqrt(2) term_diag) / max(1, terminals) / R: the mean terminal branch in image widths; 0 without one
+        link_length       the same over the branches between two nodes    longest      the longest branch that is no spur, / R
+        scored            as in skeleton_statistics: the others are not to be used where it is False
+        hist              (B, 64) int32, the branch-length histogram itself"""
+    spur = None if spur is None else _spur(spur)
+    r, ok, stats, kept = _kept_mask(images, otsu_class, min_size, threshold)
+    skeleton, sk = thin(kept)
+    _, st, hist = branch_graph(skeleton, default_spur(r) if spur is None else spur)
+    s = st.to(torch.float64)
+    root2 = math.sqrt(2.0)
+    return {"forks": s[:, 19], "nodes": s[:, 2], "terminals": s[:, 4], "spurs": s[:, 7],
+            "terminal_length": (s[:, 8] + root2 * s[:, 9]) / s[:, 4].clamp(min=1.0) / float(r),
+            "link_length": (s[:, 10] + root2 * s[:, 11]) / s[:, 5].clamp(min=1.0) / float(r), "longest": s[:, 18] / float(r),
+            "scored": ok & (stats[:, 3] > 0) & (sk[:, 0] > 0), "hist": hist}
+
+
+class Branches(Skeleton):
+    """Collects the per-image branch statistics of real and generated images and compares their distributions, as Skeleton does, and
+    keeps the branch-length histograms for the mean profile of each side:
+
+        m = Branches(image_size=64); m.feed('real', x); m.feed('fake', G(z)); m.result()
+
+    spur: terminal branches below that many pixels are pruned (None: default_spur(image_size)).  It thins, so it is active for the
+    stages the thinning kernel takes, 16 x 16 .. 512 x 512: otherwise feed() does nothing and result() says so."""
+    STATISTICS = BRANCH_STATISTICS
+
+    def __init__(self, image_size, n_colors=1, otsu_class=1, min_size=1, device="cuda", spur=None):
+        super().__init__(image_size, n_colors=n_colors, otsu_class=otsu_class, min_size=min_size, device=device)
+        self.spur = default_spur(self.image_size) if spur is None else _spur(spur)
+
+    def _statistics(self, x):
+        return branch_statistics(x, self.otsu_class, self.min_size, spur=self.spur)
+
+    def _rows(self, s):
+        """the rows of Morphology, then the 64 bins of every image (integers, exact in fp64)"""
+        return torch.cat([super()._rows(s), s["hist"].to(torch.float64).t()])
+
+    def result(self):
+        """what Skeleton.result() returns, with the seven statistics of BRANCH_STATISTICS, and 'profile': {'length': the bins' lower
+        edges k max(1, R / 128) / R in image widths, 'real', 'fake': the mean number of terminal and link branches of that length over
+        the scored images of the side (exact int64 sums divided by their number)}, cut after the last bin that either side fills"""
+        out = super().result()
+        if self.STATISTICS[0] not in out:
+            return out
+        k = len(self.STATISTICS)
+        mean = {}
+        for which in ("real", "fake"):
+            v = torch.cat(self.values[which], dim=1).cpu()
+            c = v[k + 1:][:, v[k] > 0.5].to(torch.int64)
+            mean[which] = [int(t) / float(c.shape[1]) for t in c.sum(dim=1)]
+        n = max([i + 1 for i in range(BRANCH_BINS) if mean["real"][i] or mean["fake"][i]], default=0)
+        scale = max(1, self.image_size // 128) / float(self.image_size)
+        out["profile"] = {"length": [i * scale for i in range(n)], "real": mean["real"][:n], "fake": mean["fake"][:n]}
+        return out
+
+
+def evaluate_branches(generator, dataset, n_images=8192, batch_size=64, seed=0, otsu_class=1, min_size=1, real_from=None,
+                      return_metric=False, spur=None):
+    """The branch statistics of `generator`'s samples against `dataset`'s images at the generator's current resolution, with the contract
+    of evaluate_skeleton: private generators seeded seed + 1 (augmentation) and seed + 2 (latents), the data set's generator and image
+    size restored afterwards, torch's global and device generators never consumed; real_from: a Branches that an earlier call returned
+    (return_metric=True) with the same settings, `spur` included, whose data side is taken over."""
+    return _evaluate_two_sets(Branches, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric,
+                              spur=spur)
+
+
+def format_branches(result, title="Arbor branches"):
+    """the table eval.py prints: one row per statistic -- data, generated (mean +- standard error) and the KS distance --, then the mean
+    branch-length histogram of either side, one number per bin"""
+    if "forks" not in result:
+        return f"{title}: {result['note']}"
+    pm = lambda v, e: f"{v:10.4f} +- {e:8.4f}" if e is not None else f"{v:10.4f}" + " " * 12   # noqa: E731
+    rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
+            f"{result['skipped_fake']} generated)", f"{'':>16s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
+    for name in BRANCH_STATISTICS:
+        r = result[name]
+        rows.append(f"{name:>16s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
+    p = result["profile"]
+    step = p["length"][1] if len(p["length"]) > 1 else 0.0
+    rows.append(f"{'profile data':>16s} " + " ".join(f"{v:.2f}" for v in p["real"]) + f"   (mean branches per bin, bins {step:.4f} image widths wide)")
+    rows.append(f"{'generated':>16s} " + " ".join(f"{v:.2f}" for v in p["fake"]))
     return "\n".join(rows)
 
 

@@ -1708,6 +1708,50 @@ def score_sholl(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
     return entry
 
 
+def score_branches(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
+    """One arbor-branch evaluation (metrics.evaluate_branches with cfg.branch_images images per side in minibatches of cfg.batch_size,
+    seed cfg.branch_seed, components below cfg.branch_min_size pixels dropped, terminal branches below cfg.branch_spur pixels pruned --
+    0: max(2, image size / 32)) of the training generator against the data set and, when the trainer averages, of the averaged one:
+    logged in one line and appended to checkpoint.BRANCH as {epoch, image_size, images, min_size, spur, skipped_real, skipped_fake[,
+    note]} plus, per statistic (forks, nodes, terminals, spurs, terminal_length, link_length, longest), {real, real_sem, fake, fake_sem,
+    ks} and profile: {length, real, fake}; with an averaged generator also skipped_fake_ema, <statistic>_ema: {fake, fake_sem, ks} and
+    profile_ema: {fake} over the bins of profile (the data's side is the same: it is not stored twice).  Eager, outside any captured
+    graph, no collective; it draws from private generators only, so the run trains on as if it had not happened."""
+    from .metrics import BRANCH_STATISTICS, default_spur, evaluate_branches
+    G = trainer.G
+    spur = int(getattr(cfg, 'branch_spur', 0) or 0) or default_spur(int(G.image_size))
+    kw = dict(n_images=int(getattr(cfg, 'branch_images', 8192)), batch_size=int(cfg.batch_size),
+              seed=int(getattr(cfg, 'branch_seed', 0)), min_size=int(getattr(cfg, 'branch_min_size', 1)), spur=spur)
+    res, metric = evaluate_branches(G, dataset, return_metric=True, **kw)
+    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "min_size": kw["min_size"], "spur": spur}
+    entry.update({k: ({a: (list(b) if isinstance(b, list) else b) for a, b in v.items()} if isinstance(v, dict) else v) for k, v in res.items()})
+    if metric.active and getattr(trainer, "ema_enabled", False):
+        with trainer.averaged_generator():
+            ema = evaluate_branches(G, None, real_from=metric, **kw)      # (the data's side is the same: not scored twice)
+        entry["skipped_fake_ema"] = ema["skipped_fake"]
+        for name in BRANCH_STATISTICS:
+            if name in ema:
+                entry[name + "_ema"] = {k: ema[name][k] for k in ("fake", "fake_sem", "ks")}
+        if "profile" in ema and "profile" in entry:
+            n = len(entry["profile"]["length"])
+            entry["profile_ema"] = {"fake": (list(ema["profile"]["fake"]) + [0.0] * n)[:n]}
+    if "forks" not in res:
+        log("Epoch:{}, branches: {}".format(epoch, res["note"]))
+    else:
+        one = lambda r: "forks {:.2f} (KS {:.3f}), terminals {:.2f} of {:.4f}, spurs {:.2f} (KS {:.3f}), links of {:.4f}".format(   # noqa: E731
+            r["forks"]["fake"], r["forks"]["ks"], r["terminals"]["fake"], r["terminal_length"]["fake"], r["spurs"]["fake"],
+            r["spurs"]["ks"], r["link_length"]["fake"])
+        line = "Epoch:{}, branches over {} images, spur {}: {}; data: forks {:.2f}, terminals {:.2f} of {:.4f}, spurs {:.2f}, links of {:.4f}".format(
+            epoch, res["images"], spur, one(res), res["forks"]["real"], res["terminals"]["real"], res["terminal_length"]["real"],
+            res["spurs"]["real"], res["link_length"]["real"])
+        if "forks_ema" in entry:
+            line += "; averaged generator: " + one({n: entry[n + "_ema"] for n in BRANCH_STATISTICS})
+        log(line)
+    if checkpoint is not None:
+        checkpoint.BRANCH.append(entry)
+    return entry
+
+
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
                 samples_dir=None, on_epoch=None, process_group=None, draws=None):
     """The reference's epoch loop (train.py:298-451) over a PGGANTrainer.
@@ -1725,7 +1769,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     every rank; rank 0 alone logs, saves and plots.  With one rank nothing of this is active.
     cfg.swd_period > 0: rank 0 scores every checkpoint whose epoch is a multiple of it (`score_swd`) before it is written; the other
     ranks wait at the checkpoint's barrier.  cfg.msssim_period > 0: the same with `score_msssim`; cfg.spectrum_period > 0: with `score_spectrum`;
-    cfg.morph_period > 0: with `score_morph`; cfg.skeleton_period > 0: with `score_skeleton`; cfg.sholl_period > 0: with `score_sholl`.
+    cfg.morph_period > 0: with `score_morph`; cfg.skeleton_period > 0: with `score_skeleton`; cfg.sholl_period > 0: with `score_sholl`;
+    cfg.branch_period > 0: with `score_branches`.
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
     (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
@@ -1740,6 +1785,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     morph_period = int(getattr(cfg, 'morph_period', 0) or 0)
     skeleton_period = int(getattr(cfg, 'skeleton_period', 0) or 0)
     sholl_period = int(getattr(cfg, 'sholl_period', 0) or 0)
+    branch_period = int(getattr(cfg, 'branch_period', 0) or 0)
     G, D = trainer.G, trainer.D
     dev = trainer.device
     epoch_final = epoch_final if epoch_final is not None else cfg.N_epochs + 1
@@ -1858,6 +1904,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
                     score_skeleton(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 if sholl_period > 0 and epoch % sholl_period == 0:
                     score_sholl(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
+                if branch_period > 0 and epoch % branch_period == 0:
+                    score_branches(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
                 checkpoint.save_state(epoch)
                 if samples_dir is not None:
                     from .utils import plot_gen_samples
@@ -2063,6 +2111,14 @@ def build_arg_parser():
     p.add_argument('--sholl_images', type=int, default=8192, help='images per side of one arbor-geometry evaluation')
     p.add_argument('--sholl_seed', type=int, default=0, help='seed of the arbor-geometry latents and augmentations')
     p.add_argument('--sholl_min_size', type=int, default=1, help='components below this many pixels are not measured (1 drops none)')
+    p.add_argument('--branch_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the arbor '
+                                                                'branches (forks, spurs, branch lengths) of samples against the data '
+                                                                '(metrics.py); 0: off')
+    p.add_argument('--branch_images', type=int, default=8192, help='images per side of one arbor-branch evaluation')
+    p.add_argument('--branch_seed', type=int, default=0, help='seed of the arbor-branch latents and augmentations')
+    p.add_argument('--branch_min_size', type=int, default=1, help='components below this many pixels are not measured (1 drops none)')
+    p.add_argument('--branch_spur', type=int, default=0, help='terminal branches below this many pixels are pruned as thinning spurs '
+                                                              '(0: max(2, image size / 32))')
     p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
                                                         'launch.py); batch_size stays the global batch')
     return p

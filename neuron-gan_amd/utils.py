@@ -52,7 +52,9 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # and `morph_period` adds 'MORPH': a list of {epoch, image_size, images, min_size, skipped_real, skipped_fake[, note], fill, components,
 # largest_share, dimension: {real, real_sem, fake, fake_sem, ks}[, skipped_fake_ema, <statistic>_ema: {fake, fake_sem, ks}]}, and
 # `skeleton_period` adds 'SKELETON': a list of the same shape with the statistics length, tips, junctions, width, and `sholl_period`
-# adds 'SHOLL': the same with calibre, soma, sholl_peak, sholl_radius, reach and profile: {radius, real, fake}[, profile_ema: {fake}].
+# adds 'SHOLL': the same with calibre, soma, sholl_peak, sholl_radius, reach and profile: {radius, real, fake}[, profile_ema: {fake}], and
+# `branch_period` adds 'BRANCH': the same with spur, forks, nodes, terminals, spurs, terminal_length, link_length, longest and profile:
+# {length, real, fake}[, profile_ema: {fake}].
 # ---------------------------------------------------------------------------------------------------------------------
 import os  # noqa: E402
 
@@ -99,6 +101,7 @@ SPECTRUM_KEY = 'SPECTRUM'
 MORPH_KEY = 'MORPH'
 SKELETON_KEY = 'SKELETON'
 SHOLL_KEY = 'SHOLL'
+BRANCH_KEY = 'BRANCH'
 
 
 class Checkpointer:
@@ -123,6 +126,7 @@ class Checkpointer:
         self.MORPH = []             # the same for `morph_period`
         self.SKELETON = []          # the same for `skeleton_period`
         self.SHOLL = []             # the same for `sholl_period`
+        self.BRANCH = []            # the same for `branch_period`
 
     def save_state(self, epoch):
         self.epoch = epoch
@@ -153,6 +157,8 @@ class Checkpointer:
             checkpoint_dict[SKELETON_KEY] = [dict(entry) for entry in self.SKELETON]
         if self.SHOLL:
             checkpoint_dict[SHOLL_KEY] = [dict(entry) for entry in self.SHOLL]
+        if self.BRANCH:
+            checkpoint_dict[BRANCH_KEY] = [dict(entry) for entry in self.BRANCH]
         torch.save(checkpoint_dict, self.filename)
         if epoch % self.extra_checkpoint_period == 0:
             base, ext = os.path.splitext(self.filename)
@@ -178,6 +184,7 @@ class Checkpointer:
             self.MORPH = [dict(entry) for entry in checkpoint_dict.get(MORPH_KEY, [])]
             self.SKELETON = [dict(entry) for entry in checkpoint_dict.get(SKELETON_KEY, [])]
             self.SHOLL = [dict(entry) for entry in checkpoint_dict.get(SHOLL_KEY, [])]
+            self.BRANCH = [dict(entry) for entry in checkpoint_dict.get(BRANCH_KEY, [])]
         if 'Generator_attrs' in checkpoint_dict and 'Discriminator_attrs' in checkpoint_dict:
             # (the WGAN nets list no saved_attrs: the reference fails there, utils.py:194-198; here they count as empty)
             gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in getattr(self.Generator_net, 'saved_attrs', [])}
