@@ -8,7 +8,9 @@ The directory name carries a hyphen, so it is loaded under the module name `neur
     wgan_ops.py        first-order operators of the WGAN nets (stride-2 convolutions, BatchNorm-on-load)
     models.py          Generator_PG / Discriminator_PG (and Generator_wgan / Discriminator_wgan) with the reference's surface and state_dict keys
     loss_functions.py  D_W_loss / G_W_loss / D_grad_pen_loss
-    utils.py           sample_latent_vec
+    utils.py           sample_latent_vec, the Checkpointer, sample grids
+    metric_table.py    the checkpoint metrics as one table: configuration names, flags, checkpoint keys, functions, titles
+    scoring.py         scoring a checkpoint during training: one routine over that table (`score`, `score_due`, `score_<metric>`)
     configs/config.py  module-as-singleton configuration
     train.py           the G/D step driver (flat parameters, fused Adam, data-parallel gradient exchange), epoch driver, CLI
     eval.py            sample grid from a checkpoint (the reference's eval.py), optionally from the averaged generator

@@ -15,6 +15,8 @@ from types import FunctionType, ModuleType
 import numpy as np
 import torch
 
+from ..metric_table import METRICS, settings
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 _DEFAULTS = dict(
@@ -29,13 +31,8 @@ _DEFAULTS = dict(
     ID=uuid.uuid4().hex[:4], RMSprop=False, learning_rate=0.0001, batch_size=8, N_epochs=150000, N_epochs_session=None,
     beta1=0.5, sim_loss_lambda=0.0, sim_loss_lambda_decay_rate=0.0, drift_epsilon=0.001, resume=False, N_workers=2,
     seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
-    swd_period=0, swd_images=8192, swd_seed=0,
-    msssim_period=0, msssim_pairs=10000, msssim_seed=0,
-    spectrum_period=0, spectrum_images=8192, spectrum_seed=0,
-    morph_period=0, morph_images=8192, morph_seed=0, morph_min_size=1,
-    skeleton_period=0, skeleton_images=8192, skeleton_seed=0, skeleton_min_size=1,
-    sholl_period=0, sholl_images=8192, sholl_seed=0, sholl_min_size=1,
-    branch_period=0, branch_images=8192, branch_seed=0, branch_min_size=1, branch_spur=0,
+    # the checkpoint metrics: <prefix>_period, _images (or _pairs), _seed and the metric's own options, row by row
+    **{name: default for m in METRICS for name, _, default, _ in settings(m)},
     diffaug='', diffaug_p=1.0, diffaug_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
@@ -96,43 +93,14 @@ def validate_configs(create_dirs=False):
     # the averaged generator (an addition of this implementation): 0 is off, otherwise the decay
     if not (isinstance(g['ema_beta'], (int, float)) and 0 <= g['ema_beta'] < 1):
         raise ValueError(f"ema_beta={g['ema_beta']!r} must lie in [0, 1)")
-    # the sliced Wasserstein distance at checkpoints (an addition of this implementation): swd_period 0 is off, otherwise every
-    # checkpoint whose epoch is a multiple of it is scored on swd_images images per side
-    for name, lowest in (('swd_period', 0), ('swd_images', 1), ('swd_seed', 0)):
-        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
-            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
-    # MS-SSIM between pairs of samples at checkpoints (an addition of this implementation), with the same meaning: msssim_period 0 is
-    # off, otherwise every checkpoint whose epoch is a multiple of it is scored on msssim_pairs pairs per side
-    for name, lowest in (('msssim_period', 0), ('msssim_pairs', 1), ('msssim_seed', 0)):
-        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
-            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
-    # the radial power spectrum of samples against the data at checkpoints (an addition of this implementation), with the same meaning:
-    # spectrum_period 0 is off, otherwise every checkpoint whose epoch is a multiple of it is scored on spectrum_images images per side
-    for name, lowest in (('spectrum_period', 0), ('spectrum_images', 1), ('spectrum_seed', 0)):
-        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
-            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
-    # arbor morphology (connectivity, box-counting dimension) of samples against the data at checkpoints (an addition of this
-    # implementation), with the same meaning: morph_period 0 is off, otherwise every checkpoint whose epoch is a multiple of it is scored
-    # on morph_images images per side; components below morph_min_size pixels are dropped (1 drops none)
-    for name, lowest in (('morph_period', 0), ('morph_images', 1), ('morph_seed', 0), ('morph_min_size', 1)):
-        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
-            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
-    # arbor skeleton (thinning: length, tips, junctions, width) of samples against the data at checkpoints (an addition of this
-    # implementation), with the same meaning as the morph_* names; stages above 512 x 512 are noted, not scored
-    for name, lowest in (('skeleton_period', 0), ('skeleton_images', 1), ('skeleton_seed', 0), ('skeleton_min_size', 1)):
-        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
-            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
-    # arbor geometry (distance transform, soma, Sholl profile) of samples against the data at checkpoints (an addition of this
-    # implementation), with the same meaning as the skeleton_* names; it thins, so stages above 512 x 512 are noted, not scored
-    for name, lowest in (('sholl_period', 0), ('sholl_images', 1), ('sholl_seed', 0), ('sholl_min_size', 1)):
-        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
-            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
-    # arbor branches (nodes, spur pruning, branch lengths) of samples against the data at checkpoints (an addition of this
-    # implementation), with the same meaning as the sholl_* names; branch_spur: terminal branches below that many pixels are pruned as
-    # thinning spurs, 0: max(2, image size / 32)
-    for name, lowest in (('branch_period', 0), ('branch_images', 1), ('branch_seed', 0), ('branch_min_size', 1), ('branch_spur', 0)):
-        if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
-            raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
+    # the metrics scored at checkpoints (additions of this implementation, one row of metric_table.METRICS each): <prefix>_period 0 is
+    # off, otherwise every checkpoint whose epoch is a multiple of it is scored on <prefix>_images images (msssim_pairs pairs) per side,
+    # drawn with <prefix>_seed; the arbor metrics drop components below <prefix>_min_size pixels (1 drops none) and branch_spur prunes
+    # terminal branches below that many pixels as thinning spurs, 0: max(2, image size / 32)
+    for m in METRICS:
+        for name, lowest, _, _ in settings(m):
+            if not (isinstance(g[name], int) and not isinstance(g[name], bool) and g[name] >= lowest):
+                raise ValueError(f"{name}={g[name]!r} must be an integer >= {lowest}")
     # differentiable augmentation of the critic's inputs (an addition of this implementation): diffaug '' is off, otherwise a comma
     # list of groups, each applied to each sample with probability diffaug_p; diffaug_seed seeds the parameters' private stream
     groups = [s.strip() for s in g['diffaug'].split(',')] if isinstance(g['diffaug'], str) else None
@@ -198,6 +166,3 @@ def import_configs(filename, overwritten_configs=None, create_dirs=False):
 
 
 define_ID_dependent_configs()
-
-if __name__ == '__main__':
-    print_configs()

@@ -60,6 +60,7 @@ real endings, the lengths of terminal and internal branches (csrc/branch.hip):
     branch_statistics                          per image: forks, nodes, terminals, spurs, terminal_length, link_length, longest, scored,
                                                hist
     Branches, evaluate_branches                per-image values of both sets as above, and the mean branch-length histogram of each side"""
+import contextlib
 import math
 
 import torch
@@ -313,6 +314,57 @@ class SWD:
         return {"levels": list(self.levels), "swd": swd, "mean": sum(swd) / len(swd)}
 
 
+@contextlib.contextmanager
+def _private_stream(dataset, size, seed):
+    """for the duration, `dataset` (None: nothing to do) serves images `size` pixels wide and draws its augmentations from a private
+    generator seeded seed + 1; its own generator, left where it was, and its image size are restored afterwards"""
+    if dataset is None:
+        yield
+        return
+    aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
+    old_size = dataset.image_size
+    own_gen = getattr(dataset, "gen", None)
+    dataset.set_image_size(size)
+    if own_gen is not None:
+        dataset.gen = aug
+    try:
+        yield
+    finally:
+        if own_gen is not None:
+            dataset.gen = own_gen
+        dataset.set_image_size(old_size)
+
+
+def _real_batch(dataset, idx, device):
+    """the images `idx` through the data set's own augmentation chain, on the device"""
+    if hasattr(dataset, "batch"):
+        return dataset.batch(idx)
+    return torch.stack([dataset[j] for j in idx]).to(device)
+
+
+def _latents(generator, n, lat, device):
+    """n latents of the sampler's distribution (utils.sample_latent_vec, 'randn': normal draws clamped to [-5, 5], projected on the unit
+    sphere) from the private generator `lat`"""
+    z = torch.randn(n, generator.latent_dim, generator=lat).clamp(-5, 5)
+    return (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
+
+
+def _feed_two_sets(metric, generator, dataset, n_images, batch_size, seed):
+    """the loop of evaluate_swd, evaluate_spectrum and the arbor metrics: per minibatch, feed `metric` the reals (indices cycled, under
+    _private_stream; dataset None: the data side is already there) and then the fakes under no_grad from latents of a private generator
+    seeded seed + 2; one minibatch of images alive at a time"""
+    lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
+    with _private_stream(dataset, metric.image_size, seed):
+        for i in range(0, n_images, batch_size):
+            b = min(batch_size, n_images - i)
+            if dataset is not None:
+                metric.feed("real", _real_batch(dataset, [(i + j) % len(dataset) for j in range(b)], metric.device))
+            with torch.no_grad():
+                fakes = generator(_latents(generator, b, lat, metric.device)).detach()
+            metric.feed("fake", fakes)
+            del fakes
+
+
 def evaluate_swd(generator, dataset, n_images=8192, batch_size=64, seed=0, nhoods_per_image=128, dir_repeats=4, dirs_per_repeat=128):
     """SWD of `generator` against `dataset` at the generator's current resolution: n_images reals through the dataset's own
     augmentation chain (its indices cycled, its random draws taken from a private generator so that the training stream is left
@@ -326,34 +378,7 @@ def evaluate_swd(generator, dataset, n_images=8192, batch_size=64, seed=0, nhood
                  dirs_per_repeat=dirs_per_repeat, seed=seed, device=device, n_images=n_images)
     if not metric.levels:
         return metric.result()
-    aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
-    lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
-    old_size = dataset.image_size
-    own_gen = getattr(dataset, "gen", None)
-    dataset.set_image_size(size)
-    if own_gen is not None:
-        dataset.gen = aug
-    try:
-        n_data = len(dataset)
-        for i in range(0, n_images, batch_size):
-            b = min(batch_size, n_images - i)
-            idx = [(i + j) % n_data for j in range(b)]
-            if hasattr(dataset, "batch"):
-                reals = dataset.batch(idx)
-            else:
-                reals = torch.stack([dataset[j] for j in idx]).to(device)
-            metric.feed("real", reals)
-            del reals
-            z = torch.randn(b, generator.latent_dim, generator=lat).clamp(-5, 5)
-            z = (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
-            with torch.no_grad():
-                fakes = generator(z).detach()
-            metric.feed("fake", fakes)
-            del fakes
-    finally:
-        if own_gen is not None:
-            dataset.gen = own_gen
-        dataset.set_image_size(old_size)
+    _feed_two_sets(metric, generator, dataset, n_images, batch_size, seed)
     return metric.result()
 
 
@@ -514,36 +539,17 @@ def evaluate_msssim(generator, dataset=None, n_pairs=10000, batch_size=64, seed=
         raise ValueError(f"n_pairs={n_pairs} and batch_size={batch_size} must be positive")
     lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
     for i in range(0, n_pairs, batch_size):
-        n = 2 * min(batch_size, n_pairs - i)
-        z = torch.randn(n, generator.latent_dim, generator=lat).clamp(-5, 5)
-        z = (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
         with torch.no_grad():
-            fakes = channels_last(generator(z).detach())
+            fakes = channels_last(generator(_latents(generator, 2 * min(batch_size, n_pairs - i), lat, device)).detach())
         metric.feed("fake", fakes[0::2].contiguous(), fakes[1::2].contiguous())
         del fakes
     if dataset is not None:
-        aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
-        old_size = dataset.image_size
-        own_gen = getattr(dataset, "gen", None)
-        dataset.set_image_size(size)
-        if own_gen is not None:
-            dataset.gen = aug
-        try:
-            n_data = len(dataset)
+        with _private_stream(dataset, size, seed):
             for i in range(0, n_pairs, batch_size):
-                n = 2 * min(batch_size, n_pairs - i)
-                idx = [(2 * i + j) % n_data for j in range(n)]
-                if hasattr(dataset, "batch"):
-                    reals = dataset.batch(idx)
-                else:
-                    reals = torch.stack([dataset[j] for j in idx]).to(device)
-                reals = channels_last(reals)
+                idx = [(2 * i + j) % len(dataset) for j in range(2 * min(batch_size, n_pairs - i))]
+                reals = channels_last(_real_batch(dataset, idx, device))
                 metric.feed("real", reals[0::2].contiguous(), reals[1::2].contiguous())
                 del reals
-        finally:
-            if own_gen is not None:
-                dataset.gen = own_gen
-            dataset.set_image_size(old_size)
     return metric.result()
 
 
@@ -698,36 +704,7 @@ def evaluate_spectrum(generator, dataset, n_images=8192, batch_size=64, seed=0, 
     n_images, batch_size = int(n_images), int(batch_size)
     if n_images < 1 or batch_size < 1:
         raise ValueError(f"n_images={n_images} and batch_size={batch_size} must be positive")
-    aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
-    lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
-    if real_from is None:
-        old_size = dataset.image_size
-        own_gen = getattr(dataset, "gen", None)
-        dataset.set_image_size(size)
-        if own_gen is not None:
-            dataset.gen = aug
-    try:
-        for i in range(0, n_images, batch_size):
-            b = min(batch_size, n_images - i)
-            if real_from is None:
-                idx = [(i + j) % len(dataset) for j in range(b)]
-                if hasattr(dataset, "batch"):
-                    reals = dataset.batch(idx)
-                else:
-                    reals = torch.stack([dataset[j] for j in idx]).to(device)
-                metric.feed("real", reals)
-                del reals
-            z = torch.randn(b, generator.latent_dim, generator=lat).clamp(-5, 5)
-            z = (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
-            with torch.no_grad():
-                fakes = generator(z).detach()
-            metric.feed("fake", fakes)
-            del fakes
-    finally:
-        if real_from is None:
-            if own_gen is not None:
-                dataset.gen = own_gen
-            dataset.set_image_size(old_size)
+    _feed_two_sets(metric, generator, dataset if real_from is None else None, n_images, batch_size, seed)
     return (metric.result(), metric) if return_metric else metric.result()
 
 
@@ -959,6 +936,18 @@ class Morphology:
             out[name] = row
         return out
 
+    def _profile(self, axis, bins, scale):
+        """{axis: [i scale], 'real', 'fake': per side the mean over its scored images of the `bins` integer rows a subclass's _rows()
+        appends below `scored` (exact int64 sums divided by their number)}, cut after the last bin at which either side is non-zero"""
+        k = len(self.STATISTICS)
+        mean = {}
+        for which in ("real", "fake"):
+            v = torch.cat(self.values[which], dim=1).cpu()
+            c = v[k + 1:][:, v[k] > 0.5].to(torch.int64)
+            mean[which] = [int(t) / float(c.shape[1]) for t in c.sum(dim=1)]
+        n = max([i + 1 for i in range(bins) if mean["real"][i] or mean["fake"][i]], default=0)
+        return {axis: [i * scale for i in range(n)], "real": mean["real"][:n], "fake": mean["fake"][:n]}
+
 
 def evaluate_morphology(generator, dataset, n_images=8192, batch_size=64, seed=0, otsu_class=1, min_size=1, real_from=None,
                         return_metric=False):
@@ -991,50 +980,33 @@ def _evaluate_two_sets(metric_class, generator, dataset, n_images, batch_size, s
     n_images, batch_size = int(n_images), int(batch_size)
     if n_images < 1 or batch_size < 1:
         raise ValueError(f"n_images={n_images} and batch_size={batch_size} must be positive")
-    aug = torch.Generator(device="cpu").manual_seed(int(seed) + 1)
-    lat = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
-    if real_from is None:
-        old_size = dataset.image_size
-        own_gen = getattr(dataset, "gen", None)
-        dataset.set_image_size(size)
-        if own_gen is not None:
-            dataset.gen = aug
-    try:
-        for i in range(0, n_images, batch_size):
-            b = min(batch_size, n_images - i)
-            if real_from is None:
-                idx = [(i + j) % len(dataset) for j in range(b)]
-                if hasattr(dataset, "batch"):
-                    reals = dataset.batch(idx)
-                else:
-                    reals = torch.stack([dataset[j] for j in idx]).to(device)
-                metric.feed("real", reals)
-                del reals
-            z = torch.randn(b, generator.latent_dim, generator=lat).clamp(-5, 5)
-            z = (z / z.norm(p=2, dim=1, keepdim=True)).to(device)
-            with torch.no_grad():
-                fakes = generator(z).detach()
-            metric.feed("fake", fakes)
-            del fakes
-    finally:
-        if real_from is None:
-            if own_gen is not None:
-                dataset.gen = own_gen
-            dataset.set_image_size(old_size)
+    _feed_two_sets(metric, generator, dataset if real_from is None else None, n_images, batch_size, seed)
     return (metric.result(), metric) if return_metric else metric.result()
 
 
-def format_morphology(result, title="Arbor morphology"):
-    """the table eval.py prints: one row per statistic -- data, generated (mean +- standard error) and the KS distance"""
-    if "fill" not in result:
+def _format_arbor(result, title, statistics, width=14, profile=None):
+    """the table eval.py prints for an arbor metric: one row per statistic -- data, generated (mean +- standard error) and the KS
+    distance --, labels `width` wide; profile (axis, wording): then the mean profile of either side, one number per bin, and the
+    wording formatted with the bins' step"""
+    if statistics[0] not in result:
         return f"{title}: {result['note']}"
     pm = lambda v, e: f"{v:10.4f} +- {e:8.4f}" if e is not None else f"{v:10.4f}" + " " * 12   # noqa: E731
     rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
-            f"{result['skipped_fake']} generated)", f"{'':>14s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
-    for name in MORPH_STATISTICS:
+            f"{result['skipped_fake']} generated)", f"{'':>{width}s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
+    for name in statistics:
         r = result[name]
-        rows.append(f"{name:>14s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
+        rows.append(f"{name:>{width}s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
+    if profile is not None:
+        axis, wording = profile
+        p = result["profile"]
+        step = p[axis][1] if len(p[axis]) > 1 else 0.0
+        rows.append(f"{'profile data':>{width}s} " + " ".join(f"{v:.2f}" for v in p["real"]) + "   (" + wording.format(step) + ")")
+        rows.append(f"{'generated':>{width}s} " + " ".join(f"{v:.2f}" for v in p["fake"]))
     return "\n".join(rows)
+
+
+def format_morphology(result, title="Arbor morphology"):
+    return _format_arbor(result, title, MORPH_STATISTICS)
 
 
 # ---- arbor skeleton: thinning, tips, junctions and length (csrc/skeleton.hip; include/ngan.h, last section) ------------------------------
@@ -1108,16 +1080,7 @@ def evaluate_skeleton(generator, dataset, n_images=8192, batch_size=64, seed=0, 
 
 
 def format_skeleton(result, title="Arbor skeleton"):
-    """the table eval.py prints: one row per statistic -- data, generated (mean +- standard error) and the KS distance"""
-    if "length" not in result:
-        return f"{title}: {result['note']}"
-    pm = lambda v, e: f"{v:10.4f} +- {e:8.4f}" if e is not None else f"{v:10.4f}" + " " * 12   # noqa: E731
-    rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
-            f"{result['skipped_fake']} generated)", f"{'':>14s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
-    for name in SKELETON_STATISTICS:
-        r = result[name]
-        rows.append(f"{name:>14s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
-    return "\n".join(rows)
+    return _format_arbor(result, title, SKELETON_STATISTICS)
 
 
 # ---- arbor geometry: distance transform, soma and Sholl profile (csrc/sholl.hip; include/ngan.h, last section) ---------------------------
@@ -1209,17 +1172,8 @@ class Sholl(Skeleton):
         image widths, 'real', 'fake': the mean crossings of that ring over the scored images of the side (exact int64 sums divided by
         their number)}, cut after the last ring at which either side has a crossing"""
         out = super().result()
-        if self.STATISTICS[0] not in out:
-            return out
-        k = len(self.STATISTICS)
-        mean = {}
-        for which in ("real", "fake"):
-            v = torch.cat(self.values[which], dim=1).cpu()
-            c = v[k + 1:][:, v[k] > 0.5].to(torch.int64)
-            mean[which] = [int(t) / float(c.shape[1]) for t in c.sum(dim=1)]
-        n = max([i + 1 for i in range(SHOLL_BINS) if mean["real"][i] or mean["fake"][i]], default=0)
-        scale = sholl_step(self.image_size) / float(self.image_size)
-        out["profile"] = {"radius": [i * scale for i in range(n)], "real": mean["real"][:n], "fake": mean["fake"][:n]}
+        if self.STATISTICS[0] in out:
+            out["profile"] = self._profile("radius", SHOLL_BINS, sholl_step(self.image_size) / float(self.image_size))
         return out
 
 
@@ -1232,21 +1186,8 @@ def evaluate_sholl(generator, dataset, n_images=8192, batch_size=64, seed=0, ots
 
 
 def format_sholl(result, title="Arbor geometry"):
-    """the table eval.py prints: one row per statistic -- data, generated (mean +- standard error) and the KS distance --, then the mean
-    Sholl profile of either side, one number per ring"""
-    if "calibre" not in result:
-        return f"{title}: {result['note']}"
-    pm = lambda v, e: f"{v:10.4f} +- {e:8.4f}" if e is not None else f"{v:10.4f}" + " " * 12   # noqa: E731
-    rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
-            f"{result['skipped_fake']} generated)", f"{'':>14s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
-    for name in SHOLL_STATISTICS:
-        r = result[name]
-        rows.append(f"{name:>14s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
-    p = result["profile"]
-    step = p["radius"][1] if len(p["radius"]) > 1 else 0.0
-    rows.append(f"{'profile data':>14s} " + " ".join(f"{v:.2f}" for v in p["real"]) + f"   (mean crossings per ring, rings {step:.4f} image widths apart)")
-    rows.append(f"{'generated':>14s} " + " ".join(f"{v:.2f}" for v in p["fake"]))
-    return "\n".join(rows)
+    """the table of _format_arbor, then the mean Sholl profile of either side, one number per ring"""
+    return _format_arbor(result, title, SHOLL_STATISTICS, profile=("radius", "mean crossings per ring, rings {:.4f} image widths apart"))
 
 
 # ---- arbor branches: nodes, spur pruning and branch lengths (csrc/branch.hip; include/ngan.h, last section) -------------------------------
@@ -1338,17 +1279,8 @@ class Branches(Skeleton):
         edges k max(1, R / 128) / R in image widths, 'real', 'fake': the mean number of terminal and link branches of that length over
         the scored images of the side (exact int64 sums divided by their number)}, cut after the last bin that either side fills"""
         out = super().result()
-        if self.STATISTICS[0] not in out:
-            return out
-        k = len(self.STATISTICS)
-        mean = {}
-        for which in ("real", "fake"):
-            v = torch.cat(self.values[which], dim=1).cpu()
-            c = v[k + 1:][:, v[k] > 0.5].to(torch.int64)
-            mean[which] = [int(t) / float(c.shape[1]) for t in c.sum(dim=1)]
-        n = max([i + 1 for i in range(BRANCH_BINS) if mean["real"][i] or mean["fake"][i]], default=0)
-        scale = max(1, self.image_size // 128) / float(self.image_size)
-        out["profile"] = {"length": [i * scale for i in range(n)], "real": mean["real"][:n], "fake": mean["fake"][:n]}
+        if self.STATISTICS[0] in out:
+            out["profile"] = self._profile("length", BRANCH_BINS, max(1, self.image_size // 128) / float(self.image_size))
         return out
 
 
@@ -1363,21 +1295,8 @@ def evaluate_branches(generator, dataset, n_images=8192, batch_size=64, seed=0, 
 
 
 def format_branches(result, title="Arbor branches"):
-    """the table eval.py prints: one row per statistic -- data, generated (mean +- standard error) and the KS distance --, then the mean
-    branch-length histogram of either side, one number per bin"""
-    if "forks" not in result:
-        return f"{title}: {result['note']}"
-    pm = lambda v, e: f"{v:10.4f} +- {e:8.4f}" if e is not None else f"{v:10.4f}" + " " * 12   # noqa: E731
-    rows = [f"{title} ({result['images']} images per side; not scored: {result['skipped_real']} of the data, "
-            f"{result['skipped_fake']} generated)", f"{'':>16s} {'data':>22s} {'generated':>22s} {'KS':>7s}"]
-    for name in BRANCH_STATISTICS:
-        r = result[name]
-        rows.append(f"{name:>16s} {pm(r['real'], r['real_sem'])} {pm(r['fake'], r['fake_sem'])} {r['ks']:7.3f}")
-    p = result["profile"]
-    step = p["length"][1] if len(p["length"]) > 1 else 0.0
-    rows.append(f"{'profile data':>16s} " + " ".join(f"{v:.2f}" for v in p["real"]) + f"   (mean branches per bin, bins {step:.4f} image widths wide)")
-    rows.append(f"{'generated':>16s} " + " ".join(f"{v:.2f}" for v in p["fake"]))
-    return "\n".join(rows)
+    """the table of _format_arbor, labels 16 wide, then the mean branch-length histogram of either side, one number per bin"""
+    return _format_arbor(result, title, BRANCH_STATISTICS, width=16, profile=("length", "mean branches per bin, bins {:.4f} image widths wide"))
 
 
 def format_table(result, title="SWD x 1e3"):

@@ -25,6 +25,9 @@ import torch.distributed as dist
 from . import _C, ops, wgan_ops
 from .launch import check_sharding, longest_share, shard_bounds
 from .loss_functions import D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_W_loss
+from .metric_table import METRICS, settings
+from .scoring import (score_branches, score_due, score_morph, score_msssim, score_sholl, score_skeleton,  # noqa: F401
+                      score_spectrum, score_swd)
 from .utils import sample_latent_vec, sample_latent_vec_device
 
 ADAM_CHUNK = 4096  # elements per work item of ngan_adam_step / ngan_rmsprop_step (must match csrc/adam.hip)
@@ -1507,251 +1510,6 @@ def _clone_draws(fresh):
     return {name: ([x.clone() for x in v] if isinstance(v, (list, tuple)) else v.clone()) for name, v in fresh.items()}
 
 
-def score_swd(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
-    """One SWD evaluation of the training generator and, when the trainer averages, of the averaged one (metrics.evaluate_swd with
-    cfg.swd_images images per side in minibatches of cfg.batch_size, seed cfg.swd_seed): logged in one line and appended to
-    checkpoint.SWD as {epoch, image_size, levels, swd, swd_ema}.  Eager, outside any captured graph, no collective; it draws from
-    private generators only, so the run trains on as if it had not happened."""
-    from .metrics import evaluate_swd
-    G = trainer.G
-    kw = dict(n_images=int(getattr(cfg, 'swd_images', 8192)), batch_size=int(cfg.batch_size), seed=int(getattr(cfg, 'swd_seed', 0)))
-    res = evaluate_swd(G, dataset, **kw)
-    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "levels": list(res["levels"]), "swd": list(res["swd"]),
-             "swd_ema": None}
-    if getattr(trainer, "ema_enabled", False):
-        with trainer.averaged_generator():
-            entry["swd_ema"] = list(evaluate_swd(G, dataset, **kw)["swd"])
-    fmt = lambda v: "[" + ", ".join("{:.3f}".format(x) for x in v) + "]"   # noqa: E731
-    if not entry["levels"]:
-        log("Epoch:{}, SWD: {}".format(epoch, res["note"]))
-    else:
-        log("Epoch:{}, SWD x1e3 at {}: {}{}".format(epoch, entry["levels"], fmt(entry["swd"]),
-                                                   "" if entry["swd_ema"] is None else ", averaged generator: " + fmt(entry["swd_ema"])))
-    if checkpoint is not None:
-        checkpoint.SWD.append(entry)
-    return entry
-
-
-def score_msssim(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
-    """One MS-SSIM evaluation between pairs of samples (metrics.evaluate_msssim with cfg.msssim_pairs pairs per side in minibatches of
-    cfg.batch_size, seed cfg.msssim_seed) of the training generator -- with the data set's own pair similarity next to it -- and, when
-    the trainer averages, of the averaged one: logged in one line and appended to checkpoint.MSSSIM as {epoch, image_size, scales,
-    fake, fake_ema, real, pairs}.  Eager, outside any captured graph, no collective; it draws from private generators only, so the
-    run trains on as if it had not happened."""
-    from .metrics import evaluate_msssim
-    G = trainer.G
-    kw = dict(n_pairs=int(getattr(cfg, 'msssim_pairs', 10000)), batch_size=int(cfg.batch_size), seed=int(getattr(cfg, 'msssim_seed', 0)))
-    res = evaluate_msssim(G, dataset, **kw)
-    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "scales": int(res["scales"]), "fake": res["fake"], "fake_ema": None,
-             "real": res["real"], "pairs": int(res["pairs"])}
-    if res["scales"] and getattr(trainer, "ema_enabled", False):
-        with trainer.averaged_generator():
-            entry["fake_ema"] = evaluate_msssim(G, None, **kw)["fake"]       # (the data's side is the same: not scored twice)
-    if not res["scales"]:
-        log("Epoch:{}, MS-SSIM: {}".format(epoch, res["note"]))
-    else:
-        log("Epoch:{}, MS-SSIM over {} pairs, {} scales: generated {:.5f}{}{}".format(
-            epoch, entry["pairs"], entry["scales"], entry["fake"],
-            "" if entry["fake_ema"] is None else ", averaged generator {:.5f}".format(entry["fake_ema"]),
-            "" if entry["real"] is None else ", data {:.5f}".format(entry["real"])))
-    if checkpoint is not None:
-        checkpoint.MSSSIM.append(entry)
-    return entry
-
-
-def score_spectrum(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
-    """One radial-power-spectrum evaluation (metrics.evaluate_spectrum with cfg.spectrum_images images per side in minibatches of
-    cfg.batch_size, seed cfg.spectrum_seed) of the training generator against the data set and, when the trainer averages, of the
-    averaged one: logged in one line and appended to checkpoint.SPECTRUM as {epoch, image_size, images, k, real, fake, ratio_db,
-    distance_db, high_db} plus {distance_db_ema, high_db_ema} with an averaged generator (the data's side is the same: it is not
-    stored twice).  Eager, outside any captured graph, no collective; it draws from private generators only, so the run trains on as
-    if it had not happened."""
-    from .metrics import evaluate_spectrum
-    G = trainer.G
-    kw = dict(n_images=int(getattr(cfg, 'spectrum_images', 8192)), batch_size=int(cfg.batch_size),
-              seed=int(getattr(cfg, 'spectrum_seed', 0)))
-    res, metric = evaluate_spectrum(G, dataset, return_metric=True, **kw)
-    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "images": int(res["images"]), "k": list(res["k"]),
-             "real": list(res["real"]), "fake": list(res["fake"]), "ratio_db": list(res["ratio_db"]),
-             "distance_db": res["distance_db"], "high_db": res["high_db"]}
-    if res["k"] and getattr(trainer, "ema_enabled", False):
-        with trainer.averaged_generator():
-            ema = evaluate_spectrum(G, None, real_from=metric, **kw)     # (the data's side is the same: not scored twice)
-        entry["distance_db_ema"], entry["high_db_ema"] = ema["distance_db"], ema["high_db"]
-    if not res["k"]:
-        log("Epoch:{}, spectrum: {}".format(epoch, res["note"]))
-    else:
-        db = lambda v: "-" if v is None else "{:+.2f} dB".format(v)   # noqa: E731
-        log("Epoch:{}, spectrum over {} images: distance {}, top octave {}{}".format(
-            epoch, entry["images"], db(entry["distance_db"]), db(entry["high_db"]),
-            "" if "high_db_ema" not in entry else ", averaged generator: distance {}, top octave {}".format(
-                db(entry["distance_db_ema"]), db(entry["high_db_ema"]))))
-    if checkpoint is not None:
-        checkpoint.SPECTRUM.append(entry)
-    return entry
-
-
-def score_morph(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
-    """One arbor-morphology evaluation (metrics.evaluate_morphology with cfg.morph_images images per side in minibatches of
-    cfg.batch_size, seed cfg.morph_seed, components below cfg.morph_min_size pixels dropped) of the training generator against the
-    data set and, when the trainer averages, of the averaged one: logged in one line and appended to checkpoint.MORPH as {epoch,
-    image_size, images, min_size, skipped_real, skipped_fake[, note]} plus, per statistic (fill, components, largest_share,
-    dimension), {real, real_sem, fake, fake_sem, ks}; with an averaged generator also skipped_fake_ema and <statistic>_ema: {fake,
-    fake_sem, ks} (the data's side is the same: it is not stored twice).  Eager, outside any captured graph, no collective; it draws
-    from private generators only, so the run trains on as if it had not happened."""
-    from .metrics import MORPH_STATISTICS, evaluate_morphology
-    G = trainer.G
-    kw = dict(n_images=int(getattr(cfg, 'morph_images', 8192)), batch_size=int(cfg.batch_size), seed=int(getattr(cfg, 'morph_seed', 0)),
-              min_size=int(getattr(cfg, 'morph_min_size', 1)))
-    res, metric = evaluate_morphology(G, dataset, return_metric=True, **kw)
-    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "min_size": kw["min_size"]}
-    entry.update({k: (dict(v) if isinstance(v, dict) else v) for k, v in res.items()})
-    if metric.active and getattr(trainer, "ema_enabled", False):
-        with trainer.averaged_generator():
-            ema = evaluate_morphology(G, None, real_from=metric, **kw)   # (the data's side is the same: not scored twice)
-        entry["skipped_fake_ema"] = ema["skipped_fake"]
-        for name in MORPH_STATISTICS:
-            if name in ema:
-                entry[name + "_ema"] = {k: ema[name][k] for k in ("fake", "fake_sem", "ks")}
-    if "fill" not in res:
-        log("Epoch:{}, morphology: {}".format(epoch, res["note"]))
-    else:
-        one = lambda r: "components {:.2f}, largest share {:.3f} (KS {:.3f}), fill {:.4f}, dimension {:.3f}".format(   # noqa: E731
-            r["components"]["fake"], r["largest_share"]["fake"], r["largest_share"]["ks"], r["fill"]["fake"], r["dimension"]["fake"])
-        line = "Epoch:{}, morphology over {} images: {}; data: components {:.2f}, largest share {:.3f}, fill {:.4f}, dimension {:.3f}".format(
-            epoch, res["images"], one(res), res["components"]["real"], res["largest_share"]["real"], res["fill"]["real"],
-            res["dimension"]["real"])
-        if "fill_ema" in entry:
-            line += "; averaged generator: " + one({n: entry[n + "_ema"] for n in MORPH_STATISTICS})
-        log(line)
-    if checkpoint is not None:
-        checkpoint.MORPH.append(entry)
-    return entry
-
-
-def score_skeleton(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
-    """One arbor-skeleton evaluation (metrics.evaluate_skeleton with cfg.skeleton_images images per side in minibatches of
-    cfg.batch_size, seed cfg.skeleton_seed, components below cfg.skeleton_min_size pixels dropped) of the training generator against
-    the data set and, when the trainer averages, of the averaged one: logged in one line and appended to checkpoint.SKELETON as {epoch,
-    image_size, images, min_size, skipped_real, skipped_fake[, note]} plus, per statistic (length, tips, junctions, width), {real,
-    real_sem, fake, fake_sem, ks}; with an averaged generator also skipped_fake_ema and <statistic>_ema: {fake, fake_sem, ks} (the
-    data's side is the same: it is not stored twice).  Eager, outside any captured graph, no collective; it draws from private
-    generators only, so the run trains on as if it had not happened."""
-    from .metrics import SKELETON_STATISTICS, evaluate_skeleton
-    G = trainer.G
-    kw = dict(n_images=int(getattr(cfg, 'skeleton_images', 8192)), batch_size=int(cfg.batch_size),
-              seed=int(getattr(cfg, 'skeleton_seed', 0)), min_size=int(getattr(cfg, 'skeleton_min_size', 1)))
-    res, metric = evaluate_skeleton(G, dataset, return_metric=True, **kw)
-    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "min_size": kw["min_size"]}
-    entry.update({k: (dict(v) if isinstance(v, dict) else v) for k, v in res.items()})
-    if metric.active and getattr(trainer, "ema_enabled", False):
-        with trainer.averaged_generator():
-            ema = evaluate_skeleton(G, None, real_from=metric, **kw)   # (the data's side is the same: not scored twice)
-        entry["skipped_fake_ema"] = ema["skipped_fake"]
-        for name in SKELETON_STATISTICS:
-            if name in ema:
-                entry[name + "_ema"] = {k: ema[name][k] for k in ("fake", "fake_sem", "ks")}
-    if "length" not in res:
-        log("Epoch:{}, skeleton: {}".format(epoch, res["note"]))
-    else:
-        one = lambda r: "length {:.3f}, tips {:.2f} (KS {:.3f}), junctions {:.2f}, width {:.3f}".format(   # noqa: E731
-            r["length"]["fake"], r["tips"]["fake"], r["tips"]["ks"], r["junctions"]["fake"], r["width"]["fake"])
-        line = "Epoch:{}, skeleton over {} images: {}; data: length {:.3f}, tips {:.2f}, junctions {:.2f}, width {:.3f}".format(
-            epoch, res["images"], one(res), res["length"]["real"], res["tips"]["real"], res["junctions"]["real"], res["width"]["real"])
-        if "length_ema" in entry:
-            line += "; averaged generator: " + one({n: entry[n + "_ema"] for n in SKELETON_STATISTICS})
-        log(line)
-    if checkpoint is not None:
-        checkpoint.SKELETON.append(entry)
-    return entry
-
-
-def score_sholl(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
-    """One arbor-geometry evaluation (metrics.evaluate_sholl with cfg.sholl_images images per side in minibatches of cfg.batch_size,
-    seed cfg.sholl_seed, components below cfg.sholl_min_size pixels dropped) of the training generator against the data set and, when
-    the trainer averages, of the averaged one: logged in one line and appended to checkpoint.SHOLL as {epoch, image_size, images,
-    min_size, skipped_real, skipped_fake[, note]} plus, per statistic (calibre, soma, sholl_peak, sholl_radius, reach), {real, real_sem,
-    fake, fake_sem, ks} and profile: {radius, real, fake}; with an averaged generator also skipped_fake_ema, <statistic>_ema: {fake,
-    fake_sem, ks} and profile_ema: {fake} over the rings of profile (the data's side is the same: it is not stored twice).  Eager,
-    outside any captured graph, no collective; it draws from private generators only, so the run trains on as if it had not happened."""
-    from .metrics import SHOLL_STATISTICS, evaluate_sholl
-    G = trainer.G
-    kw = dict(n_images=int(getattr(cfg, 'sholl_images', 8192)), batch_size=int(cfg.batch_size),
-              seed=int(getattr(cfg, 'sholl_seed', 0)), min_size=int(getattr(cfg, 'sholl_min_size', 1)))
-    res, metric = evaluate_sholl(G, dataset, return_metric=True, **kw)
-    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "min_size": kw["min_size"]}
-    entry.update({k: ({a: (list(b) if isinstance(b, list) else b) for a, b in v.items()} if isinstance(v, dict) else v) for k, v in res.items()})
-    if metric.active and getattr(trainer, "ema_enabled", False):
-        with trainer.averaged_generator():
-            ema = evaluate_sholl(G, None, real_from=metric, **kw)      # (the data's side is the same: not scored twice)
-        entry["skipped_fake_ema"] = ema["skipped_fake"]
-        for name in SHOLL_STATISTICS:
-            if name in ema:
-                entry[name + "_ema"] = {k: ema[name][k] for k in ("fake", "fake_sem", "ks")}
-        if "profile" in ema and "profile" in entry:
-            n = len(entry["profile"]["radius"])
-            entry["profile_ema"] = {"fake": (list(ema["profile"]["fake"]) + [0.0] * n)[:n]}
-    if "calibre" not in res:
-        log("Epoch:{}, sholl: {}".format(epoch, res["note"]))
-    else:
-        one = lambda r: "calibre {:.3f} (KS {:.3f}), soma {:.2f}, peak {:.2f} at {:.3f}, reach {:.3f} (KS {:.3f})".format(   # noqa: E731
-            r["calibre"]["fake"], r["calibre"]["ks"], r["soma"]["fake"], r["sholl_peak"]["fake"], r["sholl_radius"]["fake"],
-            r["reach"]["fake"], r["reach"]["ks"])
-        line = "Epoch:{}, sholl over {} images: {}; data: calibre {:.3f}, soma {:.2f}, peak {:.2f} at {:.3f}, reach {:.3f}".format(
-            epoch, res["images"], one(res), res["calibre"]["real"], res["soma"]["real"], res["sholl_peak"]["real"],
-            res["sholl_radius"]["real"], res["reach"]["real"])
-        if "calibre_ema" in entry:
-            line += "; averaged generator: " + one({n: entry[n + "_ema"] for n in SHOLL_STATISTICS})
-        log(line)
-    if checkpoint is not None:
-        checkpoint.SHOLL.append(entry)
-    return entry
-
-
-def score_branches(trainer, dataset, cfg, epoch, checkpoint=None, log=print):
-    """One arbor-branch evaluation (metrics.evaluate_branches with cfg.branch_images images per side in minibatches of cfg.batch_size,
-    seed cfg.branch_seed, components below cfg.branch_min_size pixels dropped, terminal branches below cfg.branch_spur pixels pruned --
-    0: max(2, image size / 32)) of the training generator against the data set and, when the trainer averages, of the averaged one:
-    logged in one line and appended to checkpoint.BRANCH as {epoch, image_size, images, min_size, spur, skipped_real, skipped_fake[,
-    note]} plus, per statistic (forks, nodes, terminals, spurs, terminal_length, link_length, longest), {real, real_sem, fake, fake_sem,
-    ks} and profile: {length, real, fake}; with an averaged generator also skipped_fake_ema, <statistic>_ema: {fake, fake_sem, ks} and
-    profile_ema: {fake} over the bins of profile (the data's side is the same: it is not stored twice).  Eager, outside any captured
-    graph, no collective; it draws from private generators only, so the run trains on as if it had not happened."""
-    from .metrics import BRANCH_STATISTICS, default_spur, evaluate_branches
-    G = trainer.G
-    spur = int(getattr(cfg, 'branch_spur', 0) or 0) or default_spur(int(G.image_size))
-    kw = dict(n_images=int(getattr(cfg, 'branch_images', 8192)), batch_size=int(cfg.batch_size),
-              seed=int(getattr(cfg, 'branch_seed', 0)), min_size=int(getattr(cfg, 'branch_min_size', 1)), spur=spur)
-    res, metric = evaluate_branches(G, dataset, return_metric=True, **kw)
-    entry = {"epoch": int(epoch), "image_size": int(G.image_size), "min_size": kw["min_size"], "spur": spur}
-    entry.update({k: ({a: (list(b) if isinstance(b, list) else b) for a, b in v.items()} if isinstance(v, dict) else v) for k, v in res.items()})
-    if metric.active and getattr(trainer, "ema_enabled", False):
-        with trainer.averaged_generator():
-            ema = evaluate_branches(G, None, real_from=metric, **kw)      # (the data's side is the same: not scored twice)
-        entry["skipped_fake_ema"] = ema["skipped_fake"]
-        for name in BRANCH_STATISTICS:
-            if name in ema:
-                entry[name + "_ema"] = {k: ema[name][k] for k in ("fake", "fake_sem", "ks")}
-        if "profile" in ema and "profile" in entry:
-            n = len(entry["profile"]["length"])
-            entry["profile_ema"] = {"fake": (list(ema["profile"]["fake"]) + [0.0] * n)[:n]}
-    if "forks" not in res:
-        log("Epoch:{}, branches: {}".format(epoch, res["note"]))
-    else:
-        one = lambda r: "forks {:.2f} (KS {:.3f}), terminals {:.2f} of {:.4f}, spurs {:.2f} (KS {:.3f}), links of {:.4f}".format(   # noqa: E731
-            r["forks"]["fake"], r["forks"]["ks"], r["terminals"]["fake"], r["terminal_length"]["fake"], r["spurs"]["fake"],
-            r["spurs"]["ks"], r["link_length"]["fake"])
-        line = "Epoch:{}, branches over {} images, spur {}: {}; data: forks {:.2f}, terminals {:.2f} of {:.4f}, spurs {:.2f}, links of {:.4f}".format(
-            epoch, res["images"], spur, one(res), res["forks"]["real"], res["terminals"]["real"], res["terminal_length"]["real"],
-            res["spurs"]["real"], res["link_length"]["real"])
-        if "forks_ema" in entry:
-            line += "; averaged generator: " + one({n: entry[n + "_ema"] for n in BRANCH_STATISTICS})
-        log(line)
-    if checkpoint is not None:
-        checkpoint.BRANCH.append(entry)
-    return entry
-
-
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
                 samples_dir=None, on_epoch=None, process_group=None, draws=None):
     """The reference's epoch loop (train.py:298-451) over a PGGANTrainer.
@@ -1767,10 +1525,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     draws the same permutation and trains its `shard_bounds` slice of every global batch, passing the global size to the trainer;
     the monitor sums are all-reduced once per epoch, so the series, the adaptive critic schedule and the NaN check are the same on
     every rank; rank 0 alone logs, saves and plots.  With one rank nothing of this is active.
-    cfg.swd_period > 0: rank 0 scores every checkpoint whose epoch is a multiple of it (`score_swd`) before it is written; the other
-    ranks wait at the checkpoint's barrier.  cfg.msssim_period > 0: the same with `score_msssim`; cfg.spectrum_period > 0: with `score_spectrum`;
-    cfg.morph_period > 0: with `score_morph`; cfg.skeleton_period > 0: with `score_skeleton`; cfg.sholl_period > 0: with `score_sholl`;
-    cfg.branch_period > 0: with `score_branches`.
+    cfg.<prefix>_period > 0, for a row of metric_table.METRICS: rank 0 scores every checkpoint whose epoch is a multiple of it
+    (scoring.score_due, in table order) before it is written; the other ranks wait at the checkpoint's barrier.
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
     (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
@@ -1779,13 +1535,6 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     sim_lambda = float(getattr(cfg, 'sim_loss_lambda', 0.0))          # train.py:300
     sim_decay = float(getattr(cfg, 'sim_loss_lambda_decay_rate', 0.0))
     adapt_critic = bool(getattr(cfg, 'adapt_critic', False))
-    swd_period = int(getattr(cfg, 'swd_period', 0) or 0)
-    msssim_period = int(getattr(cfg, 'msssim_period', 0) or 0)
-    spectrum_period = int(getattr(cfg, 'spectrum_period', 0) or 0)
-    morph_period = int(getattr(cfg, 'morph_period', 0) or 0)
-    skeleton_period = int(getattr(cfg, 'skeleton_period', 0) or 0)
-    sholl_period = int(getattr(cfg, 'sholl_period', 0) or 0)
-    branch_period = int(getattr(cfg, 'branch_period', 0) or 0)
     G, D = trainer.G, trainer.D
     dev = trainer.device
     epoch_final = epoch_final if epoch_final is not None else cfg.N_epochs + 1
@@ -1892,20 +1641,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
             consume(slot)
             checkpoint.lr = trainer.opt_g.param_groups[0]["lr"]
             if ranks.rank == 0:                                        # replicas are identical: rank 0's state is everyone's
-                if swd_period > 0 and epoch % swd_period == 0:
-                    score_swd(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
-                if msssim_period > 0 and epoch % msssim_period == 0:
-                    score_msssim(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
-                if spectrum_period > 0 and epoch % spectrum_period == 0:
-                    score_spectrum(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
-                if morph_period > 0 and epoch % morph_period == 0:
-                    score_morph(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
-                if skeleton_period > 0 and epoch % skeleton_period == 0:
-                    score_skeleton(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
-                if sholl_period > 0 and epoch % sholl_period == 0:
-                    score_sholl(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
-                if branch_period > 0 and epoch % branch_period == 0:
-                    score_branches(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)
+                score_due(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)   # the metrics whose period divides it
                 checkpoint.save_state(epoch)
                 if samples_dir is not None:
                     from .utils import plot_gen_samples
@@ -2083,42 +1819,9 @@ def build_arg_parser():
                                                            'from color,translation,cutout; empty: off')
     p.add_argument('--diffaug_p', type=float, default=1.0, help='probability of each augmentation group per sample')
     p.add_argument('--diffaug_seed', type=int, default=0, help='seed of the augmentation parameters\' private stream')
-    p.add_argument('--swd_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the '
-                                                             'sliced Wasserstein distance (metrics.py); 0: off')
-    p.add_argument('--swd_images', type=int, default=8192, help='images per side of one SWD evaluation')
-    p.add_argument('--swd_seed', type=int, default=0, help='seed of the SWD patch corners, directions, latents and augmentations')
-    p.add_argument('--msssim_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the mean '
-                                                                'MS-SSIM between pairs of samples (metrics.py); 0: off')
-    p.add_argument('--msssim_pairs', type=int, default=10000, help='pairs per side of one MS-SSIM evaluation')
-    p.add_argument('--msssim_seed', type=int, default=0, help='seed of the MS-SSIM latents and augmentations')
-    p.add_argument('--spectrum_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the '
-                                                                  'radial power spectrum of samples against the data (metrics.py); 0: off')
-    p.add_argument('--spectrum_images', type=int, default=8192, help='images per side of one spectrum evaluation')
-    p.add_argument('--spectrum_seed', type=int, default=0, help='seed of the spectrum latents and augmentations')
-    p.add_argument('--morph_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the arbor '
-                                                               'morphology of samples against the data (metrics.py); 0: off')
-    p.add_argument('--morph_images', type=int, default=8192, help='images per side of one morphology evaluation')
-    p.add_argument('--morph_seed', type=int, default=0, help='seed of the morphology latents and augmentations')
-    p.add_argument('--morph_min_size', type=int, default=1, help='components below this many pixels are dropped (1 drops none)')
-    p.add_argument('--skeleton_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the arbor '
-                                                                  'skeleton of samples against the data (metrics.py); 0: off')
-    p.add_argument('--skeleton_images', type=int, default=8192, help='images per side of one skeleton evaluation')
-    p.add_argument('--skeleton_seed', type=int, default=0, help='seed of the skeleton latents and augmentations')
-    p.add_argument('--skeleton_min_size', type=int, default=1, help='components below this many pixels are not thinned (1 drops none)')
-    p.add_argument('--sholl_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the arbor '
-                                                               'geometry (calibre, soma, Sholl profile) of samples against the data '
-                                                               '(metrics.py); 0: off')
-    p.add_argument('--sholl_images', type=int, default=8192, help='images per side of one arbor-geometry evaluation')
-    p.add_argument('--sholl_seed', type=int, default=0, help='seed of the arbor-geometry latents and augmentations')
-    p.add_argument('--sholl_min_size', type=int, default=1, help='components below this many pixels are not measured (1 drops none)')
-    p.add_argument('--branch_period', type=int, default=0, help='score every checkpoint whose epoch is a multiple of this with the arbor '
-                                                                'branches (forks, spurs, branch lengths) of samples against the data '
-                                                                '(metrics.py); 0: off')
-    p.add_argument('--branch_images', type=int, default=8192, help='images per side of one arbor-branch evaluation')
-    p.add_argument('--branch_seed', type=int, default=0, help='seed of the arbor-branch latents and augmentations')
-    p.add_argument('--branch_min_size', type=int, default=1, help='components below this many pixels are not measured (1 drops none)')
-    p.add_argument('--branch_spur', type=int, default=0, help='terminal branches below this many pixels are pruned as thinning spurs '
-                                                              '(0: max(2, image size / 32))')
+    for m in METRICS:                                                    # one group of integer flags per checkpoint metric
+        for name, _, default, text in settings(m):
+            p.add_argument('--' + name, type=int, default=default, help=text)
     p.add_argument('--gpus', type=int, default=1, help='data parallel over this many GPUs of the node (one fresh process each, '
                                                         'launch.py); batch_size stays the global batch')
     return p

@@ -1,6 +1,8 @@
 """Training utilities on the hot path: the latent sampler (reference utils.py:54-92)."""
 import torch
 
+from .metric_table import METRICS
+
 Latent_vecs_memo = {}
 
 
@@ -45,16 +47,9 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # per-tensor step counts (the reference does not save optimiser state at all).  A trainer that keeps an averaged generator
 # (train.py, `ema_beta`) adds 'Generator_ema_state': the averaged weights under the keys of 'Generator_state', tensors only.  The
 # reference's loaders read the keys they know and ignore the rest (utils.py:185-199 index five series keys and the two attribute
-# dictionaries, models.py the state dictionaries).  A run that scores its checkpoints (train.py, `swd_period`) adds 'SWD': a list of
-# {epoch, image_size, levels, swd, swd_ema} -- plain Python numbers and lists, which the weights-only unpickler accepts as it is.
-# Likewise `msssim_period` adds 'MSSSIM': a list of {epoch, image_size, scales, fake, fake_ema, real, pairs}, and `spectrum_period`
-# adds 'SPECTRUM': a list of {epoch, image_size, images, k, real, fake, ratio_db, distance_db, high_db[, distance_db_ema, high_db_ema]},
-# and `morph_period` adds 'MORPH': a list of {epoch, image_size, images, min_size, skipped_real, skipped_fake[, note], fill, components,
-# largest_share, dimension: {real, real_sem, fake, fake_sem, ks}[, skipped_fake_ema, <statistic>_ema: {fake, fake_sem, ks}]}, and
-# `skeleton_period` adds 'SKELETON': a list of the same shape with the statistics length, tips, junctions, width, and `sholl_period`
-# adds 'SHOLL': the same with calibre, soma, sholl_peak, sholl_radius, reach and profile: {radius, real, fake}[, profile_ema: {fake}], and
-# `branch_period` adds 'BRANCH': the same with spur, forks, nodes, terminals, spurs, terminal_length, link_length, longest and profile:
-# {length, real, fake}[, profile_ema: {fake}].
+# dictionaries, models.py the state dictionaries).  A run that scores its checkpoints (train.py, `<prefix>_period`) adds one key per row
+# of metric_table.METRICS that scored, 'SWD' .. 'BRANCH': a list with one entry {epoch, image_size, ...} per scored checkpoint, whose
+# fields scoring.py lists per metric -- plain Python numbers, lists and dictionaries, which the weights-only unpickler accepts as it is.
 # ---------------------------------------------------------------------------------------------------------------------
 import os  # noqa: E402
 
@@ -95,13 +90,7 @@ def load_checkpoint_dict(filename, device=torch.device('cpu')):
 
 
 EMA_KEY = 'Generator_ema_state'
-SWD_KEY = 'SWD'
-MSSSIM_KEY = 'MSSSIM'
-SPECTRUM_KEY = 'SPECTRUM'
-MORPH_KEY = 'MORPH'
-SKELETON_KEY = 'SKELETON'
-SHOLL_KEY = 'SHOLL'
-BRANCH_KEY = 'BRANCH'
+SWD_KEY, MSSSIM_KEY, SPECTRUM_KEY, MORPH_KEY, SKELETON_KEY, SHOLL_KEY, BRANCH_KEY = (m.key for m in METRICS)
 
 
 class Checkpointer:
@@ -120,13 +109,8 @@ class Checkpointer:
         self.device = device
         self.extra_checkpoint_period = extra_checkpoint_period
         self.trainer = trainer      # optional PGGANTrainer: adds / restores 'optimizer_state' (and 'Generator_ema_state')
-        self.SWD = []               # one entry per scored checkpoint (train.py, `swd_period`); saved only when it holds any
-        self.MSSSIM = []            # the same for `msssim_period`
-        self.SPECTRUM = []          # the same for `spectrum_period`
-        self.MORPH = []             # the same for `morph_period`
-        self.SKELETON = []          # the same for `skeleton_period`
-        self.SHOLL = []             # the same for `sholl_period`
-        self.BRANCH = []            # the same for `branch_period`
+        for m in METRICS:           # self.SWD .. self.BRANCH: one entry per scored checkpoint (train.py, `<prefix>_period`), saved only
+            setattr(self, m.key, [])    # when the list holds any
 
     def save_state(self, epoch):
         self.epoch = epoch
@@ -145,20 +129,9 @@ class Checkpointer:
             checkpoint_dict['optimizer_state'] = self.trainer.optimizer_state()
             if getattr(self.trainer, 'ema_enabled', False):
                 checkpoint_dict[EMA_KEY] = cpu(self.trainer.ema_state())
-        if self.SWD:
-            checkpoint_dict[SWD_KEY] = [dict(entry) for entry in self.SWD]
-        if self.MSSSIM:
-            checkpoint_dict[MSSSIM_KEY] = [dict(entry) for entry in self.MSSSIM]
-        if self.SPECTRUM:
-            checkpoint_dict[SPECTRUM_KEY] = [dict(entry) for entry in self.SPECTRUM]
-        if self.MORPH:
-            checkpoint_dict[MORPH_KEY] = [dict(entry) for entry in self.MORPH]
-        if self.SKELETON:
-            checkpoint_dict[SKELETON_KEY] = [dict(entry) for entry in self.SKELETON]
-        if self.SHOLL:
-            checkpoint_dict[SHOLL_KEY] = [dict(entry) for entry in self.SHOLL]
-        if self.BRANCH:
-            checkpoint_dict[BRANCH_KEY] = [dict(entry) for entry in self.BRANCH]
+        for m in METRICS:
+            if getattr(self, m.key):
+                checkpoint_dict[m.key] = [dict(entry) for entry in getattr(self, m.key)]
         torch.save(checkpoint_dict, self.filename)
         if epoch % self.extra_checkpoint_period == 0:
             base, ext = os.path.splitext(self.filename)
@@ -178,13 +151,8 @@ class Checkpointer:
             self.Loss_fake[:self.epoch] = checkpoint_dict['Loss_fake']
             self.Loss_G[:self.epoch] = checkpoint_dict['Loss_G']
             self.Loss_D[:self.epoch] = checkpoint_dict['Loss_D']
-            self.SWD = [dict(entry) for entry in checkpoint_dict.get(SWD_KEY, [])]      # a resumed run continues the list
-            self.MSSSIM = [dict(entry) for entry in checkpoint_dict.get(MSSSIM_KEY, [])]
-            self.SPECTRUM = [dict(entry) for entry in checkpoint_dict.get(SPECTRUM_KEY, [])]
-            self.MORPH = [dict(entry) for entry in checkpoint_dict.get(MORPH_KEY, [])]
-            self.SKELETON = [dict(entry) for entry in checkpoint_dict.get(SKELETON_KEY, [])]
-            self.SHOLL = [dict(entry) for entry in checkpoint_dict.get(SHOLL_KEY, [])]
-            self.BRANCH = [dict(entry) for entry in checkpoint_dict.get(BRANCH_KEY, [])]
+            for m in METRICS:           # a resumed run continues the lists
+                setattr(self, m.key, [dict(entry) for entry in checkpoint_dict.get(m.key, [])])
         if 'Generator_attrs' in checkpoint_dict and 'Discriminator_attrs' in checkpoint_dict:
             # (the WGAN nets list no saved_attrs: the reference fails there, utils.py:194-198; here they count as empty)
             gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in getattr(self.Generator_net, 'saved_attrs', [])}
