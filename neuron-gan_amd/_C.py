@@ -141,6 +141,13 @@ for _op in ("lrelu_pixelnorm_fwd", "lrelu_pixelnorm_bwd", "lrelu_pixelnorm_bwd2"
 SIGNATURES["ngan_bf16_conv3x3_fwd"] = [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P]
 SIGNATURES["ngan_bf16_conv3x3_wgrad"] = [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]
 
+# include/ngan_objectives.h, the extension section of the header: the scalar heads of the selectable objectives (status-returning,
+# called through `call` like the entries above; listed by `objective_symbols`, not by `exported_symbols`, which is ngan.h's own table)
+OBJECTIVE_SIGNATURES = {
+    "ngan_lsloss_head": [_P, _I, _I, _F, _F, _P, _P, _P, _P],
+    "ngan_lsloss_head_bwd": [_P, _I, _I, _F, _F, _P, _P, _P, _P, _P],
+}
+
 NON_STATUS = {
     "ngan_version": ([], ctypes.c_char_p),
     "ngan_last_error": ([], ctypes.c_char_p),
@@ -186,7 +193,7 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                f"or `make -C neuron-gan_amd/csrc`; there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
@@ -200,6 +207,10 @@ def lib():
 
 def exported_symbols():
     return list(SIGNATURES) + list(NON_STATUS)
+
+
+def objective_symbols():
+    return list(OBJECTIVE_SIGNATURES)
 
 
 def version() -> str:

@@ -33,7 +33,7 @@ _DEFAULTS = dict(
     seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
     # the checkpoint metrics: <prefix>_period, _images (or _pairs), _seed and the metric's own options, row by row
     **{name: default for m in METRICS for name, _, default, _ in settings(m)},
-    diffaug='', diffaug_p=1.0, diffaug_seed=0,
+    diffaug='', diffaug_p=1.0, diffaug_seed=0, lsgan=False,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -112,6 +112,11 @@ def validate_configs(create_dirs=False):
         raise ValueError(f"diffaug_seed={g['diffaug_seed']!r} must be an integer >= 0")
     if any(groups) and g['wgan'] and not g['pggan']:
         raise ValueError(f"diffaug={g['diffaug']!r} is not available for the WGAN nets (wgan=True, pggan=False)")
+    # the least-squares objective (an addition of this implementation: the reference ships its two losses and never calls them)
+    if not isinstance(g['lsgan'], bool):
+        raise ValueError(f"lsgan={g['lsgan']!r} must be True or False")
+    if g['lsgan'] and g['wgan']:
+        raise ValueError("lsgan=True is not available for the WGAN nets (wgan=True)")
     if g['pggan']:
         err_msg = 'The number of layers in the generator and discriminator must match.'
         assert len(g['N_gen_features']) == len(g['N_dis_features']), err_msg

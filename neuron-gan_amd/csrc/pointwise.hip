@@ -654,6 +654,33 @@ __global__ __launch_bounds__(256) void wloss_head_bwd_kernel(const float* __rest
     else if (i < n_real + n_fake) gs[i] = (gl + gf) / (float)n_fake;
 }
 
+// least-squares objective (Mao et al. 2017; loss_functions.py:77-143): out = {loss, mean real score, mean fake score};
+// loss = mean((real - t_real)^2) + mean((fake - t_fake)^2)  (loss_functions.py:99; with n_fake = 0: mean((scores - t_real)^2), the
+// generator loss, loss_functions.py:133).  The targets are arguments: one kernel pair serves the critic and the generator.
+__global__ __launch_bounds__(256) void lsloss_head_kernel(const float* __restrict__ scores, int n_real, int n_fake, float t_real, float t_fake,
+                                                          float* __restrict__ o_loss, float* __restrict__ o_real, float* __restrict__ o_fake) {
+    __shared__ float red[4];
+    float sr = 0.f, qr = 0.f, sf = 0.f, qf = 0.f;
+    for (int i = threadIdx.x; i < n_real; i += 256) { const float v = scores[i], d = v - t_real; sr += v; qr = fmaf(d, d, qr); }
+    for (int i = threadIdx.x; i < n_fake; i += 256) { const float v = scores[n_real + i], d = v - t_fake; sf += v; qf = fmaf(d, d, qf); }
+    sr = block_sum_256(sr, red); qr = block_sum_256(qr, red); sf = block_sum_256(sf, red); qf = block_sum_256(qf, red);
+    if (threadIdx.x == 0) {
+        const float lr = qr / (float)n_real;
+        o_loss[0] = n_fake ? lr + qf / (float)n_fake : lr;
+        o_real[0] = sr / (float)n_real; o_fake[0] = n_fake ? sf / (float)n_fake : 0.f;
+    }
+}
+
+// gs[i] = (g_loss * 2 (s_i - t) + g_mean) / n of its half; the three incoming gradients are device scalars (null: 0)
+__global__ __launch_bounds__(256) void lsloss_head_bwd_kernel(const float* __restrict__ scores, int n_real, int n_fake, float t_real, float t_fake,
+                                                              const float* __restrict__ g_loss, const float* __restrict__ g_real,
+                                                              const float* __restrict__ g_fake, float* __restrict__ gs) {
+    const float gl2 = g_loss ? 2.0f * g_loss[0] : 0.f, gr = g_real ? g_real[0] : 0.f, gf = g_fake ? g_fake[0] : 0.f;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_real) gs[i] = fmaf(gl2, scores[i] - t_real, gr) / (float)n_real;
+    else if (i < n_real + n_fake) gs[i] = fmaf(gl2, scores[i] - t_fake, gf) / (float)n_fake;
+}
+
 // penalty = lambda * mean((norms - 1)^2)  (loss_functions.py:176);  coef[b] = g_out * 2 lambda (norms[b] - 1) / (B norms[b])
 __global__ __launch_bounds__(256) void gp_head_kernel(const float* __restrict__ norms, int B, float lambda, float* __restrict__ out) {
     __shared__ float red[4];
@@ -690,6 +717,22 @@ extern "C" int ngan_wloss_head_bwd(const float* scores, int n_real, int n_fake, 
     hipLaunchKernelGGL(wloss_head_bwd_kernel, dim3(ngan::ceil_div(n_real + n_fake, 256)), dim3(256), 0, (hipStream_t)stream, scores, n_real,
                        n_fake, drift, g_loss, g_real, g_fake, g_scores);
     return ngan::launch_status("ngan_wloss_head_bwd");
+}
+
+extern "C" int ngan_lsloss_head(const float* scores, int n_real, int n_fake, float t_real, float t_fake, float* loss, float* mean_real,
+                                float* mean_fake, void* stream) {
+    NGAN_REQUIRE(scores && loss && mean_real && mean_fake && n_real > 0 && n_fake >= 0, NGAN_ERR_ARG, "lsloss_head: bad argument");
+    hipLaunchKernelGGL(lsloss_head_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, n_real, n_fake, t_real, t_fake, loss, mean_real,
+                       mean_fake);
+    return ngan::launch_status("ngan_lsloss_head");
+}
+
+extern "C" int ngan_lsloss_head_bwd(const float* scores, int n_real, int n_fake, float t_real, float t_fake, const float* g_loss,
+                                    const float* g_real, const float* g_fake, float* g_scores, void* stream) {
+    NGAN_REQUIRE(scores && g_scores && n_real > 0 && n_fake >= 0, NGAN_ERR_ARG, "lsloss_head_bwd: bad argument");
+    hipLaunchKernelGGL(lsloss_head_bwd_kernel, dim3(ngan::ceil_div(n_real + n_fake, 256)), dim3(256), 0, (hipStream_t)stream, scores, n_real,
+                       n_fake, t_real, t_fake, g_loss, g_real, g_fake, g_scores);
+    return ngan::launch_status("ngan_lsloss_head_bwd");
 }
 
 extern "C" int ngan_gp_head(const float* norms, int B, float lambda, float* out1, void* stream) {

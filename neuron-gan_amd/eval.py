@@ -89,8 +89,11 @@ def main(argv=None):
         for use_ema in ((False, True) if options.ema else (False,)):
             G = Generator_PG.from_state_dict(weights, device=device, use_ema=use_ema, verbose=False).to(device)
             res = getattr(metrics, m.evaluate)(G, dataset, **kw)
-            print(getattr(metrics, m.format)(res, '{}, {} generator of {}{}'.format(
-                m.title, 'averaged' if use_ema else 'training', options.weights, m.title_tail.format(n=n))))
+            # the objective the checkpoint was trained with goes into the title, unless it is the reference's (a file without the key)
+            objective = getattr(G, 'trained_objective', 'wasserstein')
+            print(getattr(metrics, m.format)(res, '{}, {} generator of {}{}{}'.format(
+                m.title, 'averaged' if use_ema else 'training', options.weights, m.title_tail.format(n=n),
+                '' if objective == 'wasserstein' else ', {} objective'.format(objective))))
     if asked:
         return 0
     G = Generator_PG.from_state_dict(weights, device=device, use_ema=options.ema).to(device)

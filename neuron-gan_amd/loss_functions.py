@@ -1,8 +1,10 @@
-"""WGAN / WGAN-GP losses with the reference's interface (loss_functions.py:7-74, 148-180), running on the HIP ops.
+"""WGAN / WGAN-GP and LSGAN losses with the reference's interface (loss_functions.py:7-74, 77-143, 148-180), running on the HIP ops.
 
     D_W_loss(G, D, drift_epsilon)(real)      -> (loss, score_real, score_fake)
     G_W_loss(G, D)(real)                     -> (loss, z)
     D_grad_pen_loss(G, D, Lambda)(real)      -> loss   (create_graph double-backward through the critic)
+    D_LS_loss(G, D, real)                    -> (loss, score_real, score_fake)   least squares, Mao et al. 2017; functions, as in the
+    G_LS_loss(G, D, real)                    -> (loss, score_fake)               reference, which ships them and never calls them
 
 Latents come from `utils.sample_latent_vec` unless a tensor is passed through the optional `z=` / `epsilon=`
 keywords (how the parity tests inject the reference's draws).  Every loss takes an optional `augment=` hook (`DiffAugmentHook`, an
@@ -105,6 +107,79 @@ class G_W_loss(nn.Module):
             G_loss = ops.WLossHead.apply(self.discriminator_net(fake_images), batch_size, 0.0)[0]       # -mean(D(G(z)))
         if self.check_nan and torch.isnan(G_loss):
             raise ValueError('Generator loss is nan.')
+        return G_loss, z_latent
+
+
+# The reference's coding of the least-squares targets (loss_functions.py:99, 133): the critic pulls real scores to 1 and generated ones to
+# 0, the generator pulls its scores to 1.  The kernels take the targets as arguments; the public functions expose this coding only.
+LS_TARGET_REAL, LS_TARGET_FAKE, LS_TARGET_GEN = 1.0, 0.0, 1.0
+
+
+def D_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, *, z=None, fake_images=None, augment=None, check_nan=True):
+    """mean((D(x) - 1)^2) + mean(D(G(z))^2) (loss_functions.py:79-112) -> (D_loss, Score_real_avg, Score_fake_avg).  `Lambda` is the
+    reference's unused argument.  One critic pass over [real | fake], differentiated once, and one launch for the scalar chain each way,
+    as D_W_loss.forward; the drift term does not enter, as in the reference's function.  z= / fake_images= / augment= / check_nan=:
+    the keyword extras of the W losses (module docstring)."""
+    batch_size, device = real_images_batch.size(0), real_images_batch.device
+    if fake_images is None:
+        z = _latents(generator_net, batch_size, device, z)
+        with torch.no_grad():
+            fake_images = generator_net(z)
+    with ops.first_order_only():
+        both = torch.cat([real_images_batch, fake_images], dim=0) if augment is None else augment.critic_batch(real_images_batch, fake_images)
+        scores = discriminator_net(both)
+    D_loss, Score_real_avg, Score_fake_avg = ops.LSLossHead.apply(scores, batch_size, LS_TARGET_REAL, LS_TARGET_FAKE)
+    if check_nan:
+        if torch.isnan(Score_real_avg):
+            raise ValueError('Real loss is nan.')
+        if torch.isnan(Score_fake_avg):
+            raise ValueError('Fake loss is nan.')
+        if torch.isnan(D_loss):
+            raise ValueError('D loss is nan.')
+    return D_loss, Score_real_avg, Score_fake_avg
+
+
+def G_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, *, z=None, augment=None, check_nan=True):
+    """mean((D(G(z)) - 1)^2) (loss_functions.py:117-143) -> (G_loss, Score_fake_avg).  One deliberate departure: the reference detaches
+    the generated images (loss_functions.py:125), so its generator would receive no gradient at all and could not be trained with
+    this loss; here the value is the same and the gradient flows into the generator (through `augment`'s transform when given)."""
+    batch_size, device = real_images_batch.size(0), real_images_batch.device
+    fake_images = generator_net(_latents(generator_net, batch_size, device, z))
+    if augment is not None:
+        fake_images = augment.generated(fake_images)
+    with ops.first_order_only():
+        G_loss, Score_fake_avg, _ = ops.LSLossHead.apply(discriminator_net(fake_images), batch_size, LS_TARGET_GEN, LS_TARGET_FAKE)
+    if check_nan:
+        if torch.isnan(Score_fake_avg):
+            raise ValueError('Fake loss is nan.')
+        if torch.isnan(G_loss):
+            raise ValueError('D loss is nan.')
+    return G_loss, Score_fake_avg
+
+
+class D_LS_module(nn.Module):
+    """D_LS_loss with D_W_loss's call shape: what a trainer with objective="lsgan" holds as `d_loss`"""
+
+    def __init__(self, generator_net, discriminator_net, check_nan=True):
+        super().__init__()
+        self.generator_net, self.discriminator_net, self.check_nan = generator_net, discriminator_net, check_nan
+
+    def forward(self, real_images, z=None, fake_images=None, augment=None):
+        return D_LS_loss(self.generator_net, self.discriminator_net, real_images, z=z, fake_images=fake_images, augment=augment,
+                         check_nan=self.check_nan)
+
+
+class G_LS_module(nn.Module):
+    """G_LS_loss with G_W_loss's call shape and return value, (loss, z): what a trainer with objective="lsgan" holds as `g_loss`"""
+
+    def __init__(self, generator_net, discriminator_net, check_nan=True):
+        super().__init__()
+        self.generator_net, self.discriminator_net, self.check_nan = generator_net, discriminator_net, check_nan
+
+    def forward(self, real_images_batch, z=None, augment=None):
+        z_latent = _latents(self.generator_net, real_images_batch.size(0), real_images_batch.device, z)
+        G_loss, _ = G_LS_loss(self.generator_net, self.discriminator_net, real_images_batch, z=z_latent, augment=augment,
+                              check_nan=self.check_nan)
         return G_loss, z_latent
 
 

@@ -562,8 +562,9 @@ class Generator_PG(_ProgressiveNet):
         """Rebuild a generator from a checkpoint written by `Checkpointer` (reference models.py:394-444), including
         checkpoints in the older layout that still carry merged ToIm_list / conv_block_list entries.
         use_ema: load the averaged weights ('Generator_ema_state', written by a trainer with ema_beta > 0) instead of the training
-        weights; KeyError if the file holds none."""
-        from .utils import EMA_KEY, load_checkpoint_dict
+        weights; KeyError if the file holds none.  The result carries `trained_objective`, the file's 'objective' key ("wasserstein"
+        for a file without one)."""
+        from .utils import EMA_KEY, OBJECTIVE_KEY, load_checkpoint_dict
         saved = load_checkpoint_dict(filename, device)
         if use_ema and EMA_KEY not in saved:
             raise KeyError(f"{EMA_KEY}: {filename} holds no averaged generator (it was written without ema_beta)")
@@ -583,6 +584,7 @@ class Generator_PG(_ProgressiveNet):
                                          _count_list_entries(state, 'conv_block_list') - len(obj.conv_block_list), from_start=True)
             state = _drop_prefix(_drop_prefix(state, 'ToIm_prev'), 'last_conv_block')
         obj.load_state_dict(state)
+        obj.trained_objective = saved.get(OBJECTIVE_KEY, 'wasserstein')      # what eval.py prints with its tables; no part of the state
         if verbose:
             print('Loaded training state from {}'.format(filename))
         return obj

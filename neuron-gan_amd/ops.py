@@ -1383,6 +1383,36 @@ class WLossHead(Function):
         return gs, None, None
 
 
+class LSLossHead(Function):
+    """(loss, mean real score, mean fake score) of scores = [n_real real | n_fake fake] under the least-squares objective (Mao et
+    al. 2017): loss = mean((real - t_real)^2) + mean((fake - t_fake)^2)  (loss_functions.py:99); n_fake = 0: mean((scores -
+    t_real)^2), the generator loss (loss_functions.py:133), with mean_fake = 0.  The two means are the plain score means, the
+    monitors.  One launch forward, one backward; once-differentiable (the penalty's second order never passes through it)."""
+
+    @staticmethod
+    def forward(ctx, scores, n_real, t_real, t_fake):
+        ctx.set_materialize_grads(False)
+        scores = _c(scores)
+        n = scores.numel()
+        # three separate 0-dim tensors, as WLossHead's: the training loop adds the penalty to the loss in place
+        loss, s_real, s_fake = (torch.empty((), device=scores.device, dtype=torch.float32) for _ in range(3))
+        _C.call("ngan_lsloss_head", scores, int(n_real), int(n - n_real), float(t_real), float(t_fake), loss, s_real, s_fake)
+        ctx.save_for_backward(scores)
+        ctx.cfg = (int(n_real), int(n - n_real), float(t_real), float(t_fake))
+        return loss, s_real, s_fake
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gl, gr, gf):
+        (scores,) = ctx.saved_tensors
+        n_real, n_fake, t_real, t_fake = ctx.cfg
+        if gl is None and gr is None and gf is None:
+            return None, None, None, None
+        gs = torch.empty_like(scores)
+        _C.call("ngan_lsloss_head_bwd", scores, n_real, n_fake, t_real, t_fake, _c(gl), _c(gr), _c(gf), gs)
+        return gs, None, None, None
+
+
 class GradPenaltyHead(Function):
     """(Lambda * mean_b((||g_b||_2 - 1)^2), norms) of the critic's input gradient g (loss_functions.py:176): SampleL2Norm and the
     penalty arithmetic as one operator; its backward scales g's rows by 2 Lambda (n_b - 1) / (B n_b)."""

@@ -24,7 +24,7 @@ import torch.distributed as dist
 
 from . import _C, ops, wgan_ops
 from .launch import check_sharding, longest_share, shard_bounds
-from .loss_functions import D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_W_loss
+from .loss_functions import D_LS_module, D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_LS_module, G_W_loss
 from .metric_table import METRICS, settings
 from .scoring import (score_branches, score_due, score_morph, score_msssim, score_sholl, score_skeleton,  # noqa: F401
                       score_spectrum, score_swd)
@@ -247,6 +247,7 @@ class FusedRMSprop(_FlatOptimizer):
 
 
 OPTIMIZERS = {"adam": FusedAdam, "rmsprop": FusedRMSprop}
+OBJECTIVES = ("wasserstein", "lsgan")      # PGGANTrainer(objective=): the reference's loop, or its never-called least-squares losses
 
 
 def exchange_gradients(flat: FlatParams, world: int, group=None, force: bool = False):
@@ -571,7 +572,7 @@ class PGGANTrainer(_AveragedGenerator):
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
-                 rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0):
+                 rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, objective="wasserstein"):
         """optimizer: "adam" -- optim.Adam(params, lr, betas=(beta1, 0.999)), the reference's default -- or "rmsprop" --
         optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps), what the reference's RMSprop switch selects (train.py:220-225);
         beta1 only matters for Adam
@@ -583,7 +584,13 @@ class PGGANTrainer(_AveragedGenerator):
         -1, the images' black, not DiffAugment's 0 (loss_functions.DIFFAUG_FILL says why).  diffaug_p: the probability with
         which each group is applied to each sample (1: DiffAugment proper; 0: off).  diffaug_seed: of the private uniform stream
         (`reseed_diffaug`).  train_iteration, replay and step draw an iteration's tables; d_step / g_step on their own read the
-        tables as they stand (`draw_diffaug_tables`)."""
+        tables as they stand (`draw_diffaug_tables`).
+        objective: "wasserstein" -- the reference's loop, D_W_loss / G_W_loss with the drift term -- or "lsgan" -- the least-squares
+        losses the reference ships and never calls (loss_functions.D_LS_loss / G_LS_loss); drift_epsilon does
+        not enter them.  Either way the penalty is added when grad_pen_lambda > 0, as the reference's loop adds it to whatever
+        D_loss is (train.py:361-362)."""
+        if objective not in OBJECTIVES:
+            raise ValueError(f"objective must be one of {list(OBJECTIVES)}, got {objective!r}")
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
         ema_beta = _check_ema_beta(ema_beta)
@@ -602,9 +609,14 @@ class PGGANTrainer(_AveragedGenerator):
         else:
             self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps, ema_beta=ema_beta)
             self.opt_d = FusedRMSprop(self.flat_d, learning_rate, rmsprop_alpha, rmsprop_eps)
-        self.d_loss = D_W_loss(generator, discriminator, drift_epsilon=drift_epsilon, check_nan=False)
+        self.objective = objective
+        if objective == "lsgan":
+            self.d_loss = D_LS_module(generator, discriminator, check_nan=False)
+            self.g_loss = G_LS_module(generator, discriminator, check_nan=False)
+        else:
+            self.d_loss = D_W_loss(generator, discriminator, drift_epsilon=drift_epsilon, check_nan=False)
+            self.g_loss = G_W_loss(generator, discriminator, check_nan=False)
         self.gp_loss = D_grad_pen_loss(generator, discriminator, Lambda=grad_pen_lambda)
-        self.g_loss = G_W_loss(generator, discriminator, check_nan=False)
         self.group = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.stem = None
@@ -1819,6 +1831,8 @@ def build_arg_parser():
                                                            'from color,translation,cutout; empty: off')
     p.add_argument('--diffaug_p', type=float, default=1.0, help='probability of each augmentation group per sample')
     p.add_argument('--diffaug_seed', type=int, default=0, help='seed of the augmentation parameters\' private stream')
+    p.add_argument('--lsgan', action='store_true', default=False, help='train the PG nets with the least-squares objective (the '
+                                                                        'reference\'s D_LS_loss / G_LS_loss) instead of the Wasserstein one')
     for m in METRICS:                                                    # one group of integer flags per checkpoint metric
         for name, _, default, text in settings(m):
             p.add_argument('--' + name, type=int, default=default, help=text)
@@ -1853,6 +1867,7 @@ def dataset_source(argv, options, config):
 def make_trainer(config, G, D, process_group=None, distributed=False):
     """The trainer `main()` trains with: RMSprop when config.RMSprop is set, else Adam with betas (beta1, 0.999) (train.py:220-225).
     wgan without pggan: a WGANTrainer (weight clipping at 0.01, reference train.py:489-490); wgan with pggan is refused.
+    config.lsgan: the PG trainer's objective is "lsgan" instead of "wasserstein" (refused for the WGAN nets).
     distributed: a launched rank -- the trainer exchanges over `process_group` (None: the default group); the WGAN nets then train
     with synchronised BatchNorm."""
     if config.wgan and config.pggan:
@@ -1860,7 +1875,10 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
                          "Generator_net.image_size); choose one")
     aug = dict(diffaug=getattr(config, 'diffaug', ''), diffaug_p=getattr(config, 'diffaug_p', 1.0),
                diffaug_seed=getattr(config, 'diffaug_seed', 0))
+    lsgan = bool(getattr(config, 'lsgan', False))
     if config.wgan:
+        if lsgan:
+            raise ValueError("lsgan=True is not available for the WGAN nets (wgan=True, pggan=False)")
         kw = dict(learning_rate=config.learning_rate, drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, device_latents=True,
                   process_group=process_group, sync_batchnorm=bool(distributed), ema_beta=getattr(config, 'ema_beta', 0.0), **aug)
         if config.RMSprop:
@@ -1869,6 +1887,8 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     kw = dict(learning_rate=config.learning_rate, grad_pen_lambda=config.grad_pen_lambda, drift_epsilon=config.drift_epsilon,
               n_critic=config.n_critic, alpha_step=config.alpha_step, device_latents=True, process_group=process_group,
               ema_beta=getattr(config, 'ema_beta', 0.0), **aug)
+    if lsgan:
+        kw["objective"] = "lsgan"
     if config.RMSprop:
         return PGGANTrainer(G, D, optimizer="rmsprop", **kw)
     return PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)

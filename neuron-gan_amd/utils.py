@@ -46,6 +46,7 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # by either side load in the other.  One optional extra key, 'optimizer_state', carries the fused Adam's moments and
 # per-tensor step counts (the reference does not save optimiser state at all).  A trainer that keeps an averaged generator
 # (train.py, `ema_beta`) adds 'Generator_ema_state': the averaged weights under the keys of 'Generator_state', tensors only.  The
+# A PGGANTrainer writes 'objective' ("wasserstein" or "lsgan", train.py `objective=`) beside it; a file without the key is Wasserstein.  The
 # reference's loaders read the keys they know and ignore the rest (utils.py:185-199 index five series keys and the two attribute
 # dictionaries, models.py the state dictionaries).  A run that scores its checkpoints (train.py, `<prefix>_period`) adds one key per row
 # of metric_table.METRICS that scored, 'SWD' .. 'BRANCH': a list with one entry {epoch, image_size, ...} per scored checkpoint, whose
@@ -90,6 +91,7 @@ def load_checkpoint_dict(filename, device=torch.device('cpu')):
 
 
 EMA_KEY = 'Generator_ema_state'
+OBJECTIVE_KEY = 'objective'      # of the trainer that wrote the file; a file without it was trained with the Wasserstein objective
 SWD_KEY, MSSSIM_KEY, SPECTRUM_KEY, MORPH_KEY, SKELETON_KEY, SHOLL_KEY, BRANCH_KEY = (m.key for m in METRICS)
 
 
@@ -129,6 +131,8 @@ class Checkpointer:
             checkpoint_dict['optimizer_state'] = self.trainer.optimizer_state()
             if getattr(self.trainer, 'ema_enabled', False):
                 checkpoint_dict[EMA_KEY] = cpu(self.trainer.ema_state())
+            if hasattr(self.trainer, 'objective'):
+                checkpoint_dict[OBJECTIVE_KEY] = self.trainer.objective
         for m in METRICS:
             if getattr(self, m.key):
                 checkpoint_dict[m.key] = [dict(entry) for entry in getattr(self, m.key)]
@@ -145,6 +149,11 @@ class Checkpointer:
         implementation does not reproduce.)"""
         source = self.filename if filename is None else filename
         checkpoint_dict = load_checkpoint_dict(source, self.device)
+        if filename is None and hasattr(self.trainer, 'objective'):
+            saved = checkpoint_dict.get(OBJECTIVE_KEY, 'wasserstein')
+            if saved != self.trainer.objective:
+                raise ValueError('{} was trained with the {} objective and cannot be resumed with the {} objective'.format(
+                    source, saved, self.trainer.objective))
         if filename is None:
             self.epoch = checkpoint_dict['epoch']
             self.Loss_real[:self.epoch] = checkpoint_dict['Loss_real']
