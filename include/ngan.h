@@ -365,7 +365,12 @@ int ngan_first_block_dx(const float* gc, const float* tables, float* gx, int B, 
  *   params  B records { float cos, sin, tx, ty, brightness, contrast; int flip, contrast_first; }   (32 bytes)
  *           source pixel = nearest([cos, sin; -sin, cos] * (dst - (tx, ty))) in centred pixel coordinates, 0 outside
  *   out     (B, S, S) in [-1, 1]: centre crop R x R of the P x P canvas, renormalised, down-sampled to S x S (S divides R) with the
- *           antialiased bilinear (triangle) filter;  workspace: ngan_augment_workspace_bytes(B, P) bytes */
+ *           antialiased bilinear (triangle) filter
+ *   workspace  ngan_augment_workspace_bytes(B, P) bytes (0 for B <= 0 or P <= 0), fp32, every element overwritten by a call:
+ *           B canvases of P x P floats -- canvas b = flip(affine(src[idx[b]])), with brightness (clamped to [0, 1]) applied iff
+ *           contrast_first == 0 -- then B x nblk partial sums, nblk = ceil(P P / 2048): partial (b, t) is the sum of the elements
+ *           [2048 t, min(2048 (t + 1), P P)) of canvas b in row-major order, added in a fixed order.  The contrast mean is the sum
+ *           of a sample's nblk partials over P P.  After the call both are there to be read (tests/test_gpu_augment.py does). */
 size_t ngan_augment_workspace_bytes(int B, int P);
 int ngan_augment_batch(const float* src, const int* idx, const void* params, float* workspace, float* out,
                        int N, int B, int P, int R, int S, void* stream);
