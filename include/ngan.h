@@ -289,7 +289,9 @@ int ngan_final_dot_dw_acc(const float* y, const float* go, float* gW, float* gb,
  *   n_hyper                 the number of floats the caller put into `hyper`: must equal NGAN_ADAM_HYPER_FLOATS.  (`hyper` grew from 5
  *                           to 9 floats in round 3; the count is checked so that a binding written against the older layout gets
  *                           NGAN_ERR_ARG instead of a kernel that reads past its buffer.  ngan_linear_wgrad_adam takes the same pair.)
- * chunk_seg / chunk_off (device int32 / int64): work list, one entry per 4096-element chunk. */
+ * chunk_seg / chunk_off (device int32 / int64): work list, one entry per 4096-element chunk.
+ * Non-finite gradients leave what torch leaves: NaN gives NaN in m, v and p; +-inf gives v = inf, p = NaN and m = +-inf, or NaN once
+ * 1 - beta1 >= 0.5 (torch's lerp_ evaluates g - (g - m) beta1 from that weight on). */
 #define NGAN_ADAM_HYPER_FLOATS 9
 int ngan_adam_step(float* p, const float* g, float* m, float* v, const long* seg_off, const long* seg_len,
                    const int* seg_active, float* seg_step, int n_seg, const int* chunk_seg, const long* chunk_off,

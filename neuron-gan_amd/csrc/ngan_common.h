@@ -76,7 +76,10 @@ __device__ __forceinline__ AdamCoef adam_coef(const float* __restrict__ hyper, f
 }
 __device__ __forceinline__ void adam_update(const AdamCoef& k, float g, float& p, float& m, float& v) {
     const float gv = g * k.gscale;                                 // 1/world_size after a SUM exchange, else 1
-    const float mv = fmaf(k.omb1, gv - m, m);                      // m.lerp_(g, 1 - beta1)
+    float mv = fmaf(k.omb1, gv - m, m);                            // m.lerp_(g, 1 - beta1)
+    // class compatibility with torch only: from the weight 1 - beta1 = 0.5 on (the default beta1 = 0.5) lerp_ evaluates g - (g - m) beta1,
+    // which is inf - inf = NaN for an infinite g where the fma gives inf.  Finite values are untouched; p' is NaN either way.
+    if (k.omb1 >= 0.5f && __builtin_isinf(gv)) mv = __builtin_nanf("");
     const float vv = fmaf(k.b2, v, k.omb2 * gv * gv);             // v.mul_(beta2).addcmul_(g, g, 1 - beta2)
     m = mv;
     v = vv;

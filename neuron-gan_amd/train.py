@@ -30,7 +30,9 @@ from .scoring import (score_branches, score_due, score_morph, score_msssim, scor
                       score_spectrum, score_swd)
 from .utils import sample_latent_vec, sample_latent_vec_device
 
-ADAM_CHUNK = 4096  # elements per work item of ngan_adam_step / ngan_rmsprop_step (must match csrc/adam.hip)
+# elements per work item of ngan_adam_step / ngan_rmsprop_step; must match CHUNK of csrc/adam.hip -- tests/test_gpu_optim.py holds the two
+# together: tensors of 4095, 4096 and 4097 elements against fp64 with sentinels in every alignment gap (a mismatch skips or overruns)
+ADAM_CHUNK = 4096
 SEG_ALIGN = 64     # parameters start on 256-byte boundaries inside the flat buffers
 
 
