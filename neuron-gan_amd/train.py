@@ -1,6 +1,6 @@
 """The PGGAN / WGAN-GP training-step driver on MI355X.
 
-Restates the reference's hot loop (/root/reference/train.py:350-394: n_critic x [D loss + gradient penalty, backward,
+Restates the reference's hot loop (train.py:350-394: n_critic x [D loss + gradient penalty, backward,
 Adam], then G loss, backward, Adam) as an engine object instead of module-level script code:
 
   * every parameter of a net is re-homed into ONE flat fp32 buffer, and every gradient into another, so that
@@ -12,9 +12,12 @@ Adam], then G loss, backward, Adam) as an engine object instead of module-level 
     (train.py:384) are not computed.
 
 The epoch-level semantics (LR schedule train.py:232-265, per-epoch alpha advance and growth train.py:318-333) are
-provided by `lr_schedule` / `PGGANTrainer.start_epoch`; data loading, plotting and checkpoints are out of scope.
+provided by `lr_schedule` / `PGGANTrainer.start_epoch`.  The second half of the file is the reference's train.py as functions: the
+epoch drivers `pggan_train` / `wgan_train` (batches from a dataset, monitors, checkpoints with sample grids and metrics) and the
+command line (`main`).
 """
 import contextlib
+import gc
 import math
 import os
 
@@ -23,7 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import _C, ops, wgan_ops
-from .launch import check_sharding, longest_share, shard_bounds
+from .launch import check_sharding, epoch_batches, longest_share, shard_bounds
 from .loss_functions import D_LS_module, D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_LS_module, G_W_loss
 from .metric_table import METRICS, settings
 from .scoring import (score_branches, score_due, score_morph, score_msssim, score_sholl, score_skeleton,  # noqa: F401
@@ -368,45 +371,6 @@ def lr_schedule(epoch, base_lr, transit_sch, n_epochs, total_decay=1 / 100):
     return None
 
 
-def _init_share(trainer):
-    """the device scalar that roots every backward of a data-parallel step (see _set_share); one rank keeps the constant `_one`"""
-    trainer._one = torch.ones((), device=trainer.device)
-    trainer._share = torch.ones((), device=trainer.device) if trainer.world > 1 else None
-    trainer._root = trainer._one if trainer.world == 1 else trainer._share
-    trainer._longest = None
-
-
-def _set_share(trainer, b, global_batch):
-    """Before a step on this rank's b samples of a global batch.  global_batch: None -- world * b, equal shares; an int -- the size of
-    the global batch, shared out by the sharding rule (what the epoch drivers pass); a sequence -- every rank's share in rank order,
-    for any other split.  Writes the weight
-    w = b * world / global_batch into device memory.  Every loss is a per-sample mean, so sum_ranks(w_r * grad_r) / world -- the
-    all-reduce and the 1/world of the optimiser launch -- is the gradient of the whole batch's mean whatever the shares are.  The
-    backward passes read w from the device, so a captured graph replays with the weight of the moment; the write itself is never
-    captured (a capture would freeze its value)."""
-    if trainer.world == 1:
-        whole = sum(global_batch) if isinstance(global_batch, (tuple, list)) else global_batch
-        if whole is not None and int(whole) != int(b):
-            raise ValueError(f"one rank holds the whole batch: global_batch={global_batch}, batch {b}")
-        return
-    if global_batch is None:
-        gb, longest = trainer.world * b, None
-    elif isinstance(global_batch, (tuple, list)):                  # every rank's share, in rank order
-        shares = [int(v) for v in global_batch]
-        if len(shares) != trainer.world or min(shares) < 1 or shares[dist.get_rank(trainer.group)] != b:
-            raise ValueError(f"shares {shares} of {trainer.world} ranks do not give this rank its {b} samples")
-        gb, longest = sum(shares), max(shares)
-    else:                                                          # shares by the sharding rule (launch.shard_bounds)
-        gb = int(global_batch)
-        longest = longest_share(gb, trainer.world)
-        if not 0 < b <= longest:
-            raise ValueError(f"this rank's {b} samples are no share of a global batch of {gb} over {trainer.world} ranks by the "
-                             f"sharding rule (at most {longest}); pass every rank's share instead")
-    trainer._longest = longest
-    if not (trainer.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
-        trainer._share.fill_(b * trainer.world / gb)
-
-
 def _check_ema_beta(ema_beta):
     """0 or None: averaging off (-> None); else a decay in (0, 1)"""
     if ema_beta is None or float(ema_beta) == 0.0:
@@ -565,12 +529,254 @@ class _AveragedGenerator:
                 e.copy_(w)
 
 
-class PGGANTrainer(_AveragedGenerator):
+@contextlib.contextmanager
+def _collector_off():
+    """The context of every stream capture: collect the cyclic garbage now, then no collection until the capture has ended."""
+    # No cyclic garbage collection while a capture is active: a collection that happens to start inside the captured region runs
+    # the finalizers of whatever cyclic garbage earlier code left behind on the capturing thread.  The one that must not run there
+    # is torch.cuda.CUDAGraph's: destroying an EARLIER captured graph (hipGraphExecDestroy / hipGraphDestroy and the release of its
+    # private pool) while a global-mode capture is active fails with hipErrorStreamCaptureUnsupported, which a destructor can only
+    # turn into std::terminate -- the `Fatal Python error: Aborted` under "Garbage-collecting" (the third
+    # capture of a process: the first two trainers' graphs were cyclic garbage by then).  Events, tensors of a released graph pool
+    # and tensors recorded on a second stream are harmless (tools/gc_capture_probe.py, one case per child process:
+    # profiles/r04_gc_capture_probe.txt).  torch.cuda.graph() no longer collects on entry by itself.  Collect now, then keep the
+    # collector off until the capture ends.  This concerns GLOBAL-mode captures (one GPU, no process group); with an RCCL group
+    # the captures run in thread_local mode, where a graph destroyed on ANOTHER thread is legal -- the collector could still pick the
+    # capturing thread, so it is kept off in both modes (gc.disable() is process-wide, for the few milliseconds of a capture).
+    # Regression: tests/test_gpu_train.py::test_capture_survives_garbage_left_by_earlier_trainers.
+    gc.collect()
+    gc_was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if gc_was_enabled:
+            gc.enable()
+
+
+class _Trainer(_AveragedGenerator):
+    """What PGGANTrainer and WGANTrainer share: the flat parameter sets with their optimiser pair, the share weight of a data-parallel
+    step, the communication stream, the optimiser state of a checkpoint, the registry of captured graphs and the two pieces of the
+    capture protocol (`_warm_up_on_snapshot`, then the capture itself under `_collector_off`)."""
+
+    _NO_GRAPH = _NO_GRAPH_FOR = None     # replay()'s two complaints (the second takes the input shape), set by the subclass
+
+    def _init_engine(self, optimizer, critic_optimizers, learning_rate, beta1, rmsprop_alpha, rmsprop_eps, ema_beta, exchanging,
+                     comm_stream):
+        """The tail of construction, after the subclass validated its arguments and set G, D, device, world and group.
+        critic_optimizers: the critic's class per optimiser kind (OPTIMIZERS, or the clipping ones); exchanging: gradients are
+        summed over the ranks, so 1/world goes into both optimiser launches; comm_stream: make a communication stream (each trainer
+        has its own rule for when)."""
+        self.optimizer_kind = optimizer
+        opt_cls = OPTIMIZERS[optimizer]
+        self.flat_g, self.flat_d = FlatParams(self.G, opt_cls.STATE), FlatParams(self.D, opt_cls.STATE)
+        args = (learning_rate, (beta1, 0.999)) if optimizer == "adam" else (learning_rate, rmsprop_alpha, rmsprop_eps)
+        self.opt_g = opt_cls(self.flat_g, *args, ema_beta=ema_beta)
+        self.opt_d = critic_optimizers[optimizer](self.flat_d, *args)
+        if exchanging:
+            self.opt_g.set_grad_scale(1.0 / self.world)
+            self.opt_d.set_grad_scale(1.0 / self.world)
+        self.last_z_g = None
+        self._init_share()
+        # collectives of the RCCL backend run on a stream of their own (see _on_comm_stream)
+        self._comm_stream = torch.cuda.Stream(device=self.device) if comm_stream else None
+        self.comm_timing = None     # bench.py, tools/wgan_time.py: a list that receives (tag, start event, end event) of every collective
+        self._graphs = {}           # graph key -> the entry of the graphs captured for it (capture / replay)
+        self._graph = self._entry = None    # the most recently captured graph or graphs, and their entry
+
+    # ---- the share weight -------------------------------------------------------------------------------------
+    def _init_share(self):
+        """the device scalar that roots every backward of a data-parallel step (see _set_share); one rank keeps the constant `_one`"""
+        self._one = torch.ones((), device=self.device)
+        self._share = torch.ones((), device=self.device) if self.world > 1 else None
+        self._root = self._one if self.world == 1 else self._share
+        self._longest = None
+
+    def _set_share(self, b, global_batch):
+        """Before a step on this rank's b samples of a global batch.  global_batch: None -- world * b, equal shares; an int -- the size of
+        the global batch, shared out by the sharding rule (what the epoch drivers pass); a sequence -- every rank's share in rank order,
+        for any other split.  Writes the weight
+        w = b * world / global_batch into device memory.  Every loss is a per-sample mean, so sum_ranks(w_r * grad_r) / world -- the
+        all-reduce and the 1/world of the optimiser launch -- is the gradient of the whole batch's mean whatever the shares are.  The
+        backward passes read w from the device, so a captured graph replays with the weight of the moment; the write itself is never
+        captured (a capture would freeze its value)."""
+        if self.world == 1:
+            whole = sum(global_batch) if isinstance(global_batch, (tuple, list)) else global_batch
+            if whole is not None and int(whole) != int(b):
+                raise ValueError(f"one rank holds the whole batch: global_batch={global_batch}, batch {b}")
+            return
+        if global_batch is None:
+            gb, longest = self.world * b, None
+        elif isinstance(global_batch, (tuple, list)):                  # every rank's share, in rank order
+            shares = [int(v) for v in global_batch]
+            if len(shares) != self.world or min(shares) < 1 or shares[dist.get_rank(self.group)] != b:
+                raise ValueError(f"shares {shares} of {self.world} ranks do not give this rank its {b} samples")
+            gb, longest = sum(shares), max(shares)
+        else:                                                          # shares by the sharding rule (launch.shard_bounds)
+            gb = int(global_batch)
+            longest = longest_share(gb, self.world)
+            if not 0 < b <= longest:
+                raise ValueError(f"this rank's {b} samples are no share of a global batch of {gb} over {self.world} ranks by the "
+                                 f"sharding rule (at most {longest}); pass every rank's share instead")
+        self._longest = longest
+        if not (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            self._share.fill_(b * self.world / gb)
+
+    def _latent(self, batch, z):
+        if z is not None:
+            return z
+        if self.device_latents:
+            return sample_latent_vec_device((batch, self.G.latent_dim), self.device)
+        return sample_latent_vec((batch, self.G.latent_dim), device=self.device)
+
+    def set_lr(self, lr):
+        self.opt_d.set_lr(lr)
+        self.opt_g.set_lr(lr)
+
+    def _on_comm_stream(self, fn, tag="exchange"):
+        """Run the collectives of `fn` on this trainer's communication stream, ordered after the work already queued on the current
+        stream and before whatever the current stream does next.
+
+        Why a stream of their own (the abort on record: gpurun_out/fd2.log of round 1, tools/capture_event_probe.py reproduces it):
+        a synchronous c10d collective records its completion event on the stream it was issued on, and the process group's
+        watchdog thread polls that event with hipEventQuery until a poll finds it complete (~100 ms period).  HIP refuses
+        hipEventQuery on an event whose last-recorded stream is part of an ACTIVE capture (hipErrorCapturedEvent) and the watchdog
+        turns that into std::terminate.  Streams of the training code do become part of captures: a captured backward pass forks
+        the stream on which a parameter's AccumulateGrad node was created into the capture.  So a collective issued on such a stream
+        shortly before capture() (warm-up iterations, the exchanges between captured segments, the last replayed step before a growth
+        event's re-capture) killed the process whenever the watchdog had not polled it yet.  Nothing but collectives ever runs on the
+        communication stream -- no autograd node is created on it, no capture is begun on it, no captured stream waits on it -- so it
+        can never be part of a capture and the watchdog may poll its events at any time.  (CPU tensors / the gloo rehearsal have no
+        such event and run in line.)"""
+        timed = self.comm_timing is not None and self.device.type == "cuda"
+        if self._comm_stream is None:
+            if timed:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                self.comm_timing.append((tag, e0, e1))
+                return None
+            return fn()
+        cur = torch.cuda.current_stream()
+        self._comm_stream.wait_stream(cur)
+        with torch.cuda.stream(self._comm_stream):
+            if timed:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            fn()
+            if timed:
+                e1.record()
+                self.comm_timing.append((tag, e0, e1))
+        cur.wait_stream(self._comm_stream)
+
+    # ---- optimiser state for checkpoints (optional extra key; the reference saves none) ---------------------------
+    def optimizer_state(self):
+        """{"kind": "adam" | "rmsprop", "G": ..., "D": ...}: per net the tensor names, lr, per-tensor step counts and, per state buffer of
+        the optimiser (exp_avg + exp_avg_sq, or square_avg), one tensor per name"""
+        out = {"kind": self.optimizer_kind}
+        for tag, flat, opt in (("G", self.flat_g, self.opt_g), ("D", self.flat_d, self.opt_d)):
+            out[tag] = {"names": list(flat.names), "lr": opt.param_groups[0]["lr"],
+                        "step": flat.seg_step.detach().cpu().clone()}
+            for buf in opt.STATE:
+                out[tag][buf] = {n: getattr(flat, buf)[o:o + p.numel()].detach().cpu().clone().view(p.shape)
+                                 for n, p, o in zip(flat.names, flat.params, flat.offsets)}
+        return out
+
+    def reset_optimizer_state(self):
+        """a fresh optimiser: state buffers and per-tensor step counts back to zero (learning rates stay)"""
+        for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
+            for buf in opt.STATE:
+                getattr(flat, buf).zero_()
+            flat.seg_step.zero_()
+
+    def load_optimizer_state(self, state):
+        """state of optimizer_state(); one without "kind" (the checkpoints written before RMSprop existed) is an Adam state.  A state
+        of the other optimiser raises ValueError."""
+        kind = state.get("kind", "adam")
+        if kind != self.optimizer_kind:
+            raise ValueError(f"optimizer state of kind {kind!r} cannot be loaded into a {self.optimizer_kind!r} trainer")
+        for tag, flat, opt in (("G", self.flat_g, self.opt_g), ("D", self.flat_d, self.opt_d)):
+            st = state[tag]
+            saved_step = dict(zip(st["names"], st["step"].tolist()))
+            steps = flat.seg_step.detach().cpu().clone()
+            first = st[opt.STATE[0]]
+            for i, (n, p, o) in enumerate(zip(flat.names, flat.params, flat.offsets)):
+                if n in first and tuple(first[n].shape) == tuple(p.shape):
+                    for buf in opt.STATE:
+                        getattr(flat, buf)[o:o + p.numel()].copy_(st[buf][n].reshape(-1))
+                    steps[i] = saved_step.get(n, 0.0)
+            flat.seg_step.copy_(steps)
+            opt.set_lr(st["lr"])
+
+    # ---- HIP-graph capture of a whole iteration ---------------------------------------------------------------
+    def _training_state(self):
+        """everything a training iteration changes on the device (parameters, optimiser state and step counts, the averaged
+        generator when there is one, the device RNG)"""
+        bufs = []
+        for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
+            bufs += [flat.flat] + [getattr(flat, buf) for buf in opt.STATE] + [flat.seg_step]
+            if flat.ema is not None:
+                bufs.append(flat.ema)
+        return bufs
+
+    def _warm_up_on_snapshot(self, iteration, warmup, generators=()):
+        """The first piece of capture(): `warmup` (at least one) calls of `iteration` on a side stream -- they register and allocate
+        the packed weight copies, workspaces and the allocator's blocks outside the capture -- and train nothing: `_training_state()`,
+        the device RNG state and the state of the trainer's further `generators` are snapshot before and restored afterwards."""
+        state = self._training_state()
+        saved = [t.clone() for t in state]
+        rng = torch.cuda.get_rng_state(self.device)
+        gen_states = [g.get_state() for g in generators]
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                iteration()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        del saved
+        torch.cuda.set_rng_state(rng, self.device)
+        for g, st in zip(generators, gen_states):
+            g.set_state(st)
+
+    def _graph_key(self, shape, global_batch=None):
+        """Graphs are kept per input shape and, data parallel with a stated global batch, per global batch size.  A capture contains
+        collectives (its warm-up iterations and the exchanges between its segments), so all ranks must capture at the same step; the
+        global batch size is what every rank sees alike, while one rank's share of two global sizes can have the same shape where
+        another rank's has not.  (The captured generator update also reads the gathered stem factors, whose row count
+        world x longest share follows from the global size.)  The share weight itself is read from device memory."""
+        if self.world == 1 or global_batch is None:
+            return tuple(shape)
+        return tuple(shape) + ("global", tuple(global_batch) if isinstance(global_batch, (tuple, list)) else int(global_batch))
+
+    def has_graph(self, shape, global_batch=None):
+        return self._graph_key(shape, global_batch) in self._graphs
+
+    def _entry_for(self, real, global_batch=None):
+        """The entry replay() runs: the one captured for `real`'s shape, with `real` copied into its static input; without `real` the
+        most recently captured one, its static input as it stands."""
+        if real is None:
+            if self._graph is None:
+                raise RuntimeError(self._NO_GRAPH)
+            return self._entry
+        entry = self._graphs.get(self._graph_key(real.shape, global_batch))
+        if entry is None:
+            raise RuntimeError(self._NO_GRAPH_FOR.format(tuple(real.shape)))
+        entry[1].copy_(real, non_blocking=True)
+        return entry
+
+
+class PGGANTrainer(_Trainer):
     """One object per process (= per GPU).  `train_iteration(real)` is train.py:356-385 with sim_loss off.
 
     Data parallel (an initialised process group): every rank trains its share of the global batch; `global_batch` (an argument of
     step / train_iteration / d_compute / g_compute / replay: the global batch size, or every rank's share; default world * this rank's
     batch) makes unequal shares exact -- see `_set_share`."""
+    _NO_GRAPH = "call capture() first (and again after every growth event)"
+    _NO_GRAPH_FOR = "no graphs captured for input shape {}: " + _NO_GRAPH
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
@@ -602,15 +808,11 @@ class PGGANTrainer(_AveragedGenerator):
         self.n_critic = n_critic
         self.alpha_step = alpha_step
         self.device_latents = device_latents
-        self.optimizer_kind = optimizer
-        opt_cls = OPTIMIZERS[optimizer]
-        self.flat_g, self.flat_d = FlatParams(generator, opt_cls.STATE), FlatParams(discriminator, opt_cls.STATE)
-        if optimizer == "adam":
-            self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999), ema_beta=ema_beta)
-            self.opt_d = FusedAdam(self.flat_d, learning_rate, (beta1, 0.999))
-        else:
-            self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps, ema_beta=ema_beta)
-            self.opt_d = FusedRMSprop(self.flat_d, learning_rate, rmsprop_alpha, rmsprop_eps)
+        self.group = process_group
+        grouped = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size(process_group) if grouped else 1
+        self._init_engine(optimizer, OPTIMIZERS, learning_rate, beta1, rmsprop_alpha, rmsprop_eps, ema_beta, exchanging=self.world > 1,
+                          comm_stream=self.device.type == "cuda" and grouped and dist.get_backend(process_group) == "nccl")
         self.objective = objective
         if objective == "lsgan":
             self.d_loss = D_LS_module(generator, discriminator, check_nan=False)
@@ -619,13 +821,9 @@ class PGGANTrainer(_AveragedGenerator):
             self.d_loss = D_W_loss(generator, discriminator, drift_epsilon=drift_epsilon, check_nan=False)
             self.g_loss = G_W_loss(generator, discriminator, check_nan=False)
         self.gp_loss = D_grad_pen_loss(generator, discriminator, Lambda=grad_pen_lambda)
-        self.group = process_group
-        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.stem = None
         self._stem_grad_skipped = self._stem_sink_active = self._stem_for_exchange = False
         if self.world > 1:
-            self.opt_g.set_grad_scale(1.0 / self.world)
-            self.opt_d.set_grad_scale(1.0 / self.world)
             self.enable_stem_exchange()
         # The generator stem's weight gradient is not stored when the stem qualifies (GPU, latent_dim a multiple of 16, at most 512):
         # g_step hands its factors to the Adam launch (FusedAdam.step).  g_compute on its own still stores it.  fused_stem=False: never.
@@ -633,15 +831,6 @@ class PGGANTrainer(_AveragedGenerator):
         if fused_stem or (fused_stem is None and self.device.type == "cuda"):
             self.enable_fused_stem()
         self.force_exchange = False
-        self.last_z_g = None
-        _init_share(self)
-        # collectives of the RCCL backend run on a stream of their own (see _on_comm_stream); created on first need
-        self._comm_stream = None
-        self.comm_timing = None     # bench.py: a list that receives (tag, start event, end event) of every gradient exchange
-        if self.device.type == "cuda" and dist.is_available() and dist.is_initialized() and dist.get_backend(process_group) == "nccl":
-            self._comm_stream = torch.cuda.Stream(device=self.device)
-        self._graphs = {}          # input shape -> captured graphs of this stage (capture / replay)
-        self._graph = self._entry = None
         self._aug = None
         self._aug_step = 0         # which critic step of the iteration d_compute serves (train_iteration counts)
         if aug_mask:
@@ -717,50 +906,6 @@ class PGGANTrainer(_AveragedGenerator):
         return changed
 
     # ---- the two half-steps ---------------------------------------------------------------------------------
-    def _latent(self, batch, z):
-        if z is not None:
-            return z
-        if self.device_latents:
-            return sample_latent_vec_device((batch, self.G.latent_dim), self.device)
-        return sample_latent_vec((batch, self.G.latent_dim), device=self.device)
-
-    def _on_comm_stream(self, fn, tag="exchange"):
-        """Run the collectives of `fn` on this trainer's communication stream, ordered after the work already queued on the current
-        stream and before whatever the current stream does next.
-
-        Why a stream of their own (the abort on record: gpurun_out/fd2.log of round 1, tools/capture_event_probe.py reproduces it):
-        a synchronous c10d collective records its completion event on the stream it was issued on, and the process group's
-        watchdog thread polls that event with hipEventQuery until a poll finds it complete (~100 ms period).  HIP refuses
-        hipEventQuery on an event whose last-recorded stream is part of an ACTIVE capture (hipErrorCapturedEvent) and the watchdog
-        turns that into std::terminate.  Streams of the training code do become part of captures: a captured backward pass forks
-        the stream on which a parameter's AccumulateGrad node was created into the capture.  So a collective issued on such a stream
-        shortly before capture() (warm-up iterations, the exchanges between captured segments, the last replayed step before a growth
-        event's re-capture) killed the process whenever the watchdog had not polled it yet.  Nothing but collectives ever runs on the
-        communication stream -- no autograd node is created on it, no capture is begun on it, no captured stream waits on it -- so it
-        can never be part of a capture and the watchdog may poll its events at any time.  (CPU tensors / the gloo rehearsal have no
-        such event and run in line.)"""
-        timed = self.comm_timing is not None and self.device.type == "cuda"
-        if self._comm_stream is None:
-            if timed:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                self.comm_timing.append((tag, e0, e1))
-                return None
-            return fn()
-        cur = torch.cuda.current_stream()
-        self._comm_stream.wait_stream(cur)
-        with torch.cuda.stream(self._comm_stream):
-            if timed:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            fn()
-            if timed:
-                e1.record()
-                self.comm_timing.append((tag, e0, e1))
-        cur.wait_stream(self._comm_stream)
-
     def _exchange(self, flat):
         if flat is self.flat_g and self._stem_sink_active:
             # the stem occupies the head of G's flat buffer: gather its factors, all-reduce only the tail
@@ -777,7 +922,7 @@ class PGGANTrainer(_AveragedGenerator):
     def d_compute(self, real, z_d=None, z_gp=None, eps=None, global_batch=None):
         """D half-step up to (and including) the backward pass: gradients end up in flat_d.grad."""
         b = real.size(0)
-        _set_share(self, b, global_batch)
+        self._set_share(b, global_batch)
         self.flat_d.ensure_grad_views()
         self.flat_d.zero_grad()  # Discriminator_net.zero_grad(), train.py:357
         # the two detached generator passes of the D step (loss_functions.py:26, 167) run as one batch-2b pass; with the penalty
@@ -818,7 +963,7 @@ class PGGANTrainer(_AveragedGenerator):
     def g_compute(self, real, z=None, skip_stem_grad=False, global_batch=None):
         """skip_stem_grad (g_step with fused_stem): the stem's gradient is neither zeroed nor stored -- its factors wait in self.stem"""
         b = real.size(0)
-        _set_share(self, b, global_batch)
+        self._set_share(b, global_batch)
         self.flat_g.ensure_grad_views()
         self._stem_grad_skipped = bool(skip_stem_grad and self.fused_stem)
         if self._stem_grad_skipped:
@@ -890,66 +1035,6 @@ class PGGANTrainer(_AveragedGenerator):
         stats.update(self.g_step(real, z_g, global_batch))
         return stats
 
-    # ---- optimiser state for checkpoints (optional extra key; the reference saves none) ---------------------------
-    def optimizer_state(self):
-        """{"kind": "adam" | "rmsprop", "G": ..., "D": ...}: per net the tensor names, lr, per-tensor step counts and, per state buffer of
-        the optimiser (exp_avg + exp_avg_sq, or square_avg), one tensor per name"""
-        out = {"kind": self.optimizer_kind}
-        for tag, flat, opt in (("G", self.flat_g, self.opt_g), ("D", self.flat_d, self.opt_d)):
-            out[tag] = {"names": list(flat.names), "lr": opt.param_groups[0]["lr"],
-                        "step": flat.seg_step.detach().cpu().clone()}
-            for buf in opt.STATE:
-                out[tag][buf] = {n: getattr(flat, buf)[o:o + p.numel()].detach().cpu().clone().view(p.shape)
-                                 for n, p, o in zip(flat.names, flat.params, flat.offsets)}
-        return out
-
-    def reset_optimizer_state(self):
-        """a fresh optimiser: state buffers and per-tensor step counts back to zero (learning rates stay)"""
-        for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
-            for buf in opt.STATE:
-                getattr(flat, buf).zero_()
-            flat.seg_step.zero_()
-
-    def load_optimizer_state(self, state):
-        """state of optimizer_state(); one without "kind" (the checkpoints written before RMSprop existed) is an Adam state.  A state
-        of the other optimiser raises ValueError."""
-        kind = state.get("kind", "adam")
-        if kind != self.optimizer_kind:
-            raise ValueError(f"optimizer state of kind {kind!r} cannot be loaded into a {self.optimizer_kind!r} trainer")
-        for tag, flat, opt in (("G", self.flat_g, self.opt_g), ("D", self.flat_d, self.opt_d)):
-            st = state[tag]
-            saved_step = dict(zip(st["names"], st["step"].tolist()))
-            steps = flat.seg_step.detach().cpu().clone()
-            first = st[opt.STATE[0]]
-            for i, (n, p, o) in enumerate(zip(flat.names, flat.params, flat.offsets)):
-                if n in first and tuple(first[n].shape) == tuple(p.shape):
-                    for buf in opt.STATE:
-                        getattr(flat, buf)[o:o + p.numel()].copy_(st[buf][n].reshape(-1))
-                    steps[i] = saved_step.get(n, 0.0)
-            flat.seg_step.copy_(steps)
-            opt.set_lr(st["lr"])
-
-    # ---- HIP-graph capture of a whole iteration ---------------------------------------------------------------
-    def _training_state(self):
-        """everything a training iteration changes on the device (parameters, optimiser state and step counts, the averaged
-        generator when there is one, the device RNG)"""
-        bufs = []
-        for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
-            bufs += [flat.flat] + [getattr(flat, buf) for buf in opt.STATE] + [flat.seg_step]
-            if flat.ema is not None:
-                bufs.append(flat.ema)
-        return bufs
-
-    def _graph_key(self, shape, global_batch=None):
-        """Graphs are kept per input shape and, data parallel with a stated global batch, per global batch size.  A capture contains
-        collectives (its warm-up iterations and the exchanges between its segments), so all ranks must capture at the same step; the
-        global batch size is what every rank sees alike, while one rank's share of two global sizes can have the same shape where
-        another rank's has not.  (The captured generator update also reads the gathered stem factors, whose row count
-        world x longest share follows from the global size.)  The share weight itself is read from device memory."""
-        if self.world == 1 or global_batch is None:
-            return tuple(shape)
-        return tuple(shape) + ("global", tuple(global_batch) if isinstance(global_batch, (tuple, list)) else int(global_batch))
-
     def capture(self, real_example, warmup=1, draws=None, global_batch=None, tables=None):
         """Capture `train_iteration` for this batch shape into HIP graphs (latents and epsilon drawn on the GPU inside
         the graph).  Afterwards `replay(real)` copies `real` into the static input of the graphs captured for its shape and
@@ -978,26 +1063,11 @@ class PGGANTrainer(_AveragedGenerator):
         if segmented and self.n_critic != 1:
             raise RuntimeError("segmented (data-parallel) capture supports n_critic = 1")
         static_real = real_example.clone()
-        _set_share(self, static_real.size(0), global_batch)     # the write stays outside the captures
+        self._set_share(static_real.size(0), global_batch)     # the write stays outside the captures
         n_packed_before = ops.registry_size()
-        state = self._training_state()
-        saved = [t.clone() for t in state]
-        rng = torch.cuda.get_rng_state(self.device)
-        aug_rng = self._aug.generator.get_state() if self._aug is not None else None
         lr_g, lr_d = self.opt_g.param_groups[0]["lr"], self.opt_d.param_groups[0]["lr"]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self.train_iteration(static_real, *d_args, z_g, global_batch, tables)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        for t, v in zip(state, saved):
-            t.copy_(v)
-        del saved
-        torch.cuda.set_rng_state(rng, self.device)
-        if aug_rng is not None:
-            self._aug.generator.set_state(aug_rng)
+        self._warm_up_on_snapshot(lambda: self.train_iteration(static_real, *d_args, z_g, global_batch, tables), warmup,
+                                  (self._aug.generator,) if self._aug is not None else ())
         assert (lr_g, lr_d) == (self.opt_g.param_groups[0]["lr"], self.opt_d.param_groups[0]["lr"])
         ops.bump_weight_epoch()   # the warm-up registered every packed weight (persistent buffers, allocated outside capture):
         self.opt_d.repack()       # rebuild both re-pack tables now (from the restored parameters), so that the captured Adam
@@ -1022,27 +1092,8 @@ class PGGANTrainer(_AveragedGenerator):
         # watchdog terminates the process); thread_local polices the capturing thread only.  The second rule (an event whose stream
         # is part of the capture) is what _on_comm_stream takes care of.  Both reproduced case by case: tools/capture_event_probe.py.
         mode = "thread_local" if self._comm_stream is not None else "global"
-        # No cyclic garbage collection while a capture is active: a collection that happens to start inside the captured region runs
-        # the finalizers of whatever cyclic garbage earlier code left behind on the capturing thread.  The one that must not run there
-        # is torch.cuda.CUDAGraph's: destroying an EARLIER captured graph (hipGraphExecDestroy / hipGraphDestroy and the release of its
-        # private pool) while a global-mode capture is active fails with hipErrorStreamCaptureUnsupported, which a destructor can only
-        # turn into std::terminate -- the `Fatal Python error: Aborted` under "Garbage-collecting" of gpurun_out/r03_a_tests.log (third
-        # capture of a process: the first two trainers' graphs were cyclic garbage by then).  Events, tensors of a released graph pool
-        # and tensors recorded on a second stream are harmless (tools/gc_capture_probe.py, one case per child process:
-        # profiles/r04_gc_capture_probe.txt).  torch.cuda.graph() no longer collects on entry by itself.  Collect now, then keep the
-        # collector off until the capture ends.  This concerns GLOBAL-mode captures (one GPU, no process group); with an RCCL group
-        # the captures run in thread_local mode, where a graph destroyed on ANOTHER thread is legal -- the collector could still pick the
-        # capturing thread, so it is kept off in both modes (gc.disable() is process-wide, for the few milliseconds of a capture).
-        # Regression: tests/test_gpu_train.py::test_capture_survives_garbage_left_by_earlier_trainers.
-        import gc
-        gc.collect()
-        gc_was_enabled = gc.isenabled()
-        gc.disable()
-        try:
+        with _collector_off():
             graphs, stats = self._capture_segments(segmented, mode, static_real, d_args, z_g, global_batch)
-        finally:
-            if gc_was_enabled:
-                gc.enable()
         # Two things the captured launches reference besides the static input: (a) the stem's factor tensors (`StemGradExchange.sink`
         # ran during THIS capture; another shape's capture overwrites stem.captured, and the eager `finish()` between replayed
         # segments must read this graph's factors, not the most recent capture's); (b) the device re-pack tables whose pointers
@@ -1078,26 +1129,12 @@ class PGGANTrainer(_AveragedGenerator):
             self.flat_g.grad.zero_()
         return graphs, stats
 
-    def has_graph(self, shape, global_batch=None):
-        return self._graph_key(shape, global_batch) in self._graphs
-
     def replay(self, real=None, global_batch=None, tables=None):
         """One training iteration from the captured graphs.  `real` selects the graphs by its shape (capture() them first);
         without an argument the most recently captured graphs run on their static input as it stands.
         With a diffaug policy the iteration's tables are drawn (or copied from `tables`) first, eagerly."""
-        if real is not None:
-            entry = self._graphs.get(self._graph_key(real.shape, global_batch))
-            if entry is None:
-                raise RuntimeError(f"no graphs captured for input shape {tuple(real.shape)}: call capture() first (and again after "
-                                   f"every growth event)")
-            static_real = entry[1]
-            static_real.copy_(real, non_blocking=True)
-        else:
-            if self._graph is None:
-                raise RuntimeError("call capture() first (and again after every growth event)")
-            entry = self._entry
-        graphs, static_real, stats, stem_factors, _, stem_flags = entry
-        _set_share(self, static_real.size(0), global_batch)
+        graphs, static_real, stats, stem_factors, _, stem_flags = self._entry_for(real, global_batch)
+        self._set_share(static_real.size(0), global_batch)
         if self._aug is not None or tables is not None:
             self.draw_diffaug_tables(static_real.size(0), tables)
         if self.stem is not None:
@@ -1142,7 +1179,7 @@ class ClippedFusedRMSprop(_ClipMixin, FusedRMSprop):
                 f.chunk_seg[n0:], f.chunk_off[n0:], n_chunks, self.hyper, self.hyper.numel(), float(self.clip))
 
 
-class WGANTrainer(_AveragedGenerator):
+class WGANTrainer(_Trainer):
     """The reference's WGAN loop (train.py:470-506) for Generator_wgan / Discriminator_wgan: n_critic x [D(real), D(G(z).detach()),
     -mean + mean + drift * mean(real^2), backward, optimiser step, clamp every critic parameter to +-clip], then one generator step
     -mean(D(G(z))).  Both nets stay in train mode, so every forward uses batch statistics and updates the BatchNorm running buffers,
@@ -1159,6 +1196,8 @@ class WGANTrainer(_AveragedGenerator):
     same sequence of steps (the same n_critic: no adapt_critic over per-rank series).  Each rank draws its own latents: seed each rank
     differently.  Eager only: capture() raises and step() runs train_iteration.  Forwards outside the steps (a sample grid on rank 0,
     eval mode) issue no collective."""
+    _NO_GRAPH = "call capture() first"
+    _NO_GRAPH_FOR = "no graph captured for input shape {}: " + _NO_GRAPH
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, drift_epsilon=0.001, n_critic=1, clip=0.01,
                  optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None, sync_batchnorm=False,
@@ -1185,36 +1224,15 @@ class WGANTrainer(_AveragedGenerator):
         self.n_critic = int(n_critic)
         self.drift_epsilon = float(drift_epsilon)
         self.device_latents = device_latents
-        self.optimizer_kind = optimizer
         self.world = world
         self.group = process_group
         self.sync_batchnorm = bool(sync_batchnorm)
-        opt_cls = OPTIMIZERS[optimizer]
-        self.flat_g, self.flat_d = FlatParams(generator, opt_cls.STATE), FlatParams(discriminator, opt_cls.STATE)
-        self.flat_g.set_active(self.flat_g.params)
-        self.flat_d.set_active(self.flat_d.params)
-        if optimizer == "adam":
-            self.opt_g = FusedAdam(self.flat_g, learning_rate, (beta1, 0.999), ema_beta=ema_beta)
-            self.opt_d = ClippedFusedAdam(self.flat_d, learning_rate, (beta1, 0.999))
-        else:
-            self.opt_g = FusedRMSprop(self.flat_g, learning_rate, rmsprop_alpha, rmsprop_eps, ema_beta=ema_beta)
-            self.opt_d = ClippedFusedRMSprop(self.flat_d, learning_rate, rmsprop_alpha, rmsprop_eps)
+        self._init_engine(optimizer, {"adam": ClippedFusedAdam, "rmsprop": ClippedFusedRMSprop}, learning_rate, beta1, rmsprop_alpha,
+                          rmsprop_eps, ema_beta, exchanging=self.sync_batchnorm,
+                          comm_stream=self.sync_batchnorm and self.device.type == "cuda" and dist.get_backend(process_group) == "nccl")
+        self.refresh_stage()
         self.opt_d.clip = float(clip)
-        if self.sync_batchnorm:
-            self.opt_g.set_grad_scale(1.0 / world)
-            self.opt_d.set_grad_scale(1.0 / world)
         self._sync = None             # the wgan_ops.SyncBN handle, made on first use (this rank's index is read from the group then)
-        # collectives of the RCCL backend run on a stream of their own (PGGANTrainer._on_comm_stream)
-        self._comm_stream = None
-        self.comm_timing = None       # tools/wgan_time.py: a list that receives (tag, start event, end event) of every collective
-        if self.sync_batchnorm and self.device.type == "cuda" and dist.get_backend(process_group) == "nccl":
-            self._comm_stream = torch.cuda.Stream(device=self.device)
-        self.last_z_g = None
-        _init_share(self)
-        self._graphs = {}
-        self._graph = self._entry = None
-
-    _on_comm_stream = PGGANTrainer._on_comm_stream
 
     def _bn_sync(self):
         """the context of a step's passes: with sync_batchnorm, every training-mode BatchNorm2d call in it uses all ranks' statistics"""
@@ -1231,20 +1249,13 @@ class WGANTrainer(_AveragedGenerator):
             self._on_comm_stream(lambda: exchange_gradients(flat, self.world, self.group, force=True),
                                  "critic" if flat is self.flat_d else "generator")
 
-    def _latent(self, batch, z):
-        if z is not None:
-            return z
-        if self.device_latents:
-            return sample_latent_vec_device((batch, self.G.latent_dim), self.device)
-        return sample_latent_vec((batch, self.G.latent_dim), device=self.device)
-
     def _bn_buffers(self):
         return [b for net in (self.G, self.D) for b in net.buffers()]
 
     def d_compute(self, real, z=None, global_batch=None):
         """D_W_loss (loss_functions.py:14-45) and its backward: gradients end up in flat_d.grad"""
         b = real.size(0)
-        _set_share(self, b, global_batch)
+        self._set_share(b, global_batch)
         self.flat_d.ensure_grad_views()
         self.flat_d.zero_grad()
         with self._bn_sync():
@@ -1265,7 +1276,7 @@ class WGANTrainer(_AveragedGenerator):
 
     def g_compute(self, real, z=None, global_batch=None):
         b = real.size(0)
-        _set_share(self, b, global_batch)
+        self._set_share(b, global_batch)
         self.flat_g.ensure_grad_views()
         self.flat_g.zero_grad()
         d_params = self.flat_d.params
@@ -1300,27 +1311,13 @@ class WGANTrainer(_AveragedGenerator):
         stats.update(self.g_step(real, z_g, global_batch))
         return stats
 
-    def set_lr(self, lr):
-        self.opt_d.set_lr(lr)
-        self.opt_g.set_lr(lr)
-
     def refresh_stage(self):
         """after parameters were loaded (Checkpointer): captured graphs are kept (they read the same buffers), nothing to re-mark"""
         self.flat_g.set_active(self.flat_g.params)
         self.flat_d.set_active(self.flat_d.params)
 
-    # ---- optimiser state for checkpoints: the same layout as PGGANTrainer's ----------------------------------------
-    optimizer_state = PGGANTrainer.optimizer_state
-    reset_optimizer_state = PGGANTrainer.reset_optimizer_state
-    load_optimizer_state = PGGANTrainer.load_optimizer_state
-
     def _training_state(self):
-        bufs = []
-        for flat, opt in ((self.flat_g, self.opt_g), (self.flat_d, self.opt_d)):
-            bufs += [flat.flat] + [getattr(flat, buf) for buf in opt.STATE] + [flat.seg_step]
-            if flat.ema is not None:
-                bufs.append(flat.ema)
-        return bufs + self._bn_buffers()
+        return super()._training_state() + self._bn_buffers()       # (both nets stay in train mode: every forward updates them)
 
     def capture(self, real_example, warmup=1, draws=None):
         """Capture one train_iteration for this batch shape into a graph (PGGANTrainer.capture without the data-parallel segments).
@@ -1334,56 +1331,25 @@ class WGANTrainer(_AveragedGenerator):
         dr = draws or {}
         z_d, z_g = dr.get("z_d"), dr.get("z_g")
         static_real = real_example.clone()
-        state = self._training_state()
-        saved = [t.clone() for t in state]
-        rng = torch.cuda.get_rng_state(self.device)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self.train_iteration(static_real, z_d, z_g)
-        torch.cuda.current_stream().wait_stream(side)
+        self._warm_up_on_snapshot(lambda: self.train_iteration(static_real, z_d, z_g), warmup)
         torch.cuda.synchronize()
-        for t, v in zip(state, saved):
-            t.copy_(v)
-        del saved
-        torch.cuda.set_rng_state(rng, self.device)
-        torch.cuda.synchronize()
-        import gc
-        gc.collect()
-        gc_was_enabled = gc.isenabled()
-        gc.disable()
-        try:
+        with _collector_off():
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 stats = self.train_iteration(static_real, z_d, z_g)
-        finally:
-            if gc_was_enabled:
-                gc.enable()
         self._graph, self._entry = graph, (graph, static_real, stats)
-        self._graphs[tuple(real_example.shape)] = self._entry
+        self._graphs[self._graph_key(real_example.shape)] = self._entry
         return graph
 
-    def has_graph(self, shape):
-        return tuple(shape) in self._graphs
-
     def replay(self, real=None):
-        if real is not None:
-            entry = self._graphs.get(tuple(real.shape))
-            if entry is None:
-                raise RuntimeError(f"no graph captured for input shape {tuple(real.shape)}: call capture() first")
-            entry[1].copy_(real, non_blocking=True)
-        else:
-            if self._graph is None:
-                raise RuntimeError("call capture() first")
-            entry = self._entry
-        entry[0].replay()
-        return entry[2]
+        graph, _, stats = self._entry_for(real)
+        graph.replay()
+        return stats
 
     def step(self, real, use_graph=True, global_batch=None):
         """graph replay when possible (capturing on first sight of a shape), else eager; always eager with sync_batchnorm"""
         if use_graph and self.device_latents and not self.sync_batchnorm:
-            _set_share(self, real.size(0), global_batch)      # (one rank: checks the argument, writes nothing)
+            self._set_share(real.size(0), global_batch)      # (one rank: checks the argument, writes nothing)
             if not self.has_graph(real.shape):
                 self.capture(real)
             return self.replay(real)
@@ -1505,8 +1471,6 @@ class _Ranks:
 def _slice_draws(draws, epoch, k, n_global, lo, hi, device):
     """this rank's rows of the global draw tensors of batch k (`draws(epoch, k, n_global)`); a list (the WGAN path's per-critic-step
     latents) is sliced element by element"""
-    if draws is None:
-        return {}
     cut = lambda v: v[lo:hi].to(device)   # noqa: E731
     return {name: ([cut(x) for x in v] if isinstance(v, (list, tuple)) else cut(v)) for name, v in draws(epoch, k, n_global).items()}
 
@@ -1522,6 +1486,69 @@ def _fill_static(static, fresh):
 
 def _clone_draws(fresh):
     return {name: ([x.clone() for x in v] if isinstance(v, (list, tuple)) else v.clone()) for name, v in fresh.items()}
+
+
+def _epoch_batches(ranks, dataset, cfg, epoch, device):
+    """(k, n_global, lo, hi, images) of every batch of `epoch`: the permutation all ranks draw alike (DataLoader(shuffle=True),
+    train.py:153), global batch k of n_global samples, and this rank's share [lo, hi) of it as images on `device`"""
+    order = ranks.order(len(dataset), getattr(cfg, "seed", 0), epoch)
+    for k, (n_global, mine) in enumerate(epoch_batches(order, cfg.batch_size, ranks.world, ranks.rank)):
+        lo, hi = ranks.share(n_global)
+        if hasattr(dataset, "batch"):                                  # device dataset: one augmentation launch per batch (data.py)
+            images = dataset.batch(mine)
+        else:
+            images = torch.stack([dataset[j] for j in mine]).to(device)
+        yield k, n_global, lo, hi, images
+
+
+def _run_batch(trainer, images, n_global, ranks, use_graph, draws_for_batch, statics):
+    """One update on this rank's `images` of a global batch of n_global -> (stats, the draws it used).  Without injected draws
+    (draws_for_batch None) that is trainer.step and nothing else of the trainer is touched; with them, a replay of the graphs cached
+    for the shape -- captured on first sight over clones of the draws, kept in `statics` and refilled before every replay -- or,
+    without use_graph, an eager iteration."""
+    shared = {"global_batch": n_global} if ranks.world > 1 else {}
+    if draws_for_batch is None:
+        return trainer.step(images, use_graph=use_graph, **shared), {}     # graphs are cached per shape until the next growth event
+    own = draws_for_batch
+    if not use_graph:
+        return trainer.train_iteration(images, **own, **shared), own
+    key = trainer._graph_key(images.shape, **shared)
+    if not trainer.has_graph(images.shape, **shared):
+        statics[key] = _clone_draws(own)
+        trainer.capture(images, draws=statics[key], **shared)
+    _fill_static(statics[key], own)
+    return trainer.replay(images, **shared), own
+
+
+def _monitored_g_loss(stats, own, trainer, ranks, images, n_global, sim_lambda):
+    """G_loss as the reference monitors it: with sim_lambda > 0 it adds similarity_loss(real images, latents) to the generator loss
+    (train.py:379-381, 493-496); that depends on neither network, so it changes the monitored value only.  It couples all pairs of the
+    GLOBAL batch: the ranks gather images and latents (DESIGN.md section 6 has the bytes) and every rank adds its share of the one
+    global value."""
+    if not sim_lambda > 0:
+        return stats["G_loss"]
+    from .utils import similarity_loss
+    z_g = own["z_g"] if "z_g" in own else trainer.last_z_g
+    return stats["G_loss"] + similarity_loss(ranks.gather_rows(images, n_global), ranks.gather_rows(z_g, n_global), sim_lambda)
+
+
+def _save_checkpoint(ranks, trainer, checkpoint, epoch, plot, before_save=None):
+    """Replicas are identical, so rank 0's state is everyone's: it alone runs before_save(), writes the checkpoint and plots the
+    sample grids -- plot(averaged): False for the live generator, then, with an averaged generator, True for the same latents
+    through it -- while the others note the epoch; all leave together."""
+    checkpoint.lr = trainer.opt_g.param_groups[0]["lr"]
+    if ranks.rank == 0:
+        if before_save is not None:
+            before_save()
+        checkpoint.save_state(epoch)
+        if plot is not None:
+            plot(False)
+            if getattr(trainer, "ema_enabled", False):
+                with trainer.averaged_generator():
+                    plot(True)
+    else:
+        checkpoint.epoch = epoch
+    ranks.barrier()
 
 
 def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final=None, use_graph=True, log=print,
@@ -1544,7 +1571,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
     (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
     import time
-    from .utils import Calculate_D_steps, similarity_loss
+    from .utils import Calculate_D_steps, plot_gen_samples
     adapt_period = 100                                                # Disc_adapt_update_period, train.py:190
     sim_lambda = float(getattr(cfg, 'sim_loss_lambda', 0.0))          # train.py:300
     sim_decay = float(getattr(cfg, 'sim_loss_lambda_decay_rate', 0.0))
@@ -1563,6 +1590,11 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     statics = {}                      # graph key -> the static draw tensors its graphs read
     pending = [None, None]
     series = {n: [] for n in names}
+    plot = None
+    if samples_dir is not None:
+        def plot(averaged):
+            name = "Samples_{}{}_{:d}.png".format("ema_" if averaged else "", cfg.ID, epoch)
+            plot_gen_samples(G, N_images=16, seed=0, filename=os.path.join(samples_dir, name))
     dataset.set_image_size(G.image_size)
     start_time = time.time()
 
@@ -1605,39 +1637,13 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
         if sim_decay > 0 and sim_lambda > 0:                          # train.py:343-348
             sim_lambda = cfg.sim_loss_lambda * (1 - sim_decay) ** (epoch - 1) if sim_lambda > 1e-5 else 0.0
         acc = torch.zeros(len(names), device=dev)
-        order = ranks.order(n_images, getattr(cfg, "seed", 0), epoch)   # DataLoader(shuffle=True), train.py:153
-        for k, i in enumerate(range(0, n_images, cfg.batch_size)):
-            batch = order[i:i + cfg.batch_size]                      # the global batch; this rank trains batch[lo:hi]
-            lo, hi = ranks.share(len(batch))
-            if hasattr(dataset, "batch"):                          # device dataset: one augmentation launch per batch (data.py)
-                images = dataset.batch(batch[lo:hi])
-            else:
-                images = torch.stack([dataset[j] for j in batch[lo:hi]]).to(dev)
-            b = images.size(0)
+        for k, n, lo, hi, images in _epoch_batches(ranks, dataset, cfg, epoch, dev):
             trainer.n_critic = n_d_steps
-            shared = {"global_batch": len(batch)} if ranks.world > 1 else {}
-            if draws is None:
-                stats = trainer.step(images, use_graph=use_graph, **shared)   # graphs are cached per shape until the next growth event
-            else:
-                own = _slice_draws(draws, epoch, k, len(batch), lo, hi, dev)
-                if use_graph and n_d_steps == 1:
-                    if not trainer.has_graph(images.shape, **shared):
-                        key = trainer._graph_key(images.shape, **shared)
-                        statics[key] = _clone_draws(own)
-                        trainer.capture(images, draws=statics[key], **shared)
-                    _fill_static(statics[trainer._graph_key(images.shape, **shared)], own)
-                    stats = trainer.replay(images, **shared)
-                else:
-                    stats = trainer.train_iteration(images, **own, **shared)
-            g_loss = stats["G_loss"]
-            if sim_lambda > 0:
-                # the reference adds similarity_loss(real images, latents) to the generator loss (train.py:379-381); it depends on
-                # neither network, so it changes the monitored value only.  It couples all pairs of the GLOBAL batch: the ranks gather
-                # images and latents (DESIGN.md section 6 has the bytes) and every rank adds its share of the one global value
-                z_g = own["z_g"] if draws is not None and "z_g" in own else trainer.last_z_g
-                g_loss = g_loss + similarity_loss(ranks.gather_rows(images, len(batch)), ranks.gather_rows(z_g, len(batch)), sim_lambda)
-            acc += b * torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss,
-                                    stats["D_grad_pen"].float()])
+            own = None if draws is None else _slice_draws(draws, epoch, k, n, lo, hi, dev)
+            stats, own = _run_batch(trainer, images, n, ranks, use_graph and (draws is None or n_d_steps == 1), own, statics)
+            g_loss = _monitored_g_loss(stats, own, trainer, ranks, images, n, sim_lambda)
+            acc += images.size(0) * torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss,
+                                                 stats["D_grad_pen"].float()])
         slot = epoch & 1
         consume(slot)
         ranks.sum_(acc)                                                # N ranks: ONE all-reduce per epoch, of the five sums
@@ -1653,20 +1659,9 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
             trainer.opt_g.set_lr(lr)
         if checkpoint is not None and epoch % cfg.checkpointing_period == 0:
             consume(slot)
-            checkpoint.lr = trainer.opt_g.param_groups[0]["lr"]
-            if ranks.rank == 0:                                        # replicas are identical: rank 0's state is everyone's
-                score_due(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log)   # the metrics whose period divides it
-                checkpoint.save_state(epoch)
-                if samples_dir is not None:
-                    from .utils import plot_gen_samples
-                    plot_gen_samples(G, N_images=16, seed=0, filename=os.path.join(samples_dir, "Samples_{}_{:d}.png".format(cfg.ID, epoch)))
-                    if getattr(trainer, "ema_enabled", False):       # the same latents through the averaged generator
-                        with trainer.averaged_generator():
-                            plot_gen_samples(G, N_images=16, seed=0,
-                                             filename=os.path.join(samples_dir, "Samples_ema_{}_{:d}.png".format(cfg.ID, epoch)))
-            else:
-                checkpoint.epoch = epoch
-            ranks.barrier()
+            # before it is written, rank 0 scores the metrics whose period divides the epoch
+            _save_checkpoint(ranks, trainer, checkpoint, epoch, plot,
+                             before_save=lambda: score_due(trainer, dataset, cfg, epoch, checkpoint=checkpoint, log=log))
     consume(0)
     consume(1)
     return series
@@ -1698,7 +1693,7 @@ def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final
     monitored value is the share-weighted mean over the ranks, the per-epoch sums of these are all-reduced once per epoch, rank 0
     alone logs, saves and plots.  Eager whatever use_graph says (a synchronised BatchNorm is a collective; logged once).
     draws(epoch, k, n_global) -> {"z_d", "z_g"}: optional global latents of batch k (z_d one tensor or one per critic step)."""
-    from .utils import plot_gen_samples, similarity_loss
+    from .utils import plot_gen_samples
     G = trainer.G
     device = trainer.device
     if epoch_final is None:
@@ -1717,6 +1712,11 @@ def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final
     names = ("score_real", "score_fake", "D_loss", "G_loss")
     history = []
     statics = {}
+    plot = None
+    if samples_dir is not None:
+        def plot(averaged):
+            name = '{}_{}_{}.png'.format('Samples_ema' if averaged else 'Test_images', cfg.ID, epoch)
+            plot_gen_samples(G, eval_noise=eval_noise, filename=os.path.join(samples_dir, name))
     if checkpoint is not None and epoch_init > 1:       # a resumed run continues the series it saved
         past = [dict(zip(names, v)) for v in zip(checkpoint.Loss_real[:epoch_init - 1], checkpoint.Loss_fake[:epoch_init - 1],
                                                  checkpoint.Loss_D[:epoch_init - 1], checkpoint.Loss_G[:epoch_init - 1])]
@@ -1728,38 +1728,15 @@ def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final
                 seen = past + history
                 trainer.n_critic = wgan_critic_steps([h["score_real"] for h in seen], [h["score_fake"] for h in seen], n_critic_max)
             acc = torch.zeros(len(names), device=device)
-            order = ranks.order(n_images, getattr(cfg, "seed", 0), epoch)   # DataLoader(shuffle=True), train.py:153
-            for k, i in enumerate(range(0, n_images, cfg.batch_size)):
-                batch = order[i:i + cfg.batch_size]                # the global batch; this rank trains batch[lo:hi]
-                lo, hi = ranks.share(len(batch))
-                if hasattr(dataset, "batch"):                      # device dataset: one augmentation launch per batch (data.py)
-                    images = dataset.batch(batch[lo:hi])
-                else:
-                    images = torch.stack([dataset[j] for j in batch[lo:hi]]).to(device)
+            for k, n, lo, hi, images in _epoch_batches(ranks, dataset, cfg, epoch, device):
                 images = images.float()
-                shared = {"global_batch": len(batch)} if ranks.world > 1 else {}
-                graph = use_graph and trainer.n_critic == n_critic_max
-                if draws is None:
-                    stats = trainer.step(images, use_graph=graph, **shared)
-                else:
-                    own = _slice_draws(draws, epoch, k, len(batch), lo, hi, device)
-                    if graph:                                      # (one rank only: see above)
-                        key = tuple(images.shape)
-                        if not trainer.has_graph(key):
-                            statics[key] = _clone_draws(own)
-                            trainer.capture(images, draws=statics[key])
-                        _fill_static(statics[key], own)
-                        stats = trainer.replay(images)
-                    else:
-                        stats = trainer.train_iteration(images, **own, **shared)
-                g_loss = stats["G_loss"]
-                if sim_lambda > 0:
-                    z_g = own["z_g"] if draws is not None and "z_g" in own else trainer.last_z_g
-                    g_loss = g_loss + similarity_loss(ranks.gather_rows(images, len(batch)), ranks.gather_rows(z_g, len(batch)), sim_lambda)
+                own = None if draws is None else _slice_draws(draws, epoch, k, n, lo, hi, device)
+                stats, own = _run_batch(trainer, images, n, ranks, use_graph and trainer.n_critic == n_critic_max, own, statics)
+                g_loss = _monitored_g_loss(stats, own, trainer, ranks, images, n, sim_lambda)
                 row = torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss])
                 # sums of the per-batch means (train.py:503-506), one read per epoch; N ranks: a batch's value is the share-weighted
                 # mean over the ranks
-                acc += row if ranks.world == 1 else row * (images.size(0) / len(batch))
+                acc += row if ranks.world == 1 else row * (images.size(0) / n)
             vals = ranks.sum_(acc).tolist()
             if any(math.isnan(v) for v in vals):
                 raise ValueError('loss is nan at epoch {}'.format(epoch))
@@ -1772,19 +1749,7 @@ def wgan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_final
             log('Epoch {}: score_real {:.5f} score_fake {:.5f} D_loss {:.5f} G_loss {:.5f} (n_critic {})'.format(
                 epoch, sums["score_real"], sums["score_fake"], sums["D_loss"], sums["G_loss"], trainer.n_critic))
             if checkpoint is not None and epoch % cfg.checkpointing_period == 0:
-                checkpoint.lr = trainer.opt_g.param_groups[0]["lr"]
-                if ranks.rank == 0:
-                    checkpoint.save_state(epoch)
-                    if samples_dir is not None:
-                        plot_gen_samples(G, eval_noise=eval_noise,
-                                         filename=os.path.join(samples_dir, 'Test_images_{}_{}.png'.format(cfg.ID, epoch)))
-                        if getattr(trainer, "ema_enabled", False):   # the same latents through the averaged generator
-                            with trainer.averaged_generator():
-                                plot_gen_samples(G, eval_noise=eval_noise,
-                                                 filename=os.path.join(samples_dir, 'Samples_ema_{}_{}.png'.format(cfg.ID, epoch)))
-                else:
-                    checkpoint.epoch = epoch
-                ranks.barrier()
+                _save_checkpoint(ranks, trainer, checkpoint, epoch, plot)
     finally:
         trainer.n_critic = n_critic_max
     return history
@@ -1866,6 +1831,10 @@ def dataset_source(argv, options, config):
     return "synthetic"
 
 
+_WGAN_AND_PGGAN = ("wgan=True together with pggan=True is not a configuration the reference can train (it fails at "
+                   "Generator_net.image_size); choose one")
+
+
 def make_trainer(config, G, D, process_group=None, distributed=False):
     """The trainer `main()` trains with: RMSprop when config.RMSprop is set, else Adam with betas (beta1, 0.999) (train.py:220-225).
     wgan without pggan: a WGANTrainer (weight clipping at 0.01, reference train.py:489-490); wgan with pggan is refused.
@@ -1873,8 +1842,7 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     distributed: a launched rank -- the trainer exchanges over `process_group` (None: the default group); the WGAN nets then train
     with synchronised BatchNorm."""
     if config.wgan and config.pggan:
-        raise ValueError("wgan=True together with pggan=True is not a configuration the reference can train (it fails at "
-                         "Generator_net.image_size); choose one")
+        raise ValueError(_WGAN_AND_PGGAN)
     aug = dict(diffaug=getattr(config, 'diffaug', ''), diffaug_p=getattr(config, 'diffaug_p', 1.0),
                diffaug_seed=getattr(config, 'diffaug_seed', 0))
     lsgan = bool(getattr(config, 'lsgan', False))
@@ -1928,7 +1896,6 @@ def _train_main(argv, options, local_rank, group):
     device latents are seeded config.seed + rank."""
     from .configs import config
     from . import models
-    from .utils import Checkpointer
     rank = dist.get_rank(group) if group is not None else 0
     overrides = cli_overrides(argv, options, config.configs_name)
     if options.configs:
@@ -1937,8 +1904,7 @@ def _train_main(argv, options, local_rank, group):
         config.set_configs(**overrides)
         config.validate_configs(create_dirs=True)
     if config.wgan and config.pggan:
-        raise ValueError("wgan=True together with pggan=True is not a configuration the reference can train (it fails at "
-                         "Generator_net.image_size); choose one")
+        raise ValueError(_WGAN_AND_PGGAN)
     if not config.pggan and not config.wgan:
         raise NotImplementedError("the DCGAN path is disabled in the reference itself (train.py:629); choose pggan or wgan")
     if config.device != 'cuda':
@@ -1973,49 +1939,34 @@ def _train_main(argv, options, local_rank, group):
     else:
         dataset = TensorImageDataset.synthetic(16, config.image_size, config.N_colors, device=device)
     if config.wgan:
-        return _wgan_main(config, dataset, device, Checkpointer, group)
+        return _wgan_main(config, dataset, device, group, rank)
     size_init = dataset.image_size_max // (2 ** n_up)                                       # train.py:162-165
     G = models.Generator_PG(config.N_gen_features, image_size_init=size_init).to(device)    # train.py:172-175
     D = models.Discriminator_PG(config.N_dis_features, image_size_init=size_init).to(device)
-    filename = os.path.join(config.weights_dir, 'GenDisc_{}.pth'.format(config.ID))         # train.py:196-197
-    # the trainer exists before the checkpoint is read, so that `--resume` also restores the optimiser state this implementation
-    # adds to its checkpoints (Adam moments or RMSprop square averages, per-tensor step counts; the reference saves none,
-    # utils.py:160-169)
-    if rank > 0:
-        torch.manual_seed(config.seed + rank)  # latents (host and device generators): each rank draws its own
-    trainer = make_trainer(config, G, D, process_group=group, distributed=group is not None)
-    checkpoint = Checkpointer(G, D, config.learning_rate, filename, N_epochs=config.N_epochs, device=device, extra_checkpoint_period=1e3,
-                              trainer=trainer, verbose=rank == 0)
-    if config.resume and os.path.exists(filename):
-        checkpoint.load_state()
-    elif config.weights_init:
-        checkpoint.load_state(os.path.join(config.weights_dir, config.weights_init))
+    trainer, checkpoint, epoch_init, epoch_final = _trainer_and_checkpoint(config, G, D, device, group, rank)
     assert G.image_size == D.image_size, 'The generator and discriminator are at different resolution'   # train.py:215-216
-    epoch_init = checkpoint.epoch + 1
     lr0 = lr_schedule(epoch_init - 1, config.learning_rate, config.transit_sch, config.N_epochs)       # train.py:288-289
     if lr0 is not None:
-        trainer.opt_d.set_lr(lr0)
-        trainer.opt_g.set_lr(lr0)
-    epoch_final = epoch_init + config.N_epochs_session if config.N_epochs_session else config.N_epochs + 1
+        trainer.set_lr(lr0)
     return pggan_train(trainer, dataset, config, checkpoint=checkpoint, epoch_init=epoch_init, epoch_final=epoch_final,
                        samples_dir=config.samples_sub_dir, process_group=group)
 
 
-def _wgan_main(config, dataset, device, Checkpointer, group=None):
-    """main() for wgan=True, pggan=False (train.py:172-180, 204-210, 269, 454-536)"""
-    from . import models
-    from .utils import init_weights
-    G = models.Generator_wgan(config.N_gen_features, latent_dim=config.latent_dim, image_size=config.image_size,
-                              N_colors=config.N_colors).to(device)
-    D = models.Discriminator_wgan(config.N_dis_features, image_size=config.image_size, N_colors=config.N_colors).to(device)
+def _trainer_and_checkpoint(config, G, D, device, group, rank, init=None):
+    """-> (trainer, checkpoint, first epoch, end of the epoch range) of a run of main(): the checkpoint GenDisc_<ID>.pth
+    (train.py:196-197) is read when `--resume` finds it, else `weights_init` when given, else the nets stay as built -- after
+    G.apply(init) / D.apply(init) when the caller has an `init`."""
+    from .utils import Checkpointer
     filename = os.path.join(config.weights_dir, 'GenDisc_{}.pth'.format(config.ID))
     resume = config.resume and os.path.exists(filename)
-    if not resume and not config.weights_init:
-        G.apply(init_weights)
-        D.apply(init_weights)
-    rank = dist.get_rank(group) if group is not None else 0
+    if init is not None and not resume and not config.weights_init:
+        G.apply(init)
+        D.apply(init)
     if rank > 0:
-        torch.manual_seed(config.seed + rank)  # latents: each rank draws its own (the nets above are the same on every rank)
+        torch.manual_seed(config.seed + rank)  # latents (host and device generators): each rank draws its own; the nets are the same
+    # the trainer exists before the checkpoint is read, so that `--resume` also restores the optimiser state this implementation
+    # adds to its checkpoints (Adam moments or RMSprop square averages, per-tensor step counts; the reference saves none,
+    # utils.py:160-169)
     trainer = make_trainer(config, G, D, process_group=group, distributed=group is not None)
     checkpoint = Checkpointer(G, D, config.learning_rate, filename, N_epochs=config.N_epochs, device=device, extra_checkpoint_period=1e3,
                               trainer=trainer, verbose=rank == 0)
@@ -2023,9 +1974,20 @@ def _wgan_main(config, dataset, device, Checkpointer, group=None):
         checkpoint.load_state()
     elif config.weights_init:
         checkpoint.load_state(os.path.join(config.weights_dir, config.weights_init))
-    eval_noise = sample_latent_vec((16, G.latent_dim), device=device)
     epoch_init = checkpoint.epoch + 1
     epoch_final = epoch_init + config.N_epochs_session if config.N_epochs_session else config.N_epochs + 1
+    return trainer, checkpoint, epoch_init, epoch_final
+
+
+def _wgan_main(config, dataset, device, group, rank):
+    """main() for wgan=True, pggan=False (train.py:172-180, 204-210, 269, 454-536)"""
+    from . import models
+    from .utils import init_weights
+    G = models.Generator_wgan(config.N_gen_features, latent_dim=config.latent_dim, image_size=config.image_size,
+                              N_colors=config.N_colors).to(device)
+    D = models.Discriminator_wgan(config.N_dis_features, image_size=config.image_size, N_colors=config.N_colors).to(device)
+    trainer, checkpoint, epoch_init, epoch_final = _trainer_and_checkpoint(config, G, D, device, group, rank, init=init_weights)
+    eval_noise = sample_latent_vec((16, G.latent_dim), device=device)
     return wgan_train(trainer, dataset, config, checkpoint=checkpoint, epoch_init=epoch_init, epoch_final=epoch_final,
                       samples_dir=config.samples_sub_dir, eval_noise=eval_noise, process_group=group)
 

@@ -277,6 +277,34 @@ def test_graph_replay_equals_eager(kind):
     assert all(torch.equal(x, y) for x, y in zip(b1, b2))
 
 
+@pytest.mark.parametrize("kind", ["adam", "rmsprop"])
+def test_capture_trains_nothing(kind):
+    """capture() warms up on a snapshot: parameters, optimiser state, step counts, the BatchNorm running buffers (num_batches_tracked
+    among them) and the device RNG state are afterwards what they were, bit for bit; the first replay() is the first update."""
+    cfg = dict(gw=[32, 16, 8], dw=[8, 16, 32], latent=16, size=64, b=5)
+    G, D = make_nets(cfg["gw"], cfg["dw"], cfg["latent"], cfg["size"])
+    G.to(DEV)
+    D.to(DEV)
+    tr = train.WGANTrainer(G, D, learning_rate=1e-3, optimizer=kind, n_critic=2, device_latents=True)
+    real = (torch.rand(cfg["b"], 1, cfg["size"], cfg["size"], generator=torch.Generator().manual_seed(3)) * 2 - 1).to(DEV)
+    state = tr._training_state()
+    assert all(any(b is t for t in state) for b in tr._bn_buffers()) and len(tr._bn_buffers()) > 0
+    before = [t.clone() for t in state]
+    rng = torch.cuda.get_rng_state()
+    tr.capture(real, warmup=2)
+    torch.cuda.synchronize()
+    for i, (a, t) in enumerate(zip(before, tr._training_state())):
+        assert torch.equal(a, t), f"capture() changed tensor {i} of _training_state()"
+    assert torch.equal(rng, torch.cuda.get_rng_state()), "capture() advanced the device RNG"
+    means = [b for net in (G, D) for n, b in net.named_buffers() if n.endswith("running_mean")]
+    means_before = [m.clone() for m in means]
+    g0, d0 = tr.flat_g.flat.clone(), tr.flat_d.flat.clone()
+    tr.replay(real)
+    torch.cuda.synchronize()
+    assert not torch.equal(g0, tr.flat_g.flat) and not torch.equal(d0, tr.flat_d.flat)
+    assert any(not torch.equal(a, m) for a, m in zip(means_before, means))
+
+
 def test_checkpoint_resume_equals_uninterrupted(tmp_path):
     cfg = dict(gw=[16, 8], dw=[8, 16], latent=16, size=32, b=4)
     gen = torch.Generator().manual_seed(5)
