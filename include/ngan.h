@@ -238,6 +238,8 @@ int ngan_wloss_head_bwd(const float* scores, int n_real, int n_fake, float drift
 /* ---- scalar heads of the objectives beside the Wasserstein one (least squares): declared in ngan_objectives.h, which this header
  * includes -- the table of this file, 165 entry points, is pinned by the suite as it stands; objectives are an extension section ---- */
 #include "ngan_objectives.h"
+/* ---- minibatch standard deviation of the PG critic's head (opt-in): declared in ngan_mbstd.h, an extension section likewise ---- */
+#include "ngan_mbstd.h"
 
 /* ---- latent projection: utils.py:77-78 (clamp(-c, c), L2-normalise each row), in place on (rows, dim) normal draws ---------- */
 int ngan_latent_normalize(float* z, int rows, int dim, float clamp, void* stream);

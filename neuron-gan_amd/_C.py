@@ -148,6 +148,20 @@ OBJECTIVE_SIGNATURES = {
     "ngan_lsloss_head_bwd": [_P, _I, _I, _F, _F, _P, _P, _P, _P, _P],
 }
 
+# include/ngan_mbstd.h, the second extension section: the critic head's minibatch standard deviation (ops.MinibatchStd, ops.StdField*);
+# listed by `mbstd_symbols`, like the objectives' table
+MBSTD_SIGNATURES = {
+    "ngan_mbstd_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ngan_mbstd_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ngan_mbstd_bwdbwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ngan_stdfield_add": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "ngan_stdfield_ds": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "ngan_stdfield_dw": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
+}
+MBSTD_NON_STATUS = {
+    "ngan_mbstd_workspace_doubles": ([_I, _I, _I, _I, _I], _L),
+}
+
 NON_STATUS = {
     "ngan_version": ([], ctypes.c_char_p),
     "ngan_last_error": ([], ctypes.c_char_p),
@@ -193,11 +207,11 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                f"or `make -C neuron-gan_amd/csrc`; there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()):
+        for name, argtypes in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(MBSTD_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
-        for name, (argtypes, restype) in NON_STATUS.items():
+        for name, (argtypes, restype) in list(NON_STATUS.items()) + list(MBSTD_NON_STATUS.items()):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -211,6 +225,14 @@ def exported_symbols():
 
 def objective_symbols():
     return list(OBJECTIVE_SIGNATURES)
+
+
+def mbstd_symbols():
+    return list(MBSTD_SIGNATURES) + list(MBSTD_NON_STATUS)
+
+
+def mbstd_workspace_doubles(B, H, W, C, G_eff) -> int:
+    return int(lib().ngan_mbstd_workspace_doubles(B, H, W, C, G_eff))
 
 
 def version() -> str:

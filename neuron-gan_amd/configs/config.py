@@ -33,7 +33,7 @@ _DEFAULTS = dict(
     seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
     # the checkpoint metrics: <prefix>_period, _images (or _pairs), _seed and the metric's own options, row by row
     **{name: default for m in METRICS for name, _, default, _ in settings(m)},
-    diffaug='', diffaug_p=1.0, diffaug_seed=0, lsgan=False,
+    diffaug='', diffaug_p=1.0, diffaug_seed=0, lsgan=False, mbstd_group=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -117,6 +117,11 @@ def validate_configs(create_dirs=False):
         raise ValueError(f"lsgan={g['lsgan']!r} must be True or False")
     if g['lsgan'] and g['wgan']:
         raise ValueError("lsgan=True is not available for the WGAN nets (wgan=True)")
+    # the PG critic's minibatch standard-deviation channel (an addition of this implementation; Karras et al. 2018, section 3, use 4)
+    if isinstance(g['mbstd_group'], bool) or not (isinstance(g['mbstd_group'], int) and g['mbstd_group'] >= 0):
+        raise ValueError(f"mbstd_group={g['mbstd_group']!r} must be an integer >= 0 (0: off)")
+    if g['mbstd_group'] and g['wgan']:
+        raise ValueError("mbstd_group > 0 is not available for the WGAN nets (wgan=True)")
     if g['pggan']:
         err_msg = 'The number of layers in the generator and discriminator must match.'
         assert len(g['N_gen_features']) == len(g['N_dis_features']), err_msg

@@ -76,8 +76,9 @@ class D_W_loss(nn.Module):
             with torch.no_grad():
                 fake_images = self.generator_net(z)
         # D(real) and D(fake) share the weights and no op couples samples, so they run as ONE critic pass over the
-        # concatenated batch (the reference makes two calls, loss_functions.py:21, 29; per-sample results are identical)
-        with ops.first_order_only():      # differentiated once (train.py:365): fused PixelNorm-backward epilogues apply
+        # concatenated batch (the reference makes two calls, loss_functions.py:21, 29; per-sample results are identical).  The one op
+        # that does couple samples, the opt-in minibatch standard deviation, is told that the batch holds two calls (mbstd_segments)
+        with ops.first_order_only(), ops.mbstd_segments(2):      # differentiated once (train.py:365): fused PixelNorm-backward epilogues apply
             both = torch.cat([real_images, fake_images], dim=0) if augment is None else augment.critic_batch(real_images, fake_images)
             scores = self.discriminator_net(both)
         # -mean(real) + mean(fake) + drift * mean(real^2) (loss_functions.py:22, 29, 33, 45) as one launch each way
@@ -125,7 +126,7 @@ def D_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, 
         z = _latents(generator_net, batch_size, device, z)
         with torch.no_grad():
             fake_images = generator_net(z)
-    with ops.first_order_only():
+    with ops.first_order_only(), ops.mbstd_segments(2):
         both = torch.cat([real_images_batch, fake_images], dim=0) if augment is None else augment.critic_batch(real_images_batch, fake_images)
         scores = discriminator_net(both)
     D_loss, Score_real_avg, Score_fake_avg = ops.LSLossHead.apply(scores, batch_size, LS_TARGET_REAL, LS_TARGET_FAKE)

@@ -10,7 +10,7 @@ must live on the GPU and the extension must be built.
 
 Reference behaviours kept on purpose: LeakyReLU comes BEFORE PixelNorm; the equalised-LR
 constant multiplies the input, so the bias is unscaled; ToImage has no weight_scale and applies tanh; fade-in
-mixes post-tanh images; the critic uses PixelNorm too and has no minibatch-stddev layer.
+mixes post-tanh images; the critic uses PixelNorm too and has no minibatch-stddev layer (an opt-in addition here: `mbstd_group`).
 """
 import math
 
@@ -248,7 +248,8 @@ def _resample_of(m):
 def _plan(mods, steps=None, pending=None):
     """Flatten an nn.Sequential of PG building blocks (nested Conv2d_scale_blocks included) into execution steps, merging
     [resample] conv LeakyReLU PixelNorm  groups:  ('stem', linear, size, slope) | ('conv_lrelu_pn', conv, resample, slope) |
-    ('conv', conv, resample) | ('lrelu_pn', slope) | ('resample', code) | ('flatten',)"""
+    ('conv', conv, resample) | ('lrelu_pn', slope) | ('resample', code) | ('flatten',) | ('mbstd_head', conv, resample, slope): the
+    critic's head conv when it carries a `weight_std` (Discriminator_PG(mbstd_group > 0)), run unfused by `_mbstd_head`"""
     top = steps is None
     if top:
         steps, pending = [], [ops.RES_NONE]
@@ -283,7 +284,8 @@ def _plan(mods, steps=None, pending=None):
             steps.append(('stem', m, s, nxt2.negative_slope))
             i += 4
         elif isinstance(m, Conv2d_normalized) and m.is_3x3() and isinstance(nxt, nn.LeakyReLU) and isinstance(nxt2, PixelNorm):
-            steps.append(('conv_lrelu_pn', m, pending[0], nxt.negative_slope))
+            kind = 'mbstd_head' if getattr(m, 'weight_std', None) is not None else 'conv_lrelu_pn'
+            steps.append((kind, m, pending[0], nxt.negative_slope))
             pending[0] = ops.RES_NONE
             i += 3
         elif isinstance(m, Conv2d_normalized):
@@ -342,6 +344,25 @@ def _conv_any_width(x, m, res, slope):
     return y
 
 
+def _mbstd_head(x, m, res, slope):
+    """The critic's head conv with the minibatch standard deviation as one extra input channel (Karras et al. 2018, section 3; DESIGN.md
+    section 7): MinibatchStd -> Conv -> StdFieldAdd -> LeakyReLU -> PixelNorm.  x has two consumers here, so no PixelNorm hand-off
+    reaches across it; the (C + 1)-channel tensor is never formed -- a constant plane through a zero-padded 3x3 conv is s times a
+    border-aware tap sum, which ops.StdFieldAdd adds to the C -> C conv's output.  The lost fusion and hand-off, with the new launches,
+    cost 0.27 ms of a 6.9 ms iteration at 512 x 512, batch 16 (profiles/mbstd_time.txt)."""
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f'mbstd_group > 0 is built for fp32 activation storage, not for the bf16 storage mode (got {x.dtype})')
+    x = _apply_resample(x, res)
+    s = ops.MinibatchStd.apply(x, ops.mbstd_segment_count(), m.mbstd_group)
+    if _odd_width(m):
+        c = _conv_any_width(x, m, ops.RES_NONE, None)
+    else:
+        c = ops.Conv.apply(x, m.weight, m.bias, ops.RES_NONE, m.scale_value)
+    c = ops.StdFieldAdd.apply(c, s, m.weight_std, m.scale_value)
+    y, _ = ops.LReLUPN.apply(c, None, slope)
+    return y
+
+
 def _exec(steps, x, link=None, to_image=None, then=None):
     """Run planned steps on a channels-last tensor (or on latents for the stem).  `link`: PNLink of the LeakyReLU->PixelNorm that
     produced x, if x has no other consumer.  Returns (output, link of the output).  Inside `ops.first_order_only()` consecutive
@@ -356,6 +377,8 @@ def _exec(steps, x, link=None, to_image=None, then=None):
             x, link = _conv_any_width(x, st[1], st[2], st[3]), None
         elif kind == 'conv' and st[1].is_3x3() and _odd_width(st[1]):
             x, link = _conv_any_width(x, st[1], st[2], None), None
+        elif kind == 'mbstd_head':
+            x, link = _mbstd_head(x, st[1], st[2], st[3]), None
         elif kind == 'conv_lrelu_pn':
             _, m, res, slope = st
             if (idx == last and to_image is not None and ops.first_order_enabled()
@@ -363,9 +386,10 @@ def _exec(steps, x, link=None, to_image=None, then=None):
                 t = ops.ConvLReLUPNToImage.apply(x, m.weight, m.bias, to_image.layers[0].weight, res, m.scale_value, slope, link,
                                                  torch.is_grad_enabled())
                 return t, None
-            out_link = ops.PNLink() if linking else None
             # the next step is an avg-pooled conv: ask this conv's kernel for the pooled copy of its output (ops._run_conv)
             nxt = steps[idx + 1] if idx < last else then
+            # (the mbstd head reads this output twice: tensors with two consumers are never linked)
+            out_link = ops.PNLink() if linking and not (nxt is not None and nxt[0] == 'mbstd_head') else None
             pool_out = (nxt is not None and nxt[0] in ('conv_lrelu_pn', 'conv') and len(nxt) > 2 and nxt[2] == ops.RES_POOL2
                         and not _odd_width(nxt[1]))
             if pool_out:
@@ -592,9 +616,15 @@ class Generator_PG(_ProgressiveNet):
 
 class Discriminator_PG(_ProgressiveNet):
     def __init__(self, N_features_per_layer: list, image_size_init=4, LeakyReLU_neg_slope=LeakyReLU_neg_slope_default,
-                 N_colors=N_colors_default):
+                 N_colors=N_colors_default, mbstd_group=0):
+        """mbstd_group: 0 -- the reference's critic, draw for draw -- or the group size G of a minibatch standard-deviation channel
+        in front of the head conv (Karras et al. 2018, section 3, whose value is 4).  The channel's weights are
+        a parameter of their own on the head conv, `weight_std` (C, 1, 3, 3), drawn after every other parameter."""
         N_scaling = len(N_features_per_layer) - 1
         super().__init__()
+        self.mbstd_group = int(mbstd_group)
+        if self.mbstd_group < 0:
+            raise ValueError(f'mbstd_group must be 0 (off) or a positive group size, got {mbstd_group}')
         self.N_features_per_layer = N_features_per_layer
         self.N_layers = 1
         self.N_layers_max = len(N_features_per_layer)
@@ -624,7 +654,16 @@ class Discriminator_PG(_ProgressiveNet):
             self.FromIm_list.append(FromImage(N_colors, N_features_per_layer[i]))
         self.FromIm = self.FromIm_list.pop(-1)
         self.downsample = Interpolate(scale_factor=0.5, mode='bilinear')
-        self.saved_attrs = self._saved_attr_names([])
+        if self.mbstd_group > 0:
+            # the head conv as Conv2d_normalized(fl + 1, fl, 3) would be: He-normal weights and an equalised-LR constant for a fan-in
+            # of (fl + 1) * 9; the extra channel's slice is drawn last, so every other parameter is the mbstd_group = 0 critic's
+            head = self.layers[0]
+            head.scale_value = float(_he_gain(act) / np.sqrt((fl + 1) * 9))
+            head.weight_scale.fill_(head.scale_value)
+            head.weight_std = nn.Parameter(torch.empty(fl, 1, 3, 3).normal_(0.0, head.scale_value))
+            head.mbstd_group = self.mbstd_group
+        # (listed only when on: the default critic's saved attributes stay the reference's)
+        self.saved_attrs = self._saved_attr_names(['mbstd_group'] if self.mbstd_group > 0 else [])
         self._tag_parameters()
 
     def forward(self, x):
@@ -669,6 +708,7 @@ class Discriminator_PG(_ProgressiveNet):
         saved = load_checkpoint_dict(filename, device)
         attrs = saved['Discriminator_attrs']
         ctor = {k: attrs[k] for k in ('N_features_per_layer', 'image_size_init', 'LeakyReLU_neg_slope', 'N_colors') if k in attrs}
+        ctor['mbstd_group'] = int(attrs.get('mbstd_group', 0))        # a file without the key holds the reference's critic
         obj = cls(**ctor)
         obj.set_resolution(attrs['image_size'], float(attrs['alpha']))
         state = saved['Discriminator_state']

@@ -14,6 +14,8 @@ Closure under differentiation (what the backward of each operator is built from)
     LReLUPNBwd    -> lrelu_pixelnorm_bwdbwd (the only operator with a non-zero Hessian)
     FromImage / FromImageDx / FromImageDw, FinalDot / FinalDotDx / FinalDotDw: bilinear triples, closed
     Lerp <-> FadeBwd, Up2 <-> Up2Adjoint, Pool2 <-> Pool2Adjoint: linear pairs
+    MinibatchStd  -> MinibatchStdBwd -> mbstd_bwdbwd (opt-in, fp32 storage; the second operator with a non-zero Hessian)
+    StdFieldAdd / StdFieldDs / StdFieldDw: bilinear triple, closed
 """
 import os
 import struct
@@ -1313,6 +1315,188 @@ class FinalDotDw(Function):
             e = hb.expand(go.shape)
             ggo = e if ggo is None else ggo + e
         return gy, ggo, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Minibatch standard deviation of the critic's head (Karras et al. 2018, section 3; include/ngan_mbstd.h).
+# Opt-in (models.Discriminator_PG(mbstd_group=G)); the only operators that couple the samples of a batch.  fp32 storage only.
+#     MinibatchStd <-> MinibatchStdBwd (whose backward is mbstd_bwdbwd: the layer sits on the gradient-penalty path)
+#     StdFieldAdd / StdFieldDs / StdFieldDw: the statistic as a constant input plane of the head conv, a bilinear triple, closed
+# The group size and the segment count are functions of shapes only: nothing here reads the device, so everything captures.
+# ---------------------------------------------------------------------------------------------------------
+def mbstd_group_size(batch, group):
+    """G_eff: the largest divisor of `batch` that does not exceed the requested group size (1 is legal: s = sqrt(eps), zero gradient)."""
+    batch, group = int(batch), int(group)
+    if batch < 1 or group < 1:
+        raise ValueError(f"mbstd_group_size: batch={batch} and group={group} must be positive")
+    g = min(batch, group)
+    while batch % g:
+        g -= 1
+    return g
+
+
+_mbstd_segments = 1
+
+
+class mbstd_segments:
+    """Inside, a critic batch holds `n` of the reference's critic calls of equal size, one after the other (the concatenated
+    [real | fake] pass of the critic losses: 2); the minibatch statistics never span two of them.  Outside it is 1."""
+
+    def __init__(self, n):
+        self.n = int(n)
+        if self.n < 1:
+            raise ValueError(f"mbstd_segments: n={n} must be positive")
+
+    def __enter__(self):
+        global _mbstd_segments
+        self.prev, _mbstd_segments = _mbstd_segments, self.n
+        return self
+
+    def __exit__(self, *exc):
+        global _mbstd_segments
+        _mbstd_segments = self.prev
+        return False
+
+
+def mbstd_segment_count():
+    return _mbstd_segments
+
+
+def _mbstd_f32(x, what):
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"{what}: the minibatch standard-deviation kernels are built for fp32 storage, not for the bf16 "
+                                  f"storage mode (got {x.dtype})")
+    return _c(x)
+
+
+def _mbstd_ws(x, g_eff):
+    b, h, w, c = x.shape
+    return torch.empty(max(1, _C.mbstd_workspace_doubles(b, h, w, c, g_eff)), device=x.device, dtype=torch.float64)
+
+
+class MinibatchStd(Function):
+    """s (B) = the minibatch standard deviation of each sample's group: x (B, H, W, C) holds `segments` critic calls, groups are
+    consecutive runs of G_eff = mbstd_group_size(B / segments, group) samples."""
+
+    @staticmethod
+    def forward(ctx, x, segments, group):
+        x = _mbstd_f32(x, "MinibatchStd")
+        b, h, w, c = x.shape
+        if b % segments:
+            raise RuntimeError(f"MinibatchStd: {segments} segments do not divide a batch of {b}")
+        g_eff = mbstd_group_size(b // segments, group)
+        s = torch.empty(b, device=x.device, dtype=torch.float32)
+        _C.call("ngan_mbstd_fwd", x, s, _mbstd_ws(x, g_eff), b, h, w, c, segments, g_eff)
+        ctx.save_for_backward(x)
+        ctx.cfg = (segments, g_eff)
+        return s
+
+    @staticmethod
+    def backward(ctx, gs):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        x, = ctx.saved_tensors
+        return MinibatchStdBwd.apply(gs, x, *ctx.cfg), None, None
+
+
+class MinibatchStdBwd(Function):
+    """gx = gs_g (x - mu) / (G J sigma): first-order backward of MinibatchStd, linear in gs."""
+
+    @staticmethod
+    def forward(ctx, gs, x, segments, g_eff):
+        gs = _c(gs)
+        b, h, w, c = x.shape
+        gx = torch.empty_like(x)
+        _C.call("ngan_mbstd_bwd", gs, x, gx, b, h, w, c, segments, g_eff)
+        ctx.save_for_backward(gs, x)
+        ctx.cfg = (segments, g_eff)
+        return gx
+
+    @staticmethod
+    def backward(ctx, hx):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("third-order derivative through the minibatch standard deviation is not on the WGAN-GP path")
+        gs, x = ctx.saved_tensors
+        segments, g_eff = ctx.cfg
+        hx = _mbstd_f32(hx, "MinibatchStdBwd")
+        b, h, w, c = x.shape
+        dgs = torch.empty(b, device=x.device, dtype=torch.float32)
+        dx = torch.empty_like(x)
+        _C.call("ngan_mbstd_bwdbwd", hx, gs, x, dgs, dx, _mbstd_ws(x, g_eff), b, h, w, c, segments, g_eff)
+        return (dgs if ctx.needs_input_grad[0] else None), (dx if ctx.needs_input_grad[1] else None), None, None
+
+
+def _stdfield(c, s, w_std, scale, shape):
+    b, h, w, ch = shape
+    out = torch.empty(shape, device=s.device, dtype=torch.float32)
+    _C.call("ngan_stdfield_add", c, s, w_std.detach(), out, b, h, w, ch, float(scale))
+    return out
+
+
+class StdFieldAdd(Function):
+    """out = c + scale * s[n] * T[y, x, co]: the head conv's output plus what the constant plane s contributes through w_std
+    (C, 1, 3, 3) under zero padding.  c None: the field alone, of shape `shape`."""
+
+    @staticmethod
+    def forward(ctx, c, s, w_std, scale, shape=None):
+        if c is not None:
+            c = _mbstd_f32(c, "StdFieldAdd")
+            shape = tuple(c.shape)
+        s, w_std = _c(s), _c(w_std)
+        if tuple(w_std.shape) != (shape[3], 1, 3, 3) or tuple(s.shape) != (shape[0],):
+            raise RuntimeError(f"StdFieldAdd: s {tuple(s.shape)} / w_std {tuple(w_std.shape)} do not fit an output of shape {shape}")
+        ctx.save_for_backward(s, w_std)
+        ctx.scale = scale
+        return _stdfield(c, s, w_std, scale, shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, w_std = ctx.saved_tensors
+        gs = StdFieldDs.apply(g, w_std, ctx.scale) if ctx.needs_input_grad[1] else None
+        gw = StdFieldDw.apply(g, s, ctx.scale) if (ctx.needs_input_grad[2] and _param_grads_wanted()) else None
+        return (g if ctx.needs_input_grad[0] else None), gs, gw, None, None
+
+
+class StdFieldDs(Function):
+    """gs[n] = scale * <g[n], T(w_std)>; bilinear in (g, w_std)."""
+
+    @staticmethod
+    def forward(ctx, g, w_std, scale):
+        g, w_std = _mbstd_f32(g, "StdFieldDs"), _c(w_std)
+        b, h, w, ch = g.shape
+        gs = torch.empty(b, device=g.device, dtype=torch.float32)
+        _C.call("ngan_stdfield_ds", g, w_std.detach(), gs, b, h, w, ch, float(scale))
+        ctx.save_for_backward(g, w_std)
+        ctx.scale = scale
+        return gs
+
+    @staticmethod
+    def backward(ctx, hs):
+        g, w_std = ctx.saved_tensors
+        gg = StdFieldAdd.apply(None, hs, w_std, ctx.scale, tuple(g.shape)) if ctx.needs_input_grad[0] else None
+        gw = StdFieldDw.apply(g, hs, ctx.scale) if (ctx.needs_input_grad[1] and _param_grads_wanted()) else None
+        return gg, gw, None
+
+
+class StdFieldDw(Function):
+    """gw (C, 1, 3, 3) = scale * sum_n s[n] * (sum of g[n] over the pixels whose tap is inside); bilinear in (g, s)."""
+
+    @staticmethod
+    def forward(ctx, g, s, scale):
+        g, s = _mbstd_f32(g, "StdFieldDw"), _c(s)
+        b, h, w, ch = g.shape
+        gw = torch.empty((ch, 1, 3, 3), device=g.device, dtype=torch.float32)
+        _C.call("ngan_stdfield_dw", g, s, gw, b, h, w, ch, float(scale))
+        ctx.save_for_backward(g, s)
+        ctx.scale = scale
+        return gw
+
+    @staticmethod
+    def backward(ctx, hw):
+        g, s = ctx.saved_tensors
+        gg = StdFieldAdd.apply(None, s, hw, ctx.scale, tuple(g.shape)) if ctx.needs_input_grad[0] else None
+        gs = StdFieldDs.apply(g, hw, ctx.scale) if ctx.needs_input_grad[1] else None
+        return gg, gs, None
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -803,6 +803,9 @@ class PGGANTrainer(_Trainer):
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
         ema_beta = _check_ema_beta(ema_beta)
         aug_mask, aug_p, aug_seed = _check_diffaug(diffaug, diffaug_p, diffaug_seed)
+        if getattr(discriminator, 'mbstd_group', 0) > 0 and ops.get_conv_precision() == "bf16":
+            raise NotImplementedError('a critic with mbstd_group > 0 is built for fp32 activation storage (conv precisions "f32" and '
+                                      '"bf16x3"), not for the "bf16" storage mode')
         self.G, self.D = generator, discriminator
         self.device = next(generator.parameters()).device
         self.n_critic = n_critic
@@ -1800,6 +1803,8 @@ def build_arg_parser():
     p.add_argument('--diffaug_seed', type=int, default=0, help='seed of the augmentation parameters\' private stream')
     p.add_argument('--lsgan', action='store_true', default=False, help='train the PG nets with the least-squares objective (the '
                                                                         'reference\'s D_LS_loss / G_LS_loss) instead of the Wasserstein one')
+    p.add_argument('--mbstd_group', type=int, default=0, help='group size of a minibatch standard-deviation channel in the PG '
+                                                              'critic\'s head (Karras et al. 2018 use 4); 0: off')
     for m in METRICS:                                                    # one group of integer flags per checkpoint metric
         for name, _, default, text in settings(m):
             p.add_argument('--' + name, type=int, default=default, help=text)
@@ -1849,6 +1854,8 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     if config.wgan:
         if lsgan:
             raise ValueError("lsgan=True is not available for the WGAN nets (wgan=True, pggan=False)")
+        if getattr(config, 'mbstd_group', 0):
+            raise ValueError("mbstd_group > 0 is not available for the WGAN nets (wgan=True, pggan=False)")
         kw = dict(learning_rate=config.learning_rate, drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, device_latents=True,
                   process_group=process_group, sync_batchnorm=bool(distributed), ema_beta=getattr(config, 'ema_beta', 0.0), **aug)
         if config.RMSprop:
@@ -1942,7 +1949,7 @@ def _train_main(argv, options, local_rank, group):
         return _wgan_main(config, dataset, device, group, rank)
     size_init = dataset.image_size_max // (2 ** n_up)                                       # train.py:162-165
     G = models.Generator_PG(config.N_gen_features, image_size_init=size_init).to(device)    # train.py:172-175
-    D = models.Discriminator_PG(config.N_dis_features, image_size_init=size_init).to(device)
+    D = models.Discriminator_PG(config.N_dis_features, image_size_init=size_init, mbstd_group=int(getattr(config, 'mbstd_group', 0))).to(device)
     trainer, checkpoint, epoch_init, epoch_final = _trainer_and_checkpoint(config, G, D, device, group, rank)
     assert G.image_size == D.image_size, 'The generator and discriminator are at different resolution'   # train.py:215-216
     lr0 = lr_schedule(epoch_init - 1, config.learning_rate, config.transit_sch, config.N_epochs)       # train.py:288-289

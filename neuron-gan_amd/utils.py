@@ -46,7 +46,9 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # by either side load in the other.  One optional extra key, 'optimizer_state', carries the fused Adam's moments and
 # per-tensor step counts (the reference does not save optimiser state at all).  A trainer that keeps an averaged generator
 # (train.py, `ema_beta`) adds 'Generator_ema_state': the averaged weights under the keys of 'Generator_state', tensors only.  The
-# A PGGANTrainer writes 'objective' ("wasserstein" or "lsgan", train.py `objective=`) beside it; a file without the key is Wasserstein.  The
+# A PGGANTrainer writes 'objective' ("wasserstein" or "lsgan", train.py `objective=`) beside it; a file without the key is Wasserstein.  A
+# critic built with mbstd_group > 0 lists 'mbstd_group' in 'Discriminator_attrs' and holds 'layers.<k>.weight_std' in its state; a file
+# without the attribute holds the reference's critic.  The
 # reference's loaders read the keys they know and ignore the rest (utils.py:185-199 index five series keys and the two attribute
 # dictionaries, models.py the state dictionaries).  A run that scores its checkpoints (train.py, `<prefix>_period`) adds one key per row
 # of metric_table.METRICS that scored, 'SWD' .. 'BRANCH': a list with one entry {epoch, image_size, ...} per scored checkpoint, whose
@@ -154,6 +156,13 @@ class Checkpointer:
             if saved != self.trainer.objective:
                 raise ValueError('{} was trained with the {} objective and cannot be resumed with the {} objective'.format(
                     source, saved, self.trainer.objective))
+        # the critic's minibatch standard-deviation group (models.Discriminator_PG(mbstd_group=); a file without the key is 0, off) changes
+        # the head's parameters and its equalised-LR constant: the file's weights mean something else under another value
+        saved_group = int(checkpoint_dict.get('Discriminator_attrs', {}).get('mbstd_group', 0))
+        own_group = int(getattr(self.Discriminator_net, 'mbstd_group', 0))
+        if saved_group != own_group:
+            raise ValueError('{} was trained with mbstd_group={} and cannot be loaded into a critic with mbstd_group={}'.format(
+                source, saved_group, own_group))
         if filename is None:
             self.epoch = checkpoint_dict['epoch']
             self.Loss_real[:self.epoch] = checkpoint_dict['Loss_real']
