@@ -138,7 +138,9 @@ int ngan_conv3x3_wgrad(const float* x, const float* g, float* gw, float* workspa
  * `entries`: host array of n records
  *   { const float* partial[4]; float* gw; int nparts[4]; int nsrc, nslices, n_ci_slices, co_s, ci_s, K, accumulate, reserved;
  *     float scale[4]; }                                                                                     (104 bytes)
- * with (nparts, nslices, n_ci_slices, co_s, ci_s) from ngan_conv3x3_wgrad_plan (out5).  accumulate != 0: gw += sum. */
+ * with (nparts, nslices, n_ci_slices, co_s, ci_s) from ngan_conv3x3_wgrad_plan (out5).  accumulate != 0: gw += sum.
+ * Several records may name the same gw (more than 4 contributions: the later records accumulate): they are applied in their order,
+ * each in a launch after the previous one's. */
 int ngan_conv3x3_wgrad_plan(int B, int H, int W, int Cin, int Cout, int precision, int* out5);
 int ngan_conv3x3_wgrad_reduce_many(const void* entries, int n, void* stream);
 

@@ -902,16 +902,25 @@ extern "C" int ngan_conv3x3_wgrad_plan(int B, int H, int W, int Cin, int Cout, i
 extern "C" int ngan_conv3x3_wgrad_reduce_many(const void* entries, int n, void* stream) {
     NGAN_REQUIRE(entries && n > 0, NGAN_ERR_ARG, "conv3x3_wgrad_reduce_many: bad argument");
     const ReduceEntry* src = reinterpret_cast<const ReduceEntry*>(entries);
-    for (int base = 0; base < n; base += kReduceBatch) {
+    for (int base = 0; base < n;) {
         ReduceBatch b;
-        b.n = n - base < kReduceBatch ? n - base : kReduceBatch;
+        b.n = 0;
         int blocks = 0;
-        for (int i = 0; i < b.n; ++i) {
+        while (base + b.n < n && b.n < kReduceBatch) {
+            const int i = b.n;
+            // Two entries of one launch run concurrently, and an entry reads and writes its gradient without atomics: a further entry
+            // for a gradient of this launch (the fifth and later contributions to it, which accumulate) starts the next launch, so that
+            // the entries of one gradient are applied in their order on the stream.
+            bool same_gw = false;
+            for (int k = 0; k < i; ++k) same_gw = same_gw || b.e[k].gw == src[base + i].gw;
+            if (same_gw) break;
             b.e[i] = src[base + i];
             NGAN_REQUIRE(b.e[i].nsrc >= 1 && b.e[i].nsrc <= 4 && b.e[i].gw, NGAN_ERR_ARG, "conv3x3_wgrad_reduce_many: bad entry %d", base + i);
             b.e[i].first_block = blocks;
             blocks += ngan::ceil_div((long)b.e[i].nslices * 9 * b.e[i].co_s * b.e[i].ci_s, 4 * (kReduceThreads / reduce_groups(b.e[i])));
+            b.n = i + 1;
         }
+        base += b.n;
         hipLaunchKernelGGL(wgrad_reduce_many_kernel, dim3(blocks), dim3(kReduceThreads), 0, (hipStream_t)stream, b);
         int st = ngan::launch_status("ngan_conv3x3_wgrad_reduce_many");
         if (st) return st;

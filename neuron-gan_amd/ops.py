@@ -465,7 +465,8 @@ def flush_wgrad():
     rec, n = b"", 0
     for e in _pending.values():
         src = sorted(e["sources"], key=lambda s: s[3])        # stable: equal roles keep their arrival order
-        for first in range(0, len(src), 4):            # at most 4 slab sets per record; further records accumulate
+        for first in range(0, len(src), 4):            # at most 4 slab sets per record; further records accumulate (reduce_many applies
+                                                       # the records of one gradient in order, in launches of their own)
             part = src[first:first + 4]
             ptrs = [s[0].data_ptr() for s in part] + [0] * (4 - len(part))
             nparts = [s[1] for s in part] + [0] * (4 - len(part))
