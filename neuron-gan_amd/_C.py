@@ -162,6 +162,14 @@ MBSTD_NON_STATUS = {
     "ngan_mbstd_workspace_doubles": ([_I, _I, _I, _I, _I], _L),
 }
 
+# include/ngan_geoaug.h, the third extension section: the geometric groups of the differentiable augmentation (ops.DiffGeometry);
+# listed by `geoaug_symbols`, like the tables above
+GEOAUG_SIGNATURES = {
+    "ngan_diffgeo_params": [_P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "ngan_diffgeo_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "ngan_diffgeo_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+}
+
 NON_STATUS = {
     "ngan_version": ([], ctypes.c_char_p),
     "ngan_last_error": ([], ctypes.c_char_p),
@@ -207,7 +215,8 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                f"or `make -C neuron-gan_amd/csrc`; there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(MBSTD_SIGNATURES.items()):
+        for name, argtypes in (list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(MBSTD_SIGNATURES.items())
+                               + list(GEOAUG_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
@@ -229,6 +238,10 @@ def objective_symbols():
 
 def mbstd_symbols():
     return list(MBSTD_SIGNATURES) + list(MBSTD_NON_STATUS)
+
+
+def geoaug_symbols():
+    return list(GEOAUG_SIGNATURES)
 
 
 def mbstd_workspace_doubles(B, H, W, C, G_eff) -> int:

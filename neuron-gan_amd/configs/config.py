@@ -104,8 +104,8 @@ def validate_configs(create_dirs=False):
     # differentiable augmentation of the critic's inputs (an addition of this implementation): diffaug '' is off, otherwise a comma
     # list of groups, each applied to each sample with probability diffaug_p; diffaug_seed seeds the parameters' private stream
     groups = [s.strip() for s in g['diffaug'].split(',')] if isinstance(g['diffaug'], str) else None
-    if groups is None or any(s not in ('', 'color', 'translation', 'cutout') for s in groups):
-        raise ValueError(f"diffaug={g['diffaug']!r} must be a comma list from color, translation, cutout (empty: off)")
+    if groups is None or any(s not in ('', 'color', 'translation', 'cutout', 'blit', 'geometry') for s in groups):
+        raise ValueError(f"diffaug={g['diffaug']!r} must be a comma list from color, translation, cutout, blit, geometry (empty: off)")
     if isinstance(g['diffaug_p'], bool) or not (isinstance(g['diffaug_p'], (int, float)) and 0 <= g['diffaug_p'] <= 1):
         raise ValueError(f"diffaug_p={g['diffaug_p']!r} must lie in [0, 1]")
     if not (isinstance(g['diffaug_seed'], int) and not isinstance(g['diffaug_seed'], bool) and g['diffaug_seed'] >= 0):

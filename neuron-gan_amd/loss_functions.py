@@ -41,24 +41,41 @@ class DiffAugmentHook:
     The critic-step images carry no gradient and are augmented without an autograd node; the penalty interpolates between images
     that are already augmented, so its double-backward graph is the un-augmented one.  colour=False: no table opens the colour
     group (b = 0, c = 1 everywhere), which saves the sum pass of every call.  fill: what shifted-out and cut pixels hold
-    (`DIFFAUG_FILL`)."""
+    (`DIFFAUG_FILL`).  geo_real / geo_fake / geo_tilde / geo_gen: affine tables of the geometric groups (fp32 (rows, 8),
+    `ops.diffgeo_table` / `ops.diffgeo_params`), one per kind of image likewise; where one is given the bilinear resampling
+    (ops.DiffGeometry) runs first, and where the matching table of the older groups is None their launches are not issued."""
 
-    def __init__(self, real=None, fake=None, tilde=None, gen=None, colour=True, fill=DIFFAUG_FILL):
+    def __init__(self, real=None, fake=None, tilde=None, gen=None, colour=True, fill=DIFFAUG_FILL, *, geo_real=None, geo_fake=None,
+                 geo_tilde=None, geo_gen=None):
         self.real, self.fake, self.tilde, self.gen, self.colour, self.fill = real, fake, tilde, gen, bool(colour), float(fill)
+        self.geo_real, self.geo_fake, self.geo_tilde, self.geo_gen = geo_real, geo_fake, geo_tilde, geo_gen
+
+    def transform(self, x, table, geo, out=None):
+        """T(x) without an autograd node: the resampling (where `geo` is given) first, then the colour / translation / cutout
+        launches (where `table` is given); the last launch issued writes `out`"""
+        if geo is not None:
+            if table is None:
+                return ops.diffgeo(x, geo, out=out, fill=self.fill)
+            x = ops.diffgeo(x, geo, fill=self.fill)
+        elif table is None:
+            raise ValueError("DiffAugmentHook: this kind of image has neither a parameter table nor an affine table")
+        return ops.diffaug(x, table, self.colour, out=out, fill=self.fill)
 
     def critic_batch(self, real, fake):
         """[T(real) | T(fake)], the W-loss's one critic batch: both halves are written straight into it"""
         b = real.size(0)
         out = torch.empty((b + fake.size(0),) + tuple(real.shape[1:]), device=real.device, dtype=real.dtype)
-        ops.diffaug(real, self.real, self.colour, out=out[:b], fill=self.fill)
-        ops.diffaug(fake, self.fake, self.colour, out=out[b:], fill=self.fill)
+        self.transform(real, self.real, self.geo_real, out=out[:b])
+        self.transform(fake, self.fake, self.geo_fake, out=out[b:])
         return out
 
     def penalty_pair(self, real, x_tilde):
-        return ops.diffaug(real, self.real, self.colour, fill=self.fill), ops.diffaug(x_tilde, self.tilde, self.colour, fill=self.fill)
+        return self.transform(real, self.real, self.geo_real), self.transform(x_tilde, self.tilde, self.geo_tilde)
 
     def generated(self, fake):
-        return ops.DiffAugment.apply(fake, self.gen, self.colour, self.fill)
+        if self.geo_gen is not None:
+            fake = ops.DiffGeometry.apply(fake, self.geo_gen, self.fill)
+        return fake if self.gen is None else ops.DiffAugment.apply(fake, self.gen, self.colour, self.fill)
 
 
 class D_W_loss(nn.Module):

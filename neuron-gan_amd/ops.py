@@ -1640,12 +1640,13 @@ def latent_normalize_(z, clamp=5.0):
 # ---------------------------------------------------------------------------------------------------------
 # differentiable augmentation of the critic's inputs (include/ngan.h, last section)
 # ---------------------------------------------------------------------------------------------------------
-DIFFAUG_GROUPS = {"color": 1, "translation": 2, "cutout": 4}      # policy names -> bits of ngan_diffaug_params' mask
+# policy names -> bits of the mask: the low three are ngan_diffaug_params' mask, bits 8 and 16 (>> 3) ngan_diffgeo_params'
+DIFFAUG_GROUPS = {"color": 1, "translation": 2, "cutout": 4, "blit": 8, "geometry": 16}
 DIFFAUG_IDENTITY = (0.0, 1.0, 0, 0, 0, 0, 0, 0)                  # {b, c, tx, ty, i0, i1, j0, j1}
 
 
 def diffaug_policy_mask(policy):
-    """"" / "color,translation,cutout" (any subset, any order) -> the mask; an unknown name raises ValueError"""
+    """"" / "color,translation,cutout,blit,geometry" (any subset, any order) -> the mask; an unknown name raises ValueError"""
     if policy is None:
         return 0
     if not isinstance(policy, str):
@@ -1694,7 +1695,7 @@ def _diffaug_ws(x, colour):
 def diffaug_params(uniforms, table, image_size, policy_mask, p):
     """rows 0 .. B-1 of `table` from the (B, 8) uniforms, on the device (ngan_diffaug_params)"""
     _C.call("ngan_diffaug_params", _c(uniforms), table, uniforms.shape[0], int(image_size), int(image_size), table.shape[0],
-            int(policy_mask), float(p))
+            int(policy_mask) & 7, float(p))
     return table
 
 
@@ -1737,3 +1738,73 @@ class DiffAugment(Function):
         gx = torch.empty_like(gy)
         _C.call("ngan_diffaug_bwd", gy, table, gx, _diffaug_ws(gy, ctx.colour), b, c, h, w, table.shape[0], int(ctx.colour))
         return gx, None, None, None
+
+
+# ---- the geometric groups: one bilinear resampling per sample (include/ngan_geoaug.h) ----------------------------
+DIFFGEO_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)                # {a00, a01, a02, a10, a11, a12}: source = (a00 i + a01 j + a02, ...)
+
+
+def diffgeo_table(rows, device=None):
+    """A table of affine rows {a00, a01, a02, a10, a11, a12}: an fp32 (B, 8) tensor, the 32-byte records of include/ngan_geoaug.h"""
+    t = torch.zeros((len(rows), 8), dtype=torch.float32)
+    if len(rows):
+        t[:, :6] = torch.from_numpy(np.asarray([tuple(r)[:6] for r in rows], dtype=np.float32).reshape(len(rows), 6))
+    return t if device is None else t.to(device)
+
+
+def diffgeo_table_rows(table):
+    """inverse of diffgeo_table: a list of tuples (a00, a01, a02, a10, a11, a12)"""
+    raw = table.detach().cpu().numpy().astype(np.float32)
+    return [tuple(float(v) for v in r[:6]) for r in raw]
+
+
+def _diffgeo_check(x, table):
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"diffgeo: images must be fp32 (B, C, R, R), got {x.dtype} {tuple(x.shape)}")
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 8:
+        raise ValueError(f"diffgeo: the table must be fp32 (rows, 8), got {table.dtype} {tuple(table.shape)}")
+
+
+def diffgeo_params(uniforms, table, image_size, policy_mask, p):
+    """rows 0 .. B-1 of `table` from the (B, 8) uniforms, on the device (ngan_diffgeo_params); policy_mask: DIFFAUG_GROUPS' bits"""
+    _C.call("ngan_diffgeo_params", _c(uniforms), table, uniforms.shape[0], int(image_size), int(image_size), table.shape[0],
+            (int(policy_mask) >> 3) & 3, float(p))
+    return table
+
+
+def diffgeo(x, table, out=None, fill=0.0):
+    """T(x) with no autograd node, for images that carry no gradient (the critic step); `out` may be a row range of a larger batch
+    buffer"""
+    x = _c(x.detach())
+    _diffgeo_check(x, table)
+    b, c, h, w = x.shape
+    y = torch.empty_like(x) if out is None else out
+    if y.shape != x.shape or y.dtype != x.dtype:
+        raise ValueError(f"diffgeo: out is {y.dtype} {tuple(y.shape)}, the images {x.dtype} {tuple(x.shape)}")
+    _C.call("ngan_diffgeo_fwd", x, table, y, b, c, h, w, table.shape[0], float(fill))
+    return y
+
+
+class DiffGeometry(Function):
+    """y = T(x) for the affine table `table` (one row per sample; `diffgeo_table`, or rows `diffgeo_params` wrote), differentiable
+    once in x: bilinear resampling with the constant `fill` outside the image (0; the trainer passes -1)."""
+
+    @staticmethod
+    def forward(ctx, x, table, fill=0.0):
+        x = _c(x)
+        _diffgeo_check(x, table)
+        b, c, h, w = x.shape
+        y = torch.empty_like(x)
+        _C.call("ngan_diffgeo_fwd", x, table, y, b, c, h, w, table.shape[0], float(fill))
+        ctx.save_for_backward(table)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        (table,) = ctx.saved_tensors
+        gy = _c(gy)
+        b, c, h, w = gy.shape
+        gx = torch.empty_like(gy)
+        _C.call("ngan_diffgeo_bwd", gy, table, gx, b, c, h, w, table.shape[0])
+        return gx, None, None

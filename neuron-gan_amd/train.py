@@ -399,15 +399,15 @@ def diffaug_stream_seed(seed, epoch, rank):
 
 
 class _CriticAugment(DiffAugmentHook):
-    """The hook of a trainer's critic step: `prepare` augments the reals (table `real`) and all generated images of the step (table
-    `fake`: the W-loss's b rows, then the penalty's b) once, into one batch buffer; the W-loss reads its first 2 b rows as they lie
-    -- no concatenation -- and the penalty interpolates between the first and the last b."""
+    """The hook of a trainer's critic step: `prepare` augments the reals (tables `real` / `geo_real`) and all generated images of the
+    step (tables `fake` / `geo_fake`: the W-loss's b rows, then the penalty's b) once, into one batch buffer; the W-loss reads its
+    first 2 b rows as they lie -- no concatenation -- and the penalty interpolates between the first and the last b."""
 
     def prepare(self, real, fakes):
         b = real.size(0)
         self._buf = torch.empty((b + fakes.size(0),) + tuple(real.shape[1:]), device=real.device, dtype=real.dtype)
-        ops.diffaug(real, self.real, self.colour, out=self._buf[:b], fill=self.fill)
-        ops.diffaug(fakes, self.fake, self.colour, out=self._buf[b:], fill=self.fill)
+        self.transform(real, self.real, self.geo_real, out=self._buf[:b])
+        self.transform(fakes, self.fake, self.geo_fake, out=self._buf[b:])
 
     def critic_batch(self, real, fake):
         return self._buf[:real.size(0) + fake.size(0)]
@@ -422,13 +422,22 @@ class _DiffAugTables:
     persistent table buffer and one persistent uniform buffer -- captured graphs hold their addresses, so neither is ever
     reallocated -- and a private generator on the trainer's device, so that neither the global nor the latent stream is touched.
     Rows of an iteration on b samples: critic step s has [s 3b, s 3b + b) for the reals and the 2 b after them for its generated
-    images; the generator step's b rows follow the last critic step's."""
+    images; the generator step's b rows follow the last critic step's.
+    The geometric groups (blit, geometry) have a second table (fp32 affine rows, `ops.diffgeo_table`) and a second uniform buffer
+    with the same row layout, allocated only when one of them is named; their (n, 8) draw follows the older groups' draw on the
+    same private stream, and each draw is made only when one of its groups is named -- a policy without the new groups consumes
+    the stream as it always did.  `table` is None without one of the older groups: their launches are then not issued."""
 
     def __init__(self, mask, p, seed, device, rank):
         self.mask, self.p, self.seed, self.rank = mask, p, seed, rank
         self.colour = bool(mask & ops.DIFFAUG_GROUPS["color"])
-        self.table = ops.diffaug_table([ops.DIFFAUG_IDENTITY], device).repeat(DIFFAUG_ROWS, 1).contiguous()
-        self.uniforms = torch.zeros((DIFFAUG_ROWS, 8), device=device, dtype=torch.float32)
+        self.table = self.uniforms = self.geo_table = self.geo_uniforms = None
+        if mask & 7:
+            self.table = ops.diffaug_table([ops.DIFFAUG_IDENTITY], device).repeat(DIFFAUG_ROWS, 1).contiguous()
+            self.uniforms = torch.zeros((DIFFAUG_ROWS, 8), device=device, dtype=torch.float32)
+        if mask >> 3:
+            self.geo_table = ops.diffgeo_table([ops.DIFFGEO_IDENTITY], device).repeat(DIFFAUG_ROWS, 1).contiguous()
+            self.geo_uniforms = torch.zeros((DIFFAUG_ROWS, 8), device=device, dtype=torch.float32)
         self.generator = torch.Generator(device=device)
         self.reseed(0)
 
@@ -440,30 +449,61 @@ class _DiffAugTables:
 
     def prepare(self, b, n_critic, image_size, tables=None):
         """the tables of one iteration: drawn from the private stream and mapped on the device, or copied from `tables`
-        ({"real": (b, 8), "fake": (2 b, 8), "gen": (b, 8)} int32, any subset; every critic step of the iteration gets the same)"""
+        ({"real": (b, 8), "fake": (2 b, 8), "gen": (b, 8)} int32 and {"geo_real", "geo_fake", "geo_gen"} fp32 of the same shapes, any
+        subset; every critic step of the iteration gets the same)"""
         n = self.rows(b, n_critic)
         if n > DIFFAUG_ROWS:
             raise ValueError(f"diffaug: batch {b} with n_critic {n_critic} needs {n} table rows, the buffer holds {DIFFAUG_ROWS}")
         if tables is None:
-            torch.rand((n, 8), generator=self.generator, out=self.uniforms[:n])
-            ops.diffaug_params(self.uniforms[:n], self.table, image_size, self.mask, self.p)
+            if self.table is not None:
+                torch.rand((n, 8), generator=self.generator, out=self.uniforms[:n])
+                ops.diffaug_params(self.uniforms[:n], self.table, image_size, self.mask, self.p)
+            if self.geo_table is not None:
+                torch.rand((n, 8), generator=self.generator, out=self.geo_uniforms[:n])
+                ops.diffgeo_params(self.geo_uniforms[:n], self.geo_table, image_size, self.mask, self.p)
             return
-        for s in range(max(int(n_critic), 1)):
-            for name, view in (("real", self.real(s, b)), ("fake", self.fake(s, b))):
-                if tables.get(name) is not None:
-                    view.copy_(tables[name], non_blocking=True)
-        if tables.get("gen") is not None:
-            self.gen(b, n_critic).copy_(tables["gen"], non_blocking=True)
+        for prefix, table in (("", self.table), ("geo_", self.geo_table)):
+            if table is None:
+                if any(tables.get(prefix + k) is not None for k in ("real", "fake", "gen")):
+                    raise ValueError(f"diffaug: {prefix}* tables were passed, the policy names none of their groups")
+                continue
+            for s in range(max(int(n_critic), 1)):
+                for name, view in ((prefix + "real", self._real(table, s, b)), (prefix + "fake", self._fake(table, s, b))):
+                    if tables.get(name) is not None:
+                        view.copy_(tables[name], non_blocking=True)
+            if tables.get(prefix + "gen") is not None:
+                self._gen(table, b, n_critic).copy_(tables[prefix + "gen"], non_blocking=True)
+
+    @staticmethod
+    def _real(table, s, b):
+        return None if table is None else table[s * 3 * b:s * 3 * b + b]
+
+    @staticmethod
+    def _fake(table, s, b):
+        return None if table is None else table[s * 3 * b + b:(s + 1) * 3 * b]
+
+    @staticmethod
+    def _gen(table, b, n_critic):
+        o = max(int(n_critic), 1) * 3 * b
+        return None if table is None else table[o:o + b]
 
     def real(self, s, b):
-        return self.table[s * 3 * b:s * 3 * b + b]
+        return self._real(self.table, s, b)
 
     def fake(self, s, b):
-        return self.table[s * 3 * b + b:(s + 1) * 3 * b]
+        return self._fake(self.table, s, b)
 
     def gen(self, b, n_critic):
-        o = max(int(n_critic), 1) * 3 * b
-        return self.table[o:o + b]
+        return self._gen(self.table, b, n_critic)
+
+    def geo_real(self, s, b):
+        return self._real(self.geo_table, s, b)
+
+    def geo_fake(self, s, b):
+        return self._fake(self.geo_table, s, b)
+
+    def geo_gen(self, b, n_critic):
+        return self._gen(self.geo_table, b, n_critic)
 
 
 class _AveragedGenerator:
@@ -787,9 +827,11 @@ class PGGANTrainer(_Trainer):
         ema_beta: 0 or None -- off (no buffer, no launch: the code path of a build without the feature); 0 < ema_beta < 1 -- keep the
         averaged generator with this decay (`_AveragedGenerator`)
         diffaug: "" -- off (no buffer, no launch, no random draw: the code path of a build without the feature); a comma list from
-        color, translation, cutout -- every image the critic sees, real and generated, goes through the same random differentiable
-        transform (Zhao et al. 2020) and the generator is trained through it; shifted-out and cut pixels hold
-        -1, the images' black, not DiffAugment's 0 (loss_functions.DIFFAUG_FILL says why).  diffaug_p: the probability with
+        color, translation, cutout, blit, geometry -- every image the critic sees, real and generated, goes through the same random
+        differentiable transform (Zhao et al. 2020) and the generator is trained through it; shifted-out and
+        cut pixels hold -1, the images' black, not DiffAugment's 0 (loss_functions.DIFFAUG_FILL says why).  blit (mirror, quarter
+        turns) and geometry (isotropic scale, rotation; Karras et al. 2020) are one bilinear resampling that runs before the other
+        groups' launches, with the same fill.  diffaug_p: the probability with
         which each group is applied to each sample (1: DiffAugment proper; 0: off).  diffaug_seed: of the private uniform stream
         (`reseed_diffaug`).  train_iteration, replay and step draw an iteration's tables; d_step / g_step on their own read the
         tables as they stand (`draw_diffaug_tables`).
@@ -855,7 +897,8 @@ class PGGANTrainer(_Trainer):
 
     def draw_diffaug_tables(self, b, tables=None):
         """The tables of one iteration on b samples: fresh draws from the private stream, or `tables` ({"real": (b, 8), "fake":
-        (2 b, 8), "gen": (b, 8)}, int32: `ops.diffaug_table`).  Eager by design -- inside a stream capture this is a no-op, the
+        (2 b, 8), "gen": (b, 8)}, int32: `ops.diffaug_table`; "geo_real" / "geo_fake" / "geo_gen", fp32 of the same shapes:
+        `ops.diffgeo_table`).  Eager by design -- inside a stream capture this is a no-op, the
         captured launches read the persistent buffer and replay() refills it first."""
         if self._aug is None:
             if tables is not None:
@@ -941,8 +984,10 @@ class PGGANTrainer(_Trainer):
         hook = None
         if self._aug is not None:
             # reals and all generated images of the step are augmented once, detached; the W-loss and the penalty read views
-            hook = _CriticAugment(real=self._aug.real(self._aug_step, b), fake=self._aug.fake(self._aug_step, b)[:fakes.size(0)],
-                                  colour=self._aug.colour)
+            cut = lambda t: None if t is None else t[:fakes.size(0)]     # noqa: E731  (without the penalty: the W-loss's b rows)
+            hook = _CriticAugment(real=self._aug.real(self._aug_step, b), fake=cut(self._aug.fake(self._aug_step, b)),
+                                  colour=self._aug.colour, geo_real=self._aug.geo_real(self._aug_step, b),
+                                  geo_fake=cut(self._aug.geo_fake(self._aug_step, b)))
             hook.prepare(real, fakes)
         loss, s_real, s_fake = self.d_loss(real, fake_images=fakes[:b], augment=hook)  # train.py:358
         gp = self.gp_loss(real, x_tilde=fakes[b:] if with_gp else None, epsilon=eps, augment=hook if with_gp else None)  # train.py:361
@@ -979,7 +1024,8 @@ class PGGANTrainer(_Trainer):
         try:
             hook = None
             if self._aug is not None:
-                hook = DiffAugmentHook(gen=self._aug.gen(b, self.n_critic), colour=self._aug.colour)
+                hook = DiffAugmentHook(gen=self._aug.gen(b, self.n_critic), colour=self._aug.colour,
+                                       geo_gen=self._aug.geo_gen(b, self.n_critic))
             loss, self.last_z_g = self.g_loss(real, z=self._latent(b, z), augment=hook)  # train.py:376
             # the stem hands over factors instead of a gradient when they are exchanged (data parallel) or go straight to Adam
             self._stem_sink_active = self.stem is not None and (self._stem_for_exchange or self._stem_grad_skipped)
@@ -1798,7 +1844,7 @@ def build_arg_parser():
     p.add_argument('--N_epochs_session', type=int, default=None)
     p.add_argument('--ema_beta', type=float, default=0.0, help='decay of the averaged generator (e.g. 0.999); 0: off')
     p.add_argument('--diffaug', type=str, default='', help='differentiable augmentation of every image the critic sees: a comma list '
-                                                           'from color,translation,cutout; empty: off')
+                                                           'from color,translation,cutout,blit,geometry; empty: off')
     p.add_argument('--diffaug_p', type=float, default=1.0, help='probability of each augmentation group per sample')
     p.add_argument('--diffaug_seed', type=int, default=0, help='seed of the augmentation parameters\' private stream')
     p.add_argument('--lsgan', action='store_true', default=False, help='train the PG nets with the least-squares objective (the '
