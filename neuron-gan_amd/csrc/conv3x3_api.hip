@@ -145,8 +145,9 @@ extern "C" int ngan_conv3x3_kernel_name(int B, int H, int W, int K, int N, int r
         return ngan::conv3x3_mid_kernel_name(B, H, W, precision == 2 ? 32 : K, N, resample, epilogue, out_mode, precision, buf, len);
     else {
         const TileCfg c = kCfg[mti][ci];
+        // (the generic kernel has epilogues 0 and 1: ngan_conv3x3_fwd_ex runs a PixelNorm backward as a second launch)
         snprintf(buf, len, "conv3x3_kernel<%d, %d, %d, %d, %d, %d, %d>", c.mtw, c.wn, c.pgw, c.pcg, out_mode ? 0 : resample,
-                 out_mode ? 0 : epilogue, out_mode);
+                 (out_mode || epilogue == EPI_PN_BWD) ? 0 : epilogue, out_mode);
     }
     return NGAN_OK;
 }

@@ -5,7 +5,8 @@ runs on the CPU (where tests/test_fp64_conv_cpu.py checks it against torch's own
 reference takes well under a second).  A 3x3 pad-1 convolution is nine shifted (P x K)(K x N) products, a 4x4 stride-2 one sixteen.
 
     resample codes (ops.RES_*):  0 plain, 1 2x2 average pool on load, 2 bilinear x2 on load (align_corners=False)
-    3x3:        conv3x3 / conv3x3_dgrad / conv3x3_wgrad, lrelu_pixelnorm (epilogue 1), pixelnorm_bwd (epilogue 2), pool2 (side output)
+    3x3:        conv3x3 / conv3x3_dgrad / conv3x3_wgrad, lrelu_pixelnorm (epilogue 1), pixelnorm_bwd (epilogue 2), pool2 (side output),
+                pool_adjoint (out_mode 1), to_image (epilogue 3's tanh colour projection)
     stride 2:   s2_down (Conv2d k4 s2 p1), s2_up (ConvTranspose2d k4 s2 p1), s2_wgrad, act_on_load (BatchNorm -> LeakyReLU on load)
     BatchNorm:  bn_stats (batch statistics, folded transform, running buffers), bn_fold_eval, bn_act_backward (with / without the
                 activation), act_backward (no BatchNorm), each with its absolute-value twin (*_abs) for tests/wgan_cases.py
@@ -114,6 +115,18 @@ def pixelnorm_bwd(g, y, r, slope):
     """epilogue 2: gradient w.r.t. the pre-activation of the producer (y, r) = lrelu_pixelnorm(c), given g w.r.t. y"""
     m = torch.where(y > 0, torch.ones_like(y), torch.full_like(y, slope))
     return m * (g - y * (g * y).mean(-1, keepdim=True)) / r.unsqueeze(-1)
+
+
+def pool_adjoint(c):
+    """the pool-adjoint store (out_mode 1): c (B, H, W, N) -> (B, 2H, 2W, N), 0.25 c to each pixel of the 2x2 block; 0.25 is exact, so the
+    absolute-value twin is pool_adjoint(|c|)"""
+    return resample_adjoint(c, 1)
+
+
+def to_image(y, wimg):
+    """the tanh colour projection of epilogue 3 (one colour): (t, sum_c |y_c| |wimg_c|) with t = tanh(sum_c y_c wimg_c); y (B, H, W, N),
+    wimg (N,) -> (B, H, W) each; the second value is the dot product's absolute-value twin (|tanh'| <= 1)"""
+    return torch.tanh((y * wimg).sum(-1)), (y.abs() * wimg.abs()).sum(-1)
 
 
 # ---- 4x4 stride-2 pad-1 (csrc/stride2.hip) ------------------------------------------------------------------------------------
