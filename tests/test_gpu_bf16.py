@@ -5,7 +5,8 @@ PixelNorm statistics / master weights) -- BASELINE.json's C2 configuration, whic
 * kernel level, through the C ABI: every bf16 kernel against an fp64 evaluation of the same operator ON THE bf16-ROUNDED OPERANDS
   (inputs as stored, weights as the packing kernel rounds them).  What is left is the fp32 accumulation order and the one rounding
   of the store: an output must be the bf16 neighbour of the fp64 value (<= 2^-7 relative, i.e. one bf16 ulp, + accumulation noise);
-  fp32 outputs (norms, weight gradients, images) to 1e-4 / 1e-5.
+  fp32 outputs (norms, weight gradients, images) to 1e-4 / 1e-5.  (The 3x3 forward / input-gradient family is pinned per element, at
+  every template instance and with the store's bits, in tests/test_gpu_bf16_conv.py.)
 * model level, against the reference's golden vectors, at this mode's OWN tolerance.  Where it comes from: tests/lowprec_budget.py
   emulates on the CPU oracle exactly what this mode rounds ("bf16 mode" rows: bf16 storage of every activation and activation
   gradient, bf16 conv weights with the scale folded in, one rounding of a resampled conv input) and reports the deviation from the

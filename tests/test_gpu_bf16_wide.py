@@ -7,7 +7,7 @@ operators at channel counts outside the lane-group kernels' range (csrc/wide.hip
       |got - ref| <= 2^-7 |ref| + C_ACC 2^-24 sum|products|,   C_ACC = 8
   -- one bf16 rounding of the store plus the fp32 accumulation term of a contraction whose terms may cancel (sum|products| is the
   same fp64 contraction on |operands|).  Operators with no contraction get the same bound with sum|products| = |ref| scaled by the
-  channel count of their per-pixel sums.
+  channel count of their per-pixel sums.  (tests/test_gpu_bf16_conv.py pins the wide conv instances per element with fp32-tight bounds.)
 * model level, against the CPU oracle, at tolerances derived BEFORE any GPU run from the CPU emulation of this mode
   (tests/lowprec_budget.py, "bf16mode") on the six width sets below: 1.5 x the largest emulated deviation over the sets, or the
   existing small-net bounds of tests/test_gpu_bf16.py where those are larger.  tests/test_bf16_wide_budget_cpu.py re-derives the
