@@ -244,6 +244,8 @@ int ngan_wloss_head_bwd(const float* scores, int n_real, int n_fake, float drift
 #include "ngan_mbstd.h"
 /* ---- geometric groups of the differentiable augmentation (blit, geometry): declared in ngan_geoaug.h, an extension section likewise ---- */
 #include "ngan_geoaug.h"
+/* ---- one-sided and zero-centred forms of the gradient penalty (opt-in): declared in ngan_penalty.h, an extension section likewise ---- */
+#include "ngan_penalty.h"
 
 /* ---- latent projection: utils.py:77-78 (clamp(-c, c), L2-normalise each row), in place on (rows, dim) normal draws ---------- */
 int ngan_latent_normalize(float* z, int rows, int dim, float clamp, void* stream);

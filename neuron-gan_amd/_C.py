@@ -170,6 +170,13 @@ GEOAUG_SIGNATURES = {
     "ngan_diffgeo_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
+# include/ngan_penalty.h, the fourth extension section: the one-sided and zero-centred forms of the gradient penalty (ops.PenaltyHead);
+# listed by `penalty_symbols`, like the tables above
+PENALTY_SIGNATURES = {
+    "ngan_penalty_head": [_P, _I, _L, _I, _F, _P, _P, _P, _P],
+    "ngan_penalty_bwd": [_P, _P, _I, _L, _I, _F, _P, _P, _P],
+}
+
 NON_STATUS = {
     "ngan_version": ([], ctypes.c_char_p),
     "ngan_last_error": ([], ctypes.c_char_p),
@@ -216,7 +223,7 @@ def lib():
                                f"or `make -C neuron-gan_amd/csrc`; there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(MBSTD_SIGNATURES.items())
-                               + list(GEOAUG_SIGNATURES.items())):
+                               + list(GEOAUG_SIGNATURES.items()) + list(PENALTY_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
@@ -242,6 +249,10 @@ def mbstd_symbols():
 
 def geoaug_symbols():
     return list(GEOAUG_SIGNATURES)
+
+
+def penalty_symbols():
+    return list(PENALTY_SIGNATURES)
 
 
 def mbstd_workspace_doubles(B, H, W, C, G_eff) -> int:

@@ -33,7 +33,7 @@ _DEFAULTS = dict(
     seed=1, checkpointing_period=100, device='default', pin_memory=False, ema_beta=0.0,
     # the checkpoint metrics: <prefix>_period, _images (or _pairs), _seed and the metric's own options, row by row
     **{name: default for m in METRICS for name, _, default, _ in settings(m)},
-    diffaug='', diffaug_p=1.0, diffaug_seed=0, lsgan=False, mbstd_group=0,
+    diffaug='', diffaug_p=1.0, diffaug_seed=0, lsgan=False, mbstd_group=0, grad_pen_mode='gp', grad_pen_interval=1,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -122,6 +122,15 @@ def validate_configs(create_dirs=False):
         raise ValueError(f"mbstd_group={g['mbstd_group']!r} must be an integer >= 0 (0: off)")
     if g['mbstd_group'] and g['wgan']:
         raise ValueError("mbstd_group > 0 is not available for the WGAN nets (wgan=True)")
+    # the penalty's form and lazy regularisation (additions of this implementation): 'gp' is the reference's two-sided penalty, 'lp' the
+    # one-sided form, 'r1' the zero-centred one on the real images; the penalty runs every grad_pen_interval-th iteration with that many
+    # times the weight
+    if g['grad_pen_mode'] not in ('gp', 'lp', 'r1'):
+        raise ValueError(f"grad_pen_mode={g['grad_pen_mode']!r} must be one of 'gp', 'lp', 'r1'")
+    if isinstance(g['grad_pen_interval'], bool) or not (isinstance(g['grad_pen_interval'], int) and g['grad_pen_interval'] >= 1):
+        raise ValueError(f"grad_pen_interval={g['grad_pen_interval']!r} must be an integer >= 1")
+    if (g['grad_pen_mode'] != 'gp' or g['grad_pen_interval'] != 1) and g['wgan']:
+        raise ValueError("grad_pen_mode / grad_pen_interval other than 'gp' / 1 are not available for the WGAN nets (wgan=True)")
     if g['pggan']:
         err_msg = 'The number of layers in the generator and discriminator must match.'
         assert len(g['N_gen_features']) == len(g['N_dis_features']), err_msg

@@ -72,6 +72,10 @@ class DiffAugmentHook:
     def penalty_pair(self, real, x_tilde):
         return self.transform(real, self.real, self.geo_real), self.transform(x_tilde, self.tilde, self.geo_tilde)
 
+    def real_only(self, real):
+        """T(real) alone: what the zero-centred penalty (D_grad_pen_loss, mode "r1") differentiates at -- the reals as the critic sees them"""
+        return self.transform(real, self.real, self.geo_real)
+
     def generated(self, fake):
         if self.geo_gen is not None:
             fake = ops.DiffGeometry.apply(fake, self.geo_gen, self.fill)
@@ -201,12 +205,24 @@ class G_LS_module(nn.Module):
         return G_loss, z_latent
 
 
+PENALTY_MODES = ("gp", "lp", "r1")      # D_grad_pen_loss(mode=)
+
+
 class D_grad_pen_loss(nn.Module):
-    def __init__(self, generator_net, discriminator_net, Lambda):
+    """mode "gp": the reference's two-sided penalty Lambda * mean((||grad D(x_hat)|| - 1)^2) on interpolates (loss_functions.py:148-180).
+    "lp": the one-sided form on the same interpolates, Lambda * mean(max(0, ||grad D(x_hat)|| - 1)^2) (WGAN-LP, Petzka et al. 2018).
+    "r1": (Lambda / 2) * mean(||grad D(x)||^2) at the real images alone (Mescheder et al. 2018) -- no latent, no generator pass, no
+    epsilon and no interpolate: `z`, `x_tilde` and `epsilon` are accepted and ignored; with an `augment` hook the gradient is taken at
+    the augmented reals, the ones the critic's loss sees (`real_only`)."""
+
+    def __init__(self, generator_net, discriminator_net, Lambda, mode="gp"):
         super().__init__()
+        if mode not in PENALTY_MODES:
+            raise ValueError(f"mode must be one of {list(PENALTY_MODES)}, got {mode!r}")
         self.generator_net = generator_net
         self.discriminator_net = discriminator_net
         self.Lambda = Lambda
+        self.mode = mode
         self.last_grad_norms = None  # per-sample |grad D| of the last call (monitoring / parity tests)
         self._ones_cache = None
 
@@ -220,6 +236,8 @@ class D_grad_pen_loss(nn.Module):
             # the reference returns the integer CPU scalar torch.tensor(0) here (loss_functions.py:179), which only survives being
             # stacked / accumulated with device tensors by accident; same value, on the images' device
             return torch.zeros((), device=real_images.device)
+        if self.mode == "r1":
+            return self._forward_r1(real_images, augment)
         batch_size, device = real_images.size(0), real_images.device
         if x_tilde is None:
             z_latent = _latents(self.generator_net, batch_size, device, z)
@@ -236,6 +254,22 @@ class D_grad_pen_loss(nn.Module):
         # (inputs_only: x_hat is the only input asked for, so the critic's weight gradients of this pass would be thrown away)
         with ops.inputs_only():
             Disc_grad = torch.autograd.grad(outputs=output, inputs=x_hat, grad_outputs=self._ones(output), create_graph=True)[0]
-        penalty, norms = ops.GradPenaltyHead.apply(Disc_grad, float(self.Lambda))
+        if self.mode == "lp":
+            penalty, norms = ops.PenaltyHead.apply(Disc_grad, float(self.Lambda), ops.PENALTY_ONE_SIDED)
+        else:
+            penalty, norms = ops.GradPenaltyHead.apply(Disc_grad, float(self.Lambda))
+        self.last_grad_norms = norms.detach()
+        return penalty
+
+    def _forward_r1(self, real_images, augment):
+        # a critic pass of its own over the reals (the critic's loss shares no graph node with it: the trainer runs the two backwards one
+        # after the other).  Without a hook a detached alias is the leaf, so the caller's tensor keeps its requires_grad as it was; the
+        # hook's output is a fresh tensor (a view of the step's buffer in the trainer's hook: the alias keeps the buffer untouched)
+        x = real_images if augment is None else augment.real_only(real_images)
+        x = x.detach().requires_grad_()
+        output = self.discriminator_net(x)
+        with ops.inputs_only():
+            Disc_grad = torch.autograd.grad(outputs=output, inputs=x, grad_outputs=self._ones(output), create_graph=True)[0]
+        penalty, norms = ops.PenaltyHead.apply(Disc_grad, float(self.Lambda), ops.PENALTY_ZERO_CENTRED)
         self.last_grad_norms = norms.detach()
         return penalty

@@ -1631,6 +1631,42 @@ class GradPenaltyHead(Function):
         return out, None
 
 
+PENALTY_ONE_SIDED, PENALTY_ZERO_CENTRED = 1, 2      # the `form` of include/ngan_penalty.h
+
+
+class PenaltyHead(Function):
+    """(Lambda * mean_b(phi(||g_b||_2)), norms) of the critic's input gradient g under the forms of include/ngan_penalty.h:
+    form 1, one-sided, phi(n) = max(0, n - 1)^2 (Petzka et al. 2018); form 2, zero-centred, phi(n) = n^2 / 2 (R1, Mescheder et al.
+    2018).  Two launches forward, one backward: the backward scales g's rows by 2 Lambda (n_b - 1) / (B n_b) where n_b > 1 and
+    writes zeros elsewhere (form 1), or by Lambda / B (form 2).  The reference's two-sided form is GradPenaltyHead."""
+
+    @staticmethod
+    def forward(ctx, g, lam, form):
+        ctx.set_materialize_grads(False)
+        g = _c(g)
+        b = g.shape[0]
+        norms = torch.empty(b, device=g.device, dtype=torch.float32)
+        ws = torch.empty(64 * b, device=g.device, dtype=torch.float32)
+        out = torch.empty((), device=g.device, dtype=torch.float32)
+        _C.call("ngan_penalty_head", g, b, g.numel() // b, int(form), float(lam), ws, norms, out)
+        ctx.save_for_backward(g, norms)
+        ctx.cfg = (int(form), float(lam))
+        ctx.mark_non_differentiable(norms)
+        return out, norms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gp, _gn):
+        g, norms = ctx.saved_tensors
+        if gp is None:
+            return None, None, None
+        form, lam = ctx.cfg
+        b = g.shape[0]
+        out = torch.empty_like(g)
+        _C.call("ngan_penalty_bwd", g, norms, b, g.numel() // b, form, lam, _c(gp), out)
+        return out, None, None
+
+
 def latent_normalize_(z, clamp=5.0):
     """in place: rows of normal draws -> clamp(-5, 5) -> unit L2 norm (reference utils.py:77-78); one launch"""
     _C.call("ngan_latent_normalize", z, z.shape[0], z.shape[1], float(clamp))

@@ -27,7 +27,7 @@ import torch.distributed as dist
 
 from . import _C, ops, wgan_ops
 from .launch import check_sharding, epoch_batches, longest_share, shard_bounds
-from .loss_functions import D_LS_module, D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_LS_module, G_W_loss
+from .loss_functions import PENALTY_MODES, D_LS_module, D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_LS_module, G_W_loss
 from .metric_table import METRICS, settings
 from .scoring import (score_branches, score_due, score_morph, score_msssim, score_sholl, score_skeleton,  # noqa: F401
                       score_spectrum, score_swd)
@@ -380,7 +380,21 @@ def _check_ema_beta(ema_beta):
     return float(ema_beta)
 
 
-DIFFAUG_ROWS = 16384   # rows of a trainer's parameter tables (512 KB, and as much again for the uniforms): n_critic x 3 b + b of them serve an iteration
+def check_grad_pen(mode, interval):
+    """(grad_pen_mode, grad_pen_interval) of the trainer arguments: a mode of loss_functions.PENALTY_MODES and an integer >= 1"""
+    if mode not in PENALTY_MODES:
+        raise ValueError(f"grad_pen_mode must be one of {list(PENALTY_MODES)}, got {mode!r}")
+    if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+        raise ValueError(f"grad_pen_interval must be an integer >= 1, got {interval!r}")
+    return mode, int(interval)
+
+
+def grad_pen_due(iteration, interval):
+    """whether training iteration `iteration` (counted from 0) carries the penalty under lazy regularisation every `interval`"""
+    return int(iteration) % int(interval) == 0
+
+
+DIFFAUG_ROWS = 16384  # rows of a trainer's parameter tables (512 KB, and as much again for the uniforms): n_critic x 3 b + b of them serve an iteration
 
 
 def _check_diffaug(policy, p, seed):
@@ -415,6 +429,9 @@ class _CriticAugment(DiffAugmentHook):
     def penalty_pair(self, real, x_tilde):
         b = real.size(0)
         return self._buf[:b], self._buf[2 * b:3 * b]
+
+    def real_only(self, real):
+        return self._buf[:real.size(0)]
 
 
 class _DiffAugTables:
@@ -820,7 +837,8 @@ class PGGANTrainer(_Trainer):
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
-                 rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, objective="wasserstein"):
+                 rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, objective="wasserstein",
+                 grad_pen_mode="gp", grad_pen_interval=1):
         """optimizer: "adam" -- optim.Adam(params, lr, betas=(beta1, 0.999)), the reference's default -- or "rmsprop" --
         optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps), what the reference's RMSprop switch selects (train.py:220-225);
         beta1 only matters for Adam
@@ -838,9 +856,18 @@ class PGGANTrainer(_Trainer):
         objective: "wasserstein" -- the reference's loop, D_W_loss / G_W_loss with the drift term -- or "lsgan" -- the least-squares
         losses the reference ships and never calls (loss_functions.D_LS_loss / G_LS_loss); drift_epsilon does
         not enter them.  Either way the penalty is added when grad_pen_lambda > 0, as the reference's loop adds it to whatever
-        D_loss is (train.py:361-362)."""
+        D_loss is (train.py:361-362).
+        grad_pen_mode: the penalty's form (loss_functions.D_grad_pen_loss): "gp" -- the reference's two-sided
+        penalty on interpolates; "lp" -- the one-sided form on the same interpolates; "r1" -- (lambda / 2) mean ||grad D(x)||^2 at the
+        real images as the critic sees them: the D step's generator pass then runs on b latents, not 2 b, and z_gp / eps are ignored.
+        grad_pen_interval: k >= 1 -- lazy regularisation (Karras et al. 2020): the penalty pass runs in the iterations whose count
+        `grad_pen_iteration` is a multiple of k, with weight k * grad_pen_lambda, and not at all in the others (no latents, no
+        launches; D_grad_pen is then the zero scalar of the lambda = 0 path).  train_iteration, replay and step advance the count;
+        d_step / d_compute on their own read the phase as it stands; capture() leaves it where it was.  With k > 1 the graphs are
+        kept per phase (`_graph_key`)."""
         if objective not in OBJECTIVES:
             raise ValueError(f"objective must be one of {list(OBJECTIVES)}, got {objective!r}")
+        grad_pen_mode, grad_pen_interval = check_grad_pen(grad_pen_mode, grad_pen_interval)
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
         ema_beta = _check_ema_beta(ema_beta)
@@ -865,7 +892,13 @@ class PGGANTrainer(_Trainer):
         else:
             self.d_loss = D_W_loss(generator, discriminator, drift_epsilon=drift_epsilon, check_nan=False)
             self.g_loss = G_W_loss(generator, discriminator, check_nan=False)
-        self.gp_loss = D_grad_pen_loss(generator, discriminator, Lambda=grad_pen_lambda)
+        self.grad_pen_mode, self.grad_pen_interval = grad_pen_mode, grad_pen_interval
+        self._phase_held = False        # capture(): its warm-up iterations and the capture itself leave the count where it was
+        self.grad_pen_iteration = 0     # host count of training iterations, the same on every rank: due when a multiple of the interval
+        if grad_pen_mode == "gp" and grad_pen_interval == 1:
+            self.gp_loss = D_grad_pen_loss(generator, discriminator, Lambda=grad_pen_lambda)
+        else:
+            self.gp_loss = D_grad_pen_loss(generator, discriminator, Lambda=grad_pen_lambda * grad_pen_interval, mode=grad_pen_mode)
         self.stem = None
         self._stem_grad_skipped = self._stem_sink_active = self._stem_for_exchange = False
         if self.world > 1:
@@ -907,6 +940,32 @@ class PGGANTrainer(_Trainer):
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
             return
         self._aug.prepare(b, self.n_critic, self.G.image_size, tables)
+
+    # ---- lazy regularisation ------------------------------------------------------------------------------------
+    @property
+    def penalty_due(self):
+        """whether a critic step taken now runs the penalty pass: lambda > 0 and `grad_pen_iteration` is a multiple of the interval"""
+        return self.gp_loss.Lambda > 0 and grad_pen_due(self.grad_pen_iteration, self.grad_pen_interval)
+
+    def _graph_key(self, shape, global_batch=None):
+        """with an interval above 1 (and a penalty at all) the graphs of the due and of the other iterations are different graphs: the
+        key carries the phase as it stands; with interval 1 it is the base class's key"""
+        key = super()._graph_key(shape, global_batch)
+        if self.grad_pen_interval > 1 and self.gp_loss.Lambda > 0:
+            key = key + ("penalty", self.penalty_due)
+        return key
+
+    def _advance_penalty_phase(self):
+        if not self._phase_held:
+            self.grad_pen_iteration += 1
+
+    @contextlib.contextmanager
+    def _penalty_phase_held(self):
+        held, self._phase_held = self._phase_held, True
+        try:
+            yield
+        finally:
+            self._phase_held = held
 
     def enable_stem_exchange(self, for_exchange=True):
         """Exchange the stem's gradient as gathered factors; the all-reduce then skips its segment of the flat buffer."""
@@ -973,9 +1032,11 @@ class PGGANTrainer(_Trainer):
         self.flat_d.zero_grad()  # Discriminator_net.zero_grad(), train.py:357
         # the two detached generator passes of the D step (loss_functions.py:26, 167) run as one batch-2b pass; with the penalty
         # switched off (Lambda = 0, the reference CLI's default) the reference draws no second latent batch, and neither does this
-        with_gp = self.gp_loss.Lambda > 0
+        # (lazy regularisation: nor does an iteration that is not due; the zero-centred form needs no generated image at all)
+        penalised = self.penalty_due
+        with_gp = penalised and self.grad_pen_mode != "r1"
         with torch.no_grad():
-            if z_d is None and z_gp is None and self.device_latents:
+            if (z_d is None and (z_gp is None or not with_gp)) and self.device_latents:
                 zz = self._latent((2 if with_gp else 1) * b, None)      # both latent batches in one draw: no concatenation
             else:
                 zs = [self._latent(b, z_d)] + ([self._latent(b, z_gp)] if with_gp else [])
@@ -990,7 +1051,10 @@ class PGGANTrainer(_Trainer):
                                   geo_fake=cut(self._aug.geo_fake(self._aug_step, b)))
             hook.prepare(real, fakes)
         loss, s_real, s_fake = self.d_loss(real, fake_images=fakes[:b], augment=hook)  # train.py:358
-        gp = self.gp_loss(real, x_tilde=fakes[b:] if with_gp else None, epsilon=eps, augment=hook if with_gp else None)  # train.py:361
+        if penalised or not self.gp_loss.Lambda > 0:
+            gp = self.gp_loss(real, x_tilde=fakes[b:] if with_gp else None, epsilon=eps, augment=hook if penalised else None)  # train.py:361
+        else:
+            gp = torch.zeros((), device=real.device)      # not due: what the penalty object returns for Lambda = 0
         # train.py:362, 365: D_loss += gp; D_loss.backward().  The two terms share no graph node (separate critic passes), so the sum's
         # backward is the two backwards; they run one after the other so that every critic parameter receives its contributions in
         # a fixed order (penalty terms, then the W-loss term): autograd's node order inside ONE run over both graphs is not
@@ -1082,6 +1146,7 @@ class PGGANTrainer(_Trainer):
         if self.n_critic == 0:          # adaptive critic schedule chose no critic step: losses for monitoring only (train.py:369-372)
             stats.update(self.d_compute(real, z_d, z_gp, eps, global_batch))
         stats.update(self.g_step(real, z_g, global_batch))
+        self._advance_penalty_phase()
         return stats
 
     def capture(self, real_example, warmup=1, draws=None, global_batch=None, tables=None):
@@ -1115,8 +1180,9 @@ class PGGANTrainer(_Trainer):
         self._set_share(static_real.size(0), global_batch)     # the write stays outside the captures
         n_packed_before = ops.registry_size()
         lr_g, lr_d = self.opt_g.param_groups[0]["lr"], self.opt_d.param_groups[0]["lr"]
-        self._warm_up_on_snapshot(lambda: self.train_iteration(static_real, *d_args, z_g, global_batch, tables), warmup,
-                                  (self._aug.generator,) if self._aug is not None else ())
+        with self._penalty_phase_held():       # every warm-up iteration runs in the phase that is being captured
+            self._warm_up_on_snapshot(lambda: self.train_iteration(static_real, *d_args, z_g, global_batch, tables), warmup,
+                                      (self._aug.generator,) if self._aug is not None else ())
         assert (lr_g, lr_d) == (self.opt_g.param_groups[0]["lr"], self.opt_d.param_groups[0]["lr"])
         ops.bump_weight_epoch()   # the warm-up registered every packed weight (persistent buffers, allocated outside capture):
         self.opt_d.repack()       # rebuild both re-pack tables now (from the restored parameters), so that the captured Adam
@@ -1141,7 +1207,7 @@ class PGGANTrainer(_Trainer):
         # watchdog terminates the process); thread_local polices the capturing thread only.  The second rule (an event whose stream
         # is part of the capture) is what _on_comm_stream takes care of.  Both reproduced case by case: tools/capture_event_probe.py.
         mode = "thread_local" if self._comm_stream is not None else "global"
-        with _collector_off():
+        with _collector_off(), self._penalty_phase_held():
             graphs, stats = self._capture_segments(segmented, mode, static_real, d_args, z_g, global_batch)
         # Two things the captured launches reference besides the static input: (a) the stem's factor tensors (`StemGradExchange.sink`
         # ran during THIS capture; another shape's capture overwrites stem.captured, and the eager `finish()` between replayed
@@ -1197,7 +1263,17 @@ class PGGANTrainer(_Trainer):
             graphs[1].replay()
             self._exchange(self.flat_g)
             graphs[2].replay()
+        self._advance_penalty_phase()
         return stats
+
+    def _entry_for(self, real, global_batch=None):
+        if real is None and self._entry is not None and self.grad_pen_interval > 1 and self.gp_loss.Lambda > 0:
+            # the most recently captured shape, in the phase of the moment (each phase's graphs have a static input of their own)
+            entry = self._graphs.get(self._graph_key(self._entry[1].shape, global_batch))
+            if entry is None:
+                raise RuntimeError("no graphs captured for this phase of grad_pen_interval: " + self._NO_GRAPH)
+            return entry
+        return super()._entry_for(real, global_batch)
 
     def step(self, real, use_graph=True, global_batch=None):
         """train on one batch: graph replay when possible (capturing on first sight of a shape), else eager"""
@@ -1250,9 +1326,13 @@ class WGANTrainer(_Trainer):
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, drift_epsilon=0.001, n_critic=1, clip=0.01,
                  optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None, sync_batchnorm=False,
-                 ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0):
+                 ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, grad_pen_mode="gp", grad_pen_interval=1):
         """ema_beta: as PGGANTrainer's -- the averaged generator's parameters; its BatchNorm buffers stay the live ones
-        diffaug: must be empty -- differentiable augmentation is built for the PGGAN trainer only"""
+        diffaug: must be empty -- differentiable augmentation is built for the PGGAN trainer only
+        grad_pen_mode, grad_pen_interval: must be the defaults -- this loop clips weights and has no penalty"""
+        if grad_pen_mode != "gp" or isinstance(grad_pen_interval, bool) or grad_pen_interval != 1:
+            raise ValueError(f"grad_pen_mode={grad_pen_mode!r}, grad_pen_interval={grad_pen_interval!r}: the WGAN nets are trained with "
+                             f"weight clipping, without a gradient penalty (PGGANTrainer only)")
         if ops.diffaug_policy_mask(diffaug):
             raise ValueError(f"diffaug={diffaug!r}: differentiable augmentation is not available for the WGAN nets (PGGANTrainer only)")
         if optimizer not in OPTIMIZERS:
@@ -1851,6 +1931,10 @@ def build_arg_parser():
                                                                         'reference\'s D_LS_loss / G_LS_loss) instead of the Wasserstein one')
     p.add_argument('--mbstd_group', type=int, default=0, help='group size of a minibatch standard-deviation channel in the PG '
                                                               'critic\'s head (Karras et al. 2018 use 4); 0: off')
+    p.add_argument('--grad_pen_mode', type=str, default='gp', choices=list(PENALTY_MODES),
+                   help='form of the gradient penalty: gp, the two-sided one on interpolates; lp, one-sided; r1, zero-centred on the reals')
+    p.add_argument('--grad_pen_interval', type=int, default=1, help='apply the penalty every K-th iteration with K times the weight '
+                                                                    '(lazy regularisation); 1: every iteration')
     for m in METRICS:                                                    # one group of integer flags per checkpoint metric
         for name, _, default, text in settings(m):
             p.add_argument('--' + name, type=int, default=default, help=text)
@@ -1890,6 +1974,7 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     """The trainer `main()` trains with: RMSprop when config.RMSprop is set, else Adam with betas (beta1, 0.999) (train.py:220-225).
     wgan without pggan: a WGANTrainer (weight clipping at 0.01, reference train.py:489-490); wgan with pggan is refused.
     config.lsgan: the PG trainer's objective is "lsgan" instead of "wasserstein" (refused for the WGAN nets).
+    config.grad_pen_mode / config.grad_pen_interval: the PG trainer's penalty form and lazy-regularisation interval (likewise refused).
     distributed: a launched rank -- the trainer exchanges over `process_group` (None: the default group); the WGAN nets then train
     with synchronised BatchNorm."""
     if config.wgan and config.pggan:
@@ -1897,11 +1982,15 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     aug = dict(diffaug=getattr(config, 'diffaug', ''), diffaug_p=getattr(config, 'diffaug_p', 1.0),
                diffaug_seed=getattr(config, 'diffaug_seed', 0))
     lsgan = bool(getattr(config, 'lsgan', False))
+    pen = (getattr(config, 'grad_pen_mode', 'gp'), getattr(config, 'grad_pen_interval', 1))
     if config.wgan:
         if lsgan:
             raise ValueError("lsgan=True is not available for the WGAN nets (wgan=True, pggan=False)")
         if getattr(config, 'mbstd_group', 0):
             raise ValueError("mbstd_group > 0 is not available for the WGAN nets (wgan=True, pggan=False)")
+        if pen != ("gp", 1):
+            raise ValueError("grad_pen_mode / grad_pen_interval other than 'gp' / 1 are not available for the WGAN nets (wgan=True, "
+                             "pggan=False): that loop clips weights")
         kw = dict(learning_rate=config.learning_rate, drift_epsilon=config.drift_epsilon, n_critic=config.n_critic, device_latents=True,
                   process_group=process_group, sync_batchnorm=bool(distributed), ema_beta=getattr(config, 'ema_beta', 0.0), **aug)
         if config.RMSprop:
@@ -1912,6 +2001,8 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
               ema_beta=getattr(config, 'ema_beta', 0.0), **aug)
     if lsgan:
         kw["objective"] = "lsgan"
+    if pen != ("gp", 1):                # (the defaults are left to the trainer, like the objective's)
+        kw["grad_pen_mode"], kw["grad_pen_interval"] = pen
     if config.RMSprop:
         return PGGANTrainer(G, D, optimizer="rmsprop", **kw)
     return PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)

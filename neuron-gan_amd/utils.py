@@ -46,7 +46,8 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # by either side load in the other.  One optional extra key, 'optimizer_state', carries the fused Adam's moments and
 # per-tensor step counts (the reference does not save optimiser state at all).  A trainer that keeps an averaged generator
 # (train.py, `ema_beta`) adds 'Generator_ema_state': the averaged weights under the keys of 'Generator_state', tensors only.  The
-# A PGGANTrainer writes 'objective' ("wasserstein" or "lsgan", train.py `objective=`) beside it; a file without the key is Wasserstein.  A
+# A PGGANTrainer writes 'objective' ("wasserstein" or "lsgan", train.py `objective=`) beside it; a file without the key is Wasserstein.  It
+# also writes 'grad_pen_mode', 'grad_pen_interval' and 'grad_pen_iteration' (PENALTY_KEYS; a file without them is 'gp' / 1 / 0).  A
 # critic built with mbstd_group > 0 lists 'mbstd_group' in 'Discriminator_attrs' and holds 'layers.<k>.weight_std' in its state; a file
 # without the attribute holds the reference's critic.  The
 # reference's loaders read the keys they know and ignore the rest (utils.py:185-199 index five series keys and the two attribute
@@ -94,6 +95,9 @@ def load_checkpoint_dict(filename, device=torch.device('cpu')):
 
 EMA_KEY = 'Generator_ema_state'
 OBJECTIVE_KEY = 'objective'      # of the trainer that wrote the file; a file without it was trained with the Wasserstein objective
+# of a PGGANTrainer's penalty (train.py `grad_pen_mode=`, `grad_pen_interval=`) and its count of iterations; the values of a file without
+# the keys
+PENALTY_KEYS = {'grad_pen_mode': 'gp', 'grad_pen_interval': 1, 'grad_pen_iteration': 0}
 SWD_KEY, MSSSIM_KEY, SPECTRUM_KEY, MORPH_KEY, SKELETON_KEY, SHOLL_KEY, BRANCH_KEY = (m.key for m in METRICS)
 
 
@@ -135,6 +139,9 @@ class Checkpointer:
                 checkpoint_dict[EMA_KEY] = cpu(self.trainer.ema_state())
             if hasattr(self.trainer, 'objective'):
                 checkpoint_dict[OBJECTIVE_KEY] = self.trainer.objective
+            if hasattr(self.trainer, 'grad_pen_mode'):
+                for key, default in PENALTY_KEYS.items():
+                    checkpoint_dict[key] = type(default)(getattr(self.trainer, key))
         for m in METRICS:
             if getattr(self, m.key):
                 checkpoint_dict[m.key] = [dict(entry) for entry in getattr(self, m.key)]
@@ -156,6 +163,12 @@ class Checkpointer:
             if saved != self.trainer.objective:
                 raise ValueError('{} was trained with the {} objective and cannot be resumed with the {} objective'.format(
                     source, saved, self.trainer.objective))
+        if filename is None and hasattr(self.trainer, 'grad_pen_mode'):
+            saved = tuple(checkpoint_dict.get(k, PENALTY_KEYS[k]) for k in ('grad_pen_mode', 'grad_pen_interval'))
+            own = (self.trainer.grad_pen_mode, self.trainer.grad_pen_interval)
+            if saved != own:
+                raise ValueError('{} was trained with grad_pen_mode={}, grad_pen_interval={} and cannot be resumed with grad_pen_mode={}, '
+                                 'grad_pen_interval={}'.format(source, saved[0], saved[1], own[0], own[1]))
         # the critic's minibatch standard-deviation group (models.Discriminator_PG(mbstd_group=); a file without the key is 0, off) changes
         # the head's parameters and its equalised-LR constant: the file's weights mean something else under another value
         saved_group = int(checkpoint_dict.get('Discriminator_attrs', {}).get('mbstd_group', 0))
@@ -200,6 +213,9 @@ class Checkpointer:
                     # the reference never restores an optimiser (utils.py:213-215): start this one fresh, as it would
                     self.trainer.reset_optimizer_state()
                     print('{} holds {} state; the {} optimiser starts fresh'.format(source, saved_kind, self.trainer.optimizer_kind))
+            if filename is None and hasattr(self.trainer, 'grad_pen_mode'):
+                # a resumed run continues the lazy-regularisation schedule where it stopped (a weights-only load restarts it)
+                self.trainer.grad_pen_iteration = int(checkpoint_dict.get('grad_pen_iteration', PENALTY_KEYS['grad_pen_iteration']))
             if getattr(self.trainer, 'ema_enabled', False):
                 self.trainer.load_ema_state(checkpoint_dict.get(EMA_KEY, {}))
                 if EMA_KEY not in checkpoint_dict:
