@@ -7,75 +7,97 @@
 
 namespace {
 
-constexpr int BCH = 16;  // batch rows handled per block
+constexpr int BCH = 16;  // batch rows per MFMA tile (one accumulator)
+constexpr int FWD_NW = 8;  // waves per block of the stem forward: two per SIMD
 
-// One block per output pixel p and batch chunk of 16.  out[b][c] = sum_k z[b][k] * W[c*S + p][k] is a 16 x C x K GEMM:
-// v_mfma_f32_16x16x4_f32 with A = z (16 samples x 4 k, from LDS) and B = W^T (4 k x 16 weight rows, streamed from HBM
+// One block per output pixel p and batch chunk of NCH * 16.  out[b][c] = sum_k z[b][k] * W[c*S + p][k] is a 16 x C x K GEMM per 16
+// samples: v_mfma_f32_16x16x4_f32 with A = z (16 samples x 4 k, from LDS) and B = W^T (4 k x 16 weight rows, streamed from HBM
 // straight into registers, 16 B per lane; the k-order inside a 16-wide group is permuted identically on both operands).
 // The accumulator holds sample 4q+r of weight row (channel) l & 15; LeakyReLU + PixelNorm over the C channels of the
 // pixel then go through LDS.
-template <typename T>
-__global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict__ z, const float* __restrict__ Wt,
-                                                         T* __restrict__ y, float* __restrict__ rn, int B, int K,
-                                                         int S, int C, float scale, float slope, float eps) {
+// NCH = 2 (B > 16: the D step runs its two detached generator passes as one batch of 32): a weight fragment is read ONCE and feeds one
+// accumulator per 16-sample chunk -- each accumulator sees the MFMA sequence over k it would see alone, so a sample's bits do not
+// depend on B -- instead of one pass over the 67 MB weight per chunk.
+// Eight waves, a channel tile each at C = 128, and the loads of the next k-steps in flight behind the MFMAs of the current ones:
+// with four waves that each loaded 16 fragments, waited, and ran 64 dependent MFMAs, nothing was in flight during the MFMAs and no
+// MFMA ran during the wait (256 blocks, one per CU: 23.9 us at B = 16 against 12 us for one pass at HBM rate).
+template <typename T, int NCH>
+__global__ __launch_bounds__(FWD_NW * 64) void linear_fwd_kernel(const float* __restrict__ z, const float* __restrict__ Wt,
+                                                                 T* __restrict__ y, float* __restrict__ rn, int B, int K,
+                                                                 int S, int C, float scale, float slope, float eps) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     // rows of K + 4 floats: the 16 lanes of a ds_read_b128 phase read 16 different samples at the same k, and a pitch of
     // K floats would put all of them in the same banks (16-way conflict)
+    constexpr int ROWS = NCH * BCH, NT = FWD_NW * 64;
     const int ZP = K + 4, CP = C + 4;
-    float* z_l = sm;                 // BCH * ZP   (row b, k contiguous)
-    float* out_l = sm + BCH * ZP;    // BCH * CP
-    float* r_l = out_l + BCH * CP;   // BCH
+    float* z_l = sm;                  // ROWS * ZP   (row b, k contiguous)
+    float* out_l = sm + ROWS * ZP;    // ROWS * CP
+    float* r_l = out_l + ROWS * CP;   // ROWS
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, q = lane >> 4;
-    const int p = blockIdx.x, b0 = blockIdx.y * BCH;
-    const int nb = min(BCH, B - b0);
-    for (int bb = tid >> 4; bb < BCH; bb += 16)
+    const int p = blockIdx.x, b0 = blockIdx.y * ROWS;
+    const int nb = min(ROWS, B - b0);
+    const int ntile = (C + 15) >> 4, ksteps = K >> 4;
+    // the weight row is read once from HBM: keep UNR 16-byte loads per lane in flight (one load per MFMA group left the
+    // wave waiting a full memory round trip every 4 MFMAs: 45 us for the 67 MB default stem instead of ~15).  A ring: the
+    // fragment of k-step s + UNR is requested into the registers of step s as soon as that step's MFMAs are issued, so the UNR
+    // loads stay in flight behind the MFMAs (straight-line code between the loads and their use: the compiler's wait counts are
+    // exact; a load under a condition made every wait a full drain)
+    constexpr int UNR = 16;
+    const int ngroup = ksteps / UNR;
+    for (int bb = tid >> 4; bb < ROWS; bb += NT / 16)
         for (int k = (tid & 15) * 4; k < K; k += 64) {
             const float4 v = bb < nb ? ld4(z + (long)(b0 + bb) * K + k) : f4zero();
             st4(z_l + bb * ZP + k, f4scale(v, scale));                            // weight_scale * x, models.py:241
         }
     __syncthreads();
-    const int ntile = (C + 15) >> 4, ksteps = K >> 4;
-    for (int ct = wave; ct < ntile; ct += 4) {
+    for (int ct = wave; ct < ntile; ct += FWD_NW) {
         const int c = ct * 16 + j;
         const float* wrow = Wt + ((long)min(c, C - 1) * S + p) * K + q * 4;
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // the weight row is read once from HBM: keep UNR 16-byte loads per lane in flight (one load per MFMA group left the
-        // wave waiting a full memory round trip every 4 MFMAs: 45 us for the 67 MB default stem instead of ~15)
-        constexpr int UNR = 16;
-        int s = 0;
-        for (; s + UNR <= ksteps; s += UNR) {
+        f32x4 acc[NCH];
+#pragma unroll
+        for (int h = 0; h < NCH; ++h) acc[h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        auto step = [&](const float4& wv, int s) {          // k-step s on every chunk's accumulator, from the same weight registers
+#pragma unroll
+            for (int h = 0; h < NCH; ++h) {
+                const float4 zv = ld4(z_l + (h * BCH + j) * ZP + s * 16 + q * 4);       // z[sample 16h + j][16 s + 4q .. +3]
+                acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.x, wv.x, acc[h], 0, 0, 0);
+                acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.y, wv.y, acc[h], 0, 0, 0);
+                acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.z, wv.z, acc[h], 0, 0, 0);
+                acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.w, wv.w, acc[h], 0, 0, 0);
+            }
+        };
+        if (ngroup > 0) {
             float4 wv[UNR];
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) wv[u] = ld4(wrow + (s + u) * 16);     // W[row c][16(s+u) + 4q .. +3]
+            for (int u = 0; u < UNR; ++u) wv[u] = ld4(wrow + u * 16);                  // W[row c][16 u + 4q .. +3]
+            for (int g = 0; g + 1 < ngroup; ++g) {
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const float4 zv = ld4(z_l + j * ZP + (s + u) * 16 + q * 4);       // z[sample j][16(s+u) + 4q .. +3]
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.x, wv[u].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.y, wv[u].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.z, wv[u].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.w, wv[u].w, acc, 0, 0, 0);
+                for (int u = 0; u < UNR; ++u) {
+                    step(wv[u], g * UNR + u);
+                    __builtin_amdgcn_sched_barrier(0);      // (the scheduler otherwise sinks all UNR requests below the last MFMA)
+                    wv[u] = ld4(wrow + ((g + 1) * UNR + u) * 16);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) step(wv[u], (ngroup - 1) * UNR + u);
         }
-        for (; s < ksteps; ++s) {
-            const float4 wv = ld4(wrow + s * 16);
-            const float4 zv = ld4(z_l + j * ZP + s * 16 + q * 4);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.x, wv.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.y, wv.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.z, wv.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zv.w, wv.w, acc, 0, 0, 0);
-        }
+        for (int s = ngroup * UNR; s < ksteps; ++s) step(ld4(wrow + s * 16), s);
         if (c < C) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float v = acc[r];
-                out_l[(4 * q + r) * CP + c] = v > 0.f ? v : slope * v;
-            }
+            for (int h = 0; h < NCH; ++h)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = acc[h][r];
+                    out_l[(h * BCH + 4 * q + r) * CP + c] = v > 0.f ? v : slope * v;
+                }
         }
     }
     __syncthreads();
-    {   // PixelNorm over the C channels of each sample: 16 lanes per sample
-        const int bb = tid >> 4, part = tid & 15;
+    // PixelNorm over the C channels of each sample: 16 lanes per sample
+    for (int bb = tid >> 4; bb < ROWS; bb += NT / 16) {
+        const int part = tid & 15;
         float ss = 0.f;
         for (int c = part; c < C; c += 16) ss = fmaf(out_l[bb * CP + c], out_l[bb * CP + c], ss);
         ss = group_sum<16>(ss);
@@ -86,7 +108,7 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
         }
     }
     __syncthreads();
-    for (int bb = tid >> 4; bb < nb; bb += 16) {
+    for (int bb = tid >> 4; bb < nb; bb += NT / 16) {
         const float inv = 1.0f / r_l[bb];
         for (int c = tid & 15; c < C; c += 16) sta1(y + ((long)(b0 + bb) * S + p) * C + c, out_l[bb * CP + c] * inv);
     }
@@ -369,14 +391,25 @@ static int linear_fwd_impl(const float* z, const float* Wt, T* y, float* rnorm, 
     NGAN_REQUIRE(B > 0 && K > 0 && K % 16 == 0 && S > 0 && C > 0, NGAN_ERR_SHAPE, "linear_lrelu_pn_fwd: B=%d K=%d (multiple of 16) S=%d C=%d unsupported",
                  B, K, S, C);
     NGAN_REQUIRE(K % 4 == 0, NGAN_ERR_SHAPE, "linear_lrelu_pn_fwd: K=%d must be a multiple of 4", K);
-    const size_t lds = (size_t)(BCH * (K + 4) + BCH * (C + 4) + BCH) * sizeof(float);
-    NGAN_REQUIRE(lds <= 160 * 1024, NGAN_ERR_SHAPE, "linear_lrelu_pn_fwd: K=%d C=%d need %zu B of LDS", K, C, lds);
-    if (lds > 64 * 1024) {      // wide stems (the 1024-channel presets): more than the default dynamic-LDS limit of a launch
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_fwd_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t lds1 = (size_t)(BCH * (K + 4) + BCH * (C + 4) + BCH) * sizeof(float);
+    NGAN_REQUIRE(lds1 <= 160 * 1024, NGAN_ERR_SHAPE, "linear_lrelu_pn_fwd: K=%d C=%d need %zu B of LDS", K, C, lds1);
+    // two 16-sample chunks per block (one pass over the weight for 32 samples) where B has a second chunk and the LDS holds both;
+    // a larger B, or a wide stem with B > 16, walks chunks of that size through grid.y
+    const int nch = B > BCH && 2 * lds1 <= 160 * 1024 ? 2 : 1;
+    const size_t lds = nch * lds1;
+    const void* fn = nch == 2 ? reinterpret_cast<const void*>(linear_fwd_kernel<T, 2>) : reinterpret_cast<const void*>(linear_fwd_kernel<T, 1>);
+    // wide stems (the 1024-channel presets), or two chunks of the default one: more than the default dynamic-LDS limit of a launch.
+    // Raised once per kernel and device, to the most a launch may ask for: the default D step gets here on every iteration
+    static bool raised[2][64] = {};          // (one array per instantiation of this function, i.e. per storage type)
+    int dev = 0;
+    if (lds > 64 * 1024 && (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !raised[nch - 1][dev])) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         NGAN_REQUIRE(e == hipSuccess, (int)e, "linear_lrelu_pn_fwd: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
+        if (dev >= 0 && dev < 64) raised[nch - 1][dev] = true;
     }
-    hipLaunchKernelGGL(linear_fwd_kernel<T>, dim3(S, ngan::ceil_div(B, BCH)), dim3(256), lds, (hipStream_t)stream, z, Wt, y, rnorm,
-                       B, K, S, C, scale, slope, eps);
+    const dim3 grid(S, ngan::ceil_div(B, nch * BCH)), block(FWD_NW * 64);
+    if (nch == 2) hipLaunchKernelGGL((linear_fwd_kernel<T, 2>), grid, block, lds, (hipStream_t)stream, z, Wt, y, rnorm, B, K, S, C, scale, slope, eps);
+    else hipLaunchKernelGGL((linear_fwd_kernel<T, 1>), grid, block, lds, (hipStream_t)stream, z, Wt, y, rnorm, B, K, S, C, scale, slope, eps);
     return ngan::launch_status("ngan_linear_lrelu_pn_fwd");
 }
 extern "C" int ngan_linear_lrelu_pn_fwd(const float* z, const float* Wt, float* y, float* rnorm, int B, int K, int S, int C,

@@ -495,6 +495,32 @@ __global__ __launch_bounds__(256) void pool2_fwd_v4_kernel(const T* __restrict__
                                      0.25f * ((a.z + b.z) + (c.z + d.z)), 0.25f * ((a.w + b.w) + (c.w + d.w))));
 }
 
+// one-channel images (C == 1, w a multiple of N): a thread takes N = 2 or 4 neighbouring output pixels of a row: N / 2 four-element
+// loads from each of the two image rows, one vector store; i / (w / N) is b * h + Y and the images' rows follow each other, so the
+// source row is 2 * (b * h + Y).  32-bit index arithmetic (the host checks the count).  Same association as the scalar kernel.
+template <typename T, int N>
+__global__ __launch_bounds__(256) void pool2_fwd_img_kernel(const T* __restrict__ x, T* __restrict__ y, int total, int w) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int wn = w / N, r = i / wn, xg = i - r * wn;
+    const T* p = x + (long)2 * r * 2 * w + 2 * N * xg;
+    float o[N];
+#pragma unroll
+    for (int k = 0; k < N / 2; ++k) {
+        const float4 t = lda4(p + 4 * k), u = lda4(p + 2 * w + 4 * k);
+        o[2 * k] = 0.25f * ((t.x + t.y) + (u.x + u.y));
+        o[2 * k + 1] = 0.25f * ((t.z + t.w) + (u.z + u.w));
+    }
+    T* q = y + (long)i * N;
+    if constexpr (N == 4) {
+        sta4(q, make_float4(o[0], o[1], o[2], o[3]));
+    } else if constexpr (sizeof(T) == 2) {
+        *reinterpret_cast<unsigned*>(q) = pack_bf16(o[0], o[1]);
+    } else {
+        *reinterpret_cast<float2*>(q) = make_float2(o[0], o[1]);
+    }
+}
+
 template <typename T>
 __global__ void pool2_adjoint_kernel(const T* __restrict__ gy, T* __restrict__ gx, int B, int h, int w, int C) {
     const long total = (long)B * 4 * h * w * C;
@@ -984,8 +1010,18 @@ extern "C" int ngan_bf16_up2_fwd(const ngan_bf16* a, ngan_bf16* o, int B, int h,
 template <typename T>
 static int launch_up2_adjoint_strip(const T* g, const T* yprev, const float* rn, T* o, int B, int h, int w, int C,
                                     float slope, hipStream_t s) {
-    const int Q = C / 4, YT = h < 16 ? h : 16;
-    const dim3 grid(ceil_div(w, 256 / Q), ceil_div(h, YT), B), block(256);
+    // Strip height by occupancy.  A thread walks its strip's rows one after the other, so a launch with fewer workgroups than the chip
+    // has CUs lasts as long as one 16-row walk (~25 us) whatever the tensor's size.  Keep YT = 16 where the grid has kStripMinWg
+    // workgroups (2 per CU) already; otherwise halve it until it has, down to 2.  A strip re-reads its two lead-in rows (34 rows per 16
+    // outputs, 10 per 4, 6 per 2), hence no further than occupancy needs.  The generator's backward at batch 16:
+    //   16 x 16 x 128: YT 2, 32 -> 256 workgroups     32 x 32 x 64: YT 2, 64 -> 512     64 x 64 x 32: YT 4, 128 -> 512
+    //   128 x 128 x 32 (512) and 256 x 256 x 16 (1024): YT 16 as before.
+    // A thread's arithmetic per output does not depend on where its strip starts: the same bits with every YT.
+    constexpr long kStripMinWg = 2 * 256;
+    const int Q = C / 4, gx = ceil_div(w, 256 / Q);
+    int YT = 16;
+    while (YT > 2 && (long)gx * ceil_div(h, YT) * B < kStripMinWg) YT >>= 1;
+    const dim3 grid(gx, ceil_div(h, YT), B), block(256);
 #define CALL(QV)                                                                                                                   \
     if (yprev) hipLaunchKernelGGL((up2_adjoint_strip_kernel<T, QV, 1>), grid, block, 0, s, g, o, yprev, rn, h, w, slope, YT);        \
     else hipLaunchKernelGGL((up2_adjoint_strip_kernel<T, QV, 0>), grid, block, 0, s, g, o, yprev, rn, h, w, slope, YT)
@@ -1039,6 +1075,10 @@ static int pool2_fwd_impl(const T* a, T* o, int B, int h, int w, int C, void* st
     const long total = (long)B * h * w * C;
     if (C % 4 == 0 && total / 4 < (1L << 31) - 256)
         hipLaunchKernelGGL(pool2_fwd_v4_kernel<T>, dim3(ceil_div(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, a, o, (int)(total / 4), h, w, C / 4);
+    else if (C == 1 && w % 4 == 0 && total / 4 < (1L << 31) - 256)      // the critic's input image
+        hipLaunchKernelGGL((pool2_fwd_img_kernel<T, 4>), dim3(ceil_div(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, a, o, (int)(total / 4), w);
+    else if (C == 1 && w % 2 == 0 && total / 2 < (1L << 31) - 256)
+        hipLaunchKernelGGL((pool2_fwd_img_kernel<T, 2>), dim3(ceil_div(total / 2, 256)), dim3(256), 0, (hipStream_t)stream, a, o, (int)(total / 2), w);
     else
         hipLaunchKernelGGL(pool2_fwd_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, a, o, B, h, w, C);
     return ngan::launch_status("ngan_pool2_fwd");
