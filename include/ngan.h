@@ -246,6 +246,8 @@ int ngan_wloss_head_bwd(const float* scores, int n_real, int n_fake, float drift
 #include "ngan_geoaug.h"
 /* ---- one-sided and zero-centred forms of the gradient penalty (opt-in): declared in ngan_penalty.h, an extension section likewise ---- */
 #include "ngan_penalty.h"
+/* ---- launch plan of the folded critic first block as a host query: declared in ngan_first_block.h, an extension section likewise ---- */
+#include "ngan_first_block.h"
 
 /* ---- latent projection: utils.py:77-78 (clamp(-c, c), L2-normalise each row), in place on (rows, dim) normal draws ---------- */
 int ngan_latent_normalize(float* z, int rows, int dim, float clamp, void* stream);
@@ -358,7 +360,8 @@ int ngan_ema_step(const float* p, float* ema, const long* seg_off, const long* s
  *   p (B,H,W) image (already pooled);  w_conv (N,C,3,3), b_conv (N) or NULL;  wf, bf (C);  y (B,H,W,N), rnorm (B,H,W);
  *   N in {16, 32}, C <= 64
  *   bwd: gw_conv (+)= dL/dW, gwf, gbf, gb_conv (or NULL) from gc = dL/d(pre-activation);  workspace: ngan_first_block_workspace_floats floats
- *   dx:  gx = dL/dp (pool = 0) or its avg-pool adjoint on the (B,2H,2W) image (pool = 1) */
+ *   dx:  gx = dL/dp (pool = 0) or its avg-pool adjoint on the (B,2H,2W) image (pool = 1)
+ *   the three refuse the same shapes (NGAN_ERR_SHAPE), those for which the plan query of ngan_first_block.h does */
 size_t ngan_first_block_table_floats(int N);      /* = 2*9*N: the folded tables A, Bv (written by fwd, read by dx) */
 int ngan_first_block_fwd(const float* p, const float* w_conv, const float* wf, const float* bf, const float* b_conv, float* y,
                          float* rnorm, float* tables, int B, int H, int W, int C, int N, float scale, float slope, float eps,

@@ -177,6 +177,12 @@ PENALTY_SIGNATURES = {
     "ngan_penalty_bwd": [_P, _P, _I, _L, _I, _F, _P, _P, _P],
 }
 
+# include/ngan_first_block.h, the fifth extension section: the launch plan of the folded critic first block as a host query
+# (ops.first_block_fusable); listed by `first_block_symbols`, like the tables above
+FIRST_BLOCK_NON_STATUS = {
+    "ngan_first_block_plan": ([_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)], _I),
+}
+
 NON_STATUS = {
     "ngan_version": ([], ctypes.c_char_p),
     "ngan_last_error": ([], ctypes.c_char_p),
@@ -227,7 +233,7 @@ def lib():
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
-        for name, (argtypes, restype) in list(NON_STATUS.items()) + list(MBSTD_NON_STATUS.items()):
+        for name, (argtypes, restype) in list(NON_STATUS.items()) + list(MBSTD_NON_STATUS.items()) + list(FIRST_BLOCK_NON_STATUS.items()):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -253,6 +259,10 @@ def geoaug_symbols():
 
 def penalty_symbols():
     return list(PENALTY_SIGNATURES)
+
+
+def first_block_symbols():
+    return list(FIRST_BLOCK_NON_STATUS)
 
 
 def mbstd_workspace_doubles(B, H, W, C, G_eff) -> int:
@@ -345,6 +355,14 @@ def wgrad_plan(B, H, W, Cin, Cout, precision=0):
     if lib().ngan_conv3x3_wgrad_plan(B, H, W, Cin, Cout, precision, out) != 0:
         raise RuntimeError(lib().ngan_last_error().decode())
     return tuple(out)
+
+
+def first_block_plan(B, H, W, C, N):
+    """(status, (grid.x, R, nchunk, slabs)) of ngan_first_block_plan: host arithmetic, nothing is launched; status 0 where the three
+    first-block entry points take the shape"""
+    out = (ctypes.c_int * 4)()
+    status = lib().ngan_first_block_plan(B, H, W, C, N, out)
+    return int(status), tuple(out)
 
 
 def wgrad_reduce_many(raw_entries: bytes, n: int):

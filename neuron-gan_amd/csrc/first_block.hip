@@ -254,14 +254,34 @@ bool fb_shape_ok(int B, int H, int W, int C, int N) {
            (long)B * ngan::ceil_div(H, FB_ROWS) < 65536 && (long)B * H * W * N < (1L << 31);
 }
 
-// rows per workgroup of the sums kernel: at most 1024 slabs
-int fb_sums_rows(int B, int H, int gx) {
-    int R = FB_ROWS;
-    while ((long)gx * B * ngan::ceil_div(H, R) > 1024) R *= 2;
-    return R;
+// The launch plan of the family, host arithmetic only.  gx: workgroups along x (256 / (N/4) pixels each; all three kernels);  R: image
+// rows per workgroup of the sums kernel, FB_ROWS doubled until the launch has at most 1024 slabs or one workgroup owns the whole
+// column (ceil(H / R) == 1: doubling further cannot lower the count, so the loop ends whatever gx * B is);  nchunk = ceil(H / R);
+// slabs = gx * B * nchunk.  The forward and image-gradient kernels always walk FB_ROWS rows per workgroup.
+struct FbPlan { int gx, R, nchunk; long slabs; };
+
+int fb_plan(const char* who, int B, int H, int W, int C, int N, FbPlan& pl) {
+    pl = FbPlan{0, 0, 0, 0};
+    NGAN_REQUIRE(fb_shape_ok(B, H, W, C, N), NGAN_ERR_SHAPE,
+                 "%s: B=%d H=%d W=%d C=%d N=%d unsupported (N 16 or 32, C <= 64, < 2^31 output elements)", who, B, H, W, C, N);
+    pl.gx = ngan::ceil_div((long)W * (N / 4), 256);
+    pl.R = FB_ROWS;
+    while ((long)pl.gx * B * ngan::ceil_div(H, pl.R) > 1024 && ngan::ceil_div(H, pl.R) > 1) pl.R *= 2;
+    pl.nchunk = ngan::ceil_div(H, pl.R);
+    pl.slabs = (long)pl.gx * B * pl.nchunk;
+    NGAN_REQUIRE(pl.slabs <= 1024, NGAN_ERR_SHAPE, "%s: B=%d H=%d W=%d N=%d needs %ld slabs (max 1024)", who, B, H, W, N, pl.slabs);
+    return NGAN_OK;
 }
 
 }  // namespace
+
+extern "C" int ngan_first_block_plan(int B, int H, int W, int C, int N, int* out4) {
+    NGAN_REQUIRE(out4, NGAN_ERR_ARG, "first_block_plan: null pointer");
+    FbPlan pl;
+    const int st = fb_plan("first_block_plan", B, H, W, C, N, pl);
+    out4[0] = pl.gx; out4[1] = pl.R; out4[2] = pl.nchunk; out4[3] = st ? 0 : (int)pl.slabs;
+    return st;
+}
 
 extern "C" size_t ngan_first_block_table_floats(int N) { return N > 0 ? (size_t)2 * 9 * N : 0; }
 
@@ -269,13 +289,14 @@ extern "C" int ngan_first_block_fwd(const float* p, const float* w_conv, const f
                                     float* y, float* rnorm, float* tables, int B, int H, int W, int C, int N, float scale,
                                     float slope, float eps, void* stream) {
     NGAN_REQUIRE(p && w_conv && wf && y && rnorm && tables, NGAN_ERR_ARG, "first_block_fwd: null pointer");
-    NGAN_REQUIRE(fb_shape_ok(B, H, W, C, N), NGAN_ERR_SHAPE,
-                 "first_block_fwd: B=%d H=%d W=%d C=%d N=%d unsupported (N 16 or 32, C <= 64, < 2^31 output elements)", B, H, W, C, N);
+    FbPlan pl;
+    int st = fb_plan("first_block_fwd", B, H, W, C, N, pl);
+    if (st) return st;
     hipStream_t s = (hipStream_t)stream;
-    int st = fb_tables(w_conv, wf, bf, tables, N, C, scale, s);
+    st = fb_tables(w_conv, wf, bf, tables, N, C, scale, s);
     if (st) return st;
     const int nchunk = ngan::ceil_div(H, FB_ROWS);
-    const dim3 grid(ngan::ceil_div((long)W * (N / 4), 256), B * nchunk), block(256);
+    const dim3 grid(pl.gx, B * nchunk), block(256);
     if (N == 16) hipLaunchKernelGGL((first_block_fwd_kernel<4>), grid, block, 0, s, p, tables, b_conv, y, rnorm, H, W, FB_ROWS, nchunk, slope, eps);
     else hipLaunchKernelGGL((first_block_fwd_kernel<8>), grid, block, 0, s, p, tables, b_conv, y, rnorm, H, W, FB_ROWS, nchunk, slope, eps);
     return ngan::launch_status("ngan_first_block_fwd");
@@ -290,17 +311,16 @@ extern "C" int ngan_first_block_bwd(const float* p, const float* gc, const float
                                     float* gw_conv, float* gwf, float* gbf, float* gb_conv, float* workspace, int B, int H, int W,
                                     int C, int N, float scale, int accumulate, void* stream) {
     NGAN_REQUIRE(p && gc && w_conv && wf && gw_conv && gwf && workspace, NGAN_ERR_ARG, "first_block_bwd: null pointer");
-    NGAN_REQUIRE(fb_shape_ok(B, H, W, C, N), NGAN_ERR_SHAPE, "first_block_bwd: B=%d H=%d W=%d C=%d N=%d unsupported", B, H, W, C, N);
-    const int gx = ngan::ceil_div((long)W * (N / 4), 256);
-    const int R = fb_sums_rows(B, H, gx), nchunk = ngan::ceil_div(H, R);
-    const int nblk = gx * B * nchunk;
-    NGAN_REQUIRE(nblk <= 1024 && (long)B * nchunk < 65536, NGAN_ERR_SHAPE, "first_block_bwd: B=%d W=%d needs %d slabs (max 1024)", B, W, nblk);
+    FbPlan pl;
+    int st = fb_plan("first_block_bwd", B, H, W, C, N, pl);
+    if (st) return st;
+    const int gx = pl.gx, R = pl.R, nchunk = pl.nchunk, nblk = (int)pl.slabs;
     hipStream_t s = (hipStream_t)stream;
     float* tables = workspace + (size_t)1024 * 2 * 9 * N;
     const dim3 grid(gx, B * nchunk);
     if (N == 16) hipLaunchKernelGGL((first_block_sums_kernel<4>), grid, dim3(256), 0, s, p, gc, workspace, H, W, R, nchunk);
     else hipLaunchKernelGGL((first_block_sums_kernel<8>), grid, dim3(256), 0, s, p, gc, workspace, H, W, R, nchunk);
-    int st = ngan::launch_status("ngan_first_block_bwd(sums)");
+    st = ngan::launch_status("ngan_first_block_bwd(sums)");
     if (st) return st;
     st = ngan::reduce_partials(workspace, nblk, 2 * 9 * N, tables, 1.0f, s);
     if (st) return st;
@@ -310,9 +330,11 @@ extern "C" int ngan_first_block_bwd(const float* p, const float* gc, const float
 
 extern "C" int ngan_first_block_dx(const float* gc, const float* tables, float* gx, int B, int H, int W, int N, int pool, void* stream) {
     NGAN_REQUIRE(gc && tables && gx, NGAN_ERR_ARG, "first_block_dx: null pointer");
-    NGAN_REQUIRE(fb_shape_ok(B, H, W, 1, N), NGAN_ERR_SHAPE, "first_block_dx: B=%d H=%d W=%d N=%d unsupported", B, H, W, N);
+    FbPlan pl;
+    const int st = fb_plan("first_block_dx", B, H, W, 1, N, pl);
+    if (st) return st;
     const int nchunk = ngan::ceil_div(H, FB_ROWS);
-    const dim3 grid(ngan::ceil_div((long)W * (N / 4), 256), B * nchunk), block(256);
+    const dim3 grid(pl.gx, B * nchunk), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (N == 16) hipLaunchKernelGGL((first_block_dx_kernel<4>), grid, block, 0, s, gc, tables, gx, H, W, FB_ROWS, nchunk, pool);
     else hipLaunchKernelGGL((first_block_dx_kernel<8>), grid, block, 0, s, gc, tables, gx, H, W, FB_ROWS, nchunk, pool);

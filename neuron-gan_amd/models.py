@@ -689,7 +689,7 @@ class Discriminator_PG(_ProgressiveNet):
         steps = _plan(list(block)[1:] if pool else block)
         first = steps[0]
         if (ops.first_order_enabled() and first[0] == 'conv_lrelu_pn' and first[2] == ops.RES_NONE
-                and ops.first_block_fusable(x, from_im.conv.weight, first[1].weight)):
+                and ops.first_block_fusable(x, from_im.conv.weight, first[1].weight, pool)):
             # differentiated once, one colour: FromImage folds into the conv (ops.FirstBlock), its output is never materialised
             link = ops.PNLink() if torch.is_grad_enabled() else None
             y, _ = ops.FirstBlock.apply(x, from_im.conv.weight, from_im.conv.bias, first[1].weight, first[1].bias, pool,

@@ -904,11 +904,15 @@ class FromImage(Function):
 _first_block_allowed = True      # off only for a sensitivity run (tools/first_block_sensitivity.py)
 
 
-def first_block_fusable(x, w_from, w_conv):
-    """can FirstBlock take FromImage -> conv3x3 -> LeakyReLU -> PixelNorm?  (one colour channel, 16 or 32 conv outputs; fp32 storage:
-    the folded kernels write fp32 activations, the bf16 mode runs the two layers as they are)"""
-    return (_first_block_allowed and _conv_precision != 5 and x.shape[-1] == 1 and w_from.shape[1] == 1 and w_conv.shape[0] in (16, 32)
-            and w_conv.shape[1] <= 64 and x.shape[0] * x.shape[1] < 65536)
+def first_block_fusable(x, w_from, w_conv, pool=False):
+    """can FirstBlock take FromImage -> conv3x3 -> LeakyReLU -> PixelNorm on the NHWC image x (pooled 2x2 first with `pool`)?  One
+    colour channel and fp32 storage (the folded kernels write fp32 activations, the bf16 mode runs the two layers as they are); the
+    shape is the library's to judge (ngan_first_block_plan: 16 or 32 conv outputs, at most 64 channels between the layers, the size
+    and slab limits), so a shape the fold refuses takes the unfused pair."""
+    if not (_first_block_allowed and _conv_precision != 5 and x.dim() == 4 and x.shape[-1] == 1 and w_from.shape[1] == 1):
+        return False
+    b, h, wd = _from_image_out_hw(x, pool)
+    return _C.first_block_plan(b, h, wd, w_conv.shape[1], w_conv.shape[0])[0] == 0
 
 
 class FirstBlock(Function):
