@@ -569,8 +569,12 @@ int ngan_wgan_stem_grad(const float* z, const float* g, float* gW, float* gb, in
  * Each rank reduces its own pixels into an fp64 record, the caller all-gathers the records (rank order 0 .. world-1 in `recs`), and
  * every rank merges the same bytes in the same order: bit-identical statistics on every rank.  The single-GPU entry points above are
  * unchanged; no float atomics here either.
- * ngan_bn_moments: rec (1 + 2C doubles) = [count, mean[C], M2[C]] of y (npix, C), M2 = sum (y - mean)^2 (from sums shifted by the
- *     channel's first pixel: no cancellation).  work: ngan_chan_reduce_workspace_floats(npix, C) floats.
+ * ngan_bn_moments: rec (1 + 2C doubles) = [count, mean[C], M2[C]] of y (npix, C), M2 = sum (y - mean)^2.  All of it is fp64
+ *     arithmetic on the fp32 pixels: s0 = sum d and s1 = sum d^2 of d = y - y[0, c] (the channel's first pixel), every addition in
+ *     fp64 from the first on, then mean = y[0, c] + s0/n and M2 = s1 - s0*s0/n.  That difference cancels by 1 + 2 (s0/n)^2 / var,
+ *     which costs fp64 sums nothing an fp32 result can show, wherever the first pixel lies (fp32 sums per chunk lost tens of fp32
+ *     roundings of rstd to a first pixel six sigma out).  work: ngan_chan_reduce_workspace_floats(npix, C) floats, 8-byte aligned
+ *     (2 np C doubles of chunk partials).
  * ngan_bn_merge_fold: merges world records (world x (1 + 2C) doubles) in rank order, pairwise (Chan et al.): n = na + nb,
  *     d = mean_b - mean_a, mean = mean_a + d*nb/n, M2 = M2_a + M2_b + d^2*na*nb/n.  Then writes what ngan_bn_stats writes from the
  *     global N and M2: mean, rstd = 1/sqrt(M2/N + eps), scale, shift, running statistics (variance M2/(N-1)), *nbt += 1 -- and

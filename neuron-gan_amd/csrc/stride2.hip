@@ -258,8 +258,7 @@ void wgrad_plan(int B, int Hh, int Wh, int CH, int CF, int& HB, int& FB, int& ns
 // ---------------------------------------------------------------------------------------------------------------------------------
 // per-channel reductions over an (npix, C) channels-last tensor, in two fixed-order stages.
 // Stage 1: workgroup g sums pixels [g*chunk, (g+1)*chunk); thread tid owns one channel and one pixel lane (see the kernel).
-//   mode 0 (BN moments of the synchronised path; ngan_bn_stats has its own fp64 stage 1, bn_stats_stage1):
-//                             s0 = sum (y - y[0,c]),  s1 = sum (y - y[0,c])^2        (shifted by the first pixel)
+//   (the BN moments, s0 = sum (y - y[0,c]) and s1 = sum (y - y[0,c])^2, have a stage 1 of their own in fp64: bn_stats_stage1)
 //   mode 1 (BN backward):     gz = g * act'(z),  z = scale*y + shift;  s0 = sum gz,  s1 = sum gz * xhat,  xhat = (y - mean) * rstd
 //   mode 2 (plain sum):       s0 = sum g
 // Partials: part[g][2][C].  Stage 2 (one thread per channel) sums the chunks in order.
@@ -288,16 +287,11 @@ __global__ __launch_bounds__(256) void chan_reduce_stage1(RedArgs a) {
         const int lane = split ? tid / a.C : 0;
         float s0 = 0.f, s1 = 0.f;
         if (c < a.C && lane < L) {
-            const float piv = MODE == 0 ? a.y[c] : 0.f;
             const float sc = (MODE == 1 && a.scale) ? a.scale[c] : 1.f, sh = (MODE == 1 && a.scale) ? a.shift[c] : 0.f;
             const float mu = (MODE == 1 && a.mean) ? a.mean[c] : 0.f, rs = (MODE == 1 && a.rstd) ? a.rstd[c] : 1.f;
             for (long pix = p0 + lane; pix < p1; pix += L) {
                 const long i = pix * a.C + c;
-                if (MODE == 0) {
-                    const float d = a.y[i] - piv;
-                    s0 += d;
-                    s1 = fmaf(d, d, s1);
-                } else if (MODE == 1) {
+                if (MODE == 1) {
                     const float yv = a.y[i];
                     const float z = fmaf(sc, yv, sh);
                     float gz = a.g[i];
@@ -326,14 +320,16 @@ __global__ __launch_bounds__(256) void chan_reduce_stage1(RedArgs a) {
     }
 }
 
-// BN statistics of the single-GPU path, stage 1: chan_reduce_stage1<0>'s partition, order and fp32 sums of d = y - y[0,c] and d^2
-// (part32[g][2][C], the same bits), and beside them the same two sums in fp64 (part[g][2][C] doubles).  The variance is
+// BN statistics, stage 1: chan_reduce_stage1's partition and order; fp32 sums of d = y - y[0,c] and d^2 (part32[g][2][C]: the one-pass
+// fp32 form the single-GPU path had before, bit for bit), and beside them the same two sums in fp64 (part[g][2][C] doubles).  The variance is
 // s1/n - (s0/n)^2, which cancels by a factor 1 + 2 (s0/n)^2 / var: in fp32 a first pixel six sigma from its channel's mean costs 73
 // roundings' worth of the variance, in fp64 nothing that an fp32 result can show.  bn_stats_finish keeps the fp32 moments where the
-// fp64 ones confirm them and takes the fp64 ones elsewhere.
+// fp64 ones confirm them and takes the fp64 ones elsewhere.  F32 = false (ngan_bn_moments, the synchronised path: its record is fp64
+// and nothing downstream reads an fp32 moment) leaves the fp32 sums out.
+template <bool F32>
 __global__ __launch_bounds__(256) void bn_stats_stage1(RedArgs a, double* __restrict__ part) {
     __shared__ double sm[2][256];
-    __shared__ float sm32[2][256];
+    __shared__ float sm32[2][F32 ? 256 : 1];
     const int tid = threadIdx.x;
     const bool split = a.C <= 256;
     const int L = split ? 256 / a.C : 1;
@@ -349,9 +345,11 @@ __global__ __launch_bounds__(256) void bn_stats_stage1(RedArgs a, double* __rest
             const float piv = a.y[c];
             for (long pix = p0 + lane; pix < p1; pix += L) {
                 const float yv = a.y[pix * a.C + c];
-                const float df = yv - piv;
-                f0 += df;
-                f1 = fmaf(df, df, f1);
+                if (F32) {
+                    const float df = yv - piv;
+                    f0 += df;
+                    f1 = fmaf(df, df, f1);
+                }
                 const double d = (double)yv - (double)piv;
                 s0 += d;
                 s1 = fma(d, d, s1);
@@ -359,8 +357,10 @@ __global__ __launch_bounds__(256) void bn_stats_stage1(RedArgs a, double* __rest
         }
         sm[0][tid] = s0;
         sm[1][tid] = s1;
-        sm32[0][tid] = f0;
-        sm32[1][tid] = f1;
+        if (F32) {
+            sm32[0][tid] = f0;
+            sm32[1][tid] = f1;
+        }
         __syncthreads();
         if (tid < CW && cbase + tid < a.C) {
             double t0 = 0.0, t1 = 0.0;
@@ -369,14 +369,18 @@ __global__ __launch_bounds__(256) void bn_stats_stage1(RedArgs a, double* __rest
                 const int j = tid + l * (split ? a.C : 0);
                 t0 += sm[0][j];
                 t1 += sm[1][j];
-                u0 += sm32[0][j];
-                u1 += sm32[1][j];
+                if (F32) {
+                    u0 += sm32[0][j];
+                    u1 += sm32[1][j];
+                }
             }
             const int cc = split ? tid : cbase + tid;
             part[((long)blockIdx.x * 2 + 0) * a.C + cc] = t0;
             part[((long)blockIdx.x * 2 + 1) * a.C + cc] = t1;
-            a.part[((long)blockIdx.x * 2 + 0) * a.C + cc] = u0;
-            a.part[((long)blockIdx.x * 2 + 1) * a.C + cc] = u1;
+            if (F32) {
+                a.part[((long)blockIdx.x * 2 + 0) * a.C + cc] = u0;
+                a.part[((long)blockIdx.x * 2 + 1) * a.C + cc] = u1;
+            }
         }
         __syncthreads();
     }
@@ -542,10 +546,13 @@ __global__ __launch_bounds__(256) void stem_grad_kernel(const float* __restrict_
 // synchronised BatchNorm (data parallel): per-rank records in fp64 that are all-gathered and merged in rank order.
 //   moments record  [count, mean[C], M2[C]]     (M2 = sum of squared deviations from the record's own mean)
 //   backward record [S0[C], S1[C]]               (S0 = sum gz, S1 = sum gz * xhat, xhat from the GLOBAL statistics)
-// The stage-1 partials come from chan_reduce_stage1 as on the single-GPU path; sum_parts_f64 adds them in fp64 with a block of
-// 16 channels x 16 lanes (lane l takes the partials l, l + 16, ... in order, then the channel's thread adds the 16 lane sums in order).
+// The moments' stage-1 partials are fp64 (bn_stats_stage1<false>: the sums about the rank's first pixel cancel in M2 = s1 - s0 d, and
+// fp32 partials lost tens of roundings of rstd to an outlying first pixel); the backward's are the fp32 ones of chan_reduce_stage1<1>,
+// as on the single-GPU path.  sum_parts_f64 adds either kind in fp64 with a block of 16 channels x 16 lanes (lane l takes the partials
+// l, l + 16, ... in order, then the channel's thread adds the 16 lane sums in order).
 // ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool sum_parts_f64(const float* __restrict__ part, int nparts, int C, double& s0, double& s1, int& c) {
+template <typename T>
+__device__ __forceinline__ bool sum_parts_f64(const T* __restrict__ part, int nparts, int C, double& s0, double& s1, int& c) {
     __shared__ double sm[2][256];
     const int t = threadIdx.x;
     const int cc = blockIdx.x * 16 + (t & 15), lane = t >> 4;
@@ -571,7 +578,7 @@ __device__ __forceinline__ bool sum_parts_f64(const float* __restrict__ part, in
 }
 
 // shifted sums (pivot y[0, c]) -> this rank's moments record
-__global__ __launch_bounds__(256) void bn_moments_finish(const float* __restrict__ part, int nparts, const float* __restrict__ y, long npix,
+__global__ __launch_bounds__(256) void bn_moments_finish(const double* __restrict__ part, int nparts, const float* __restrict__ y, long npix,
                                                          int C, double* __restrict__ rec) {
     if (blockIdx.x == 0 && threadIdx.x == 0) rec[0] = (double)npix;
     double s0, s1;
@@ -719,7 +726,8 @@ int ngan_s2_wgrad(const float* half, const float* full, const float* h_scale, co
 long ngan_chan_reduce_workspace_floats(long npix, int C) {
     int np;
     red_chunk(npix, C, np);
-    return 6L * np * C;      // ngan_bn_stats: part[np][2][C] as doubles, then as floats; the fp32 reductions use the first third
+    return 6L * np * C;      // ngan_bn_stats: part[np][2][C] as doubles, then as floats; ngan_bn_moments: the doubles; the fp32
+                             // reductions use the first third
 }
 
 int ngan_bn_stats(const float* y, long npix, int C, const float* gamma, const float* beta, float* mean, float* rstd, float* scale,
@@ -733,7 +741,7 @@ int ngan_bn_stats(const float* y, long npix, int C, const float* gamma, const fl
     hipStream_t s = (hipStream_t)stream;
     double* part = reinterpret_cast<double*>(work);       // 2 np C doubles, then the 2 np C floats of the fp32 sums
     a.part = work + 4L * np * C;
-    hipLaunchKernelGGL(bn_stats_stage1, dim3(np), dim3(256), 0, s, a, part);
+    hipLaunchKernelGGL(bn_stats_stage1<true>, dim3(np), dim3(256), 0, s, a, part);
     int st = ngan::launch_status("ngan_bn_stats");
     if (st) return st;
     hipLaunchKernelGGL(bn_stats_finish, dim3(ngan::ceil_div(C, 256)), dim3(256), 0, s, part, a.part, np, y, npix, C, gamma, beta, mean, rstd,
@@ -828,13 +836,15 @@ int ngan_wgan_stem_grad(const float* z, const float* g, float* gW, float* gb, in
 int ngan_bn_moments(const float* y, long npix, int C, double* rec, float* work, void* stream) {
     NGAN_REQUIRE(y && rec && work, NGAN_ERR_ARG, "bn_moments: null pointer");
     NGAN_REQUIRE(npix > 0 && C > 0, NGAN_ERR_SHAPE, "bn_moments: npix=%ld C=%d", npix, C);
+    NGAN_REQUIRE(reinterpret_cast<uintptr_t>(work) % sizeof(double) == 0, NGAN_ERR_ARG, "bn_moments: work must be 8-byte aligned");
     int np;
-    RedArgs a{y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, npix, C, red_chunk(npix, C, np), work};
+    RedArgs a{y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, npix, C, red_chunk(npix, C, np), nullptr};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(chan_reduce_stage1<0>, dim3(np), dim3(256), 0, s, a);
+    double* part = reinterpret_cast<double*>(work);       // 2 np C doubles, the first two thirds of the workspace
+    hipLaunchKernelGGL(bn_stats_stage1<false>, dim3(np), dim3(256), 0, s, a, part);
     int st = ngan::launch_status("ngan_bn_moments");
     if (st) return st;
-    hipLaunchKernelGGL(bn_moments_finish, dim3(ngan::ceil_div(C, 16)), dim3(256), 0, s, work, np, y, npix, C, rec);
+    hipLaunchKernelGGL(bn_moments_finish, dim3(ngan::ceil_div(C, 16)), dim3(256), 0, s, part, np, y, npix, C, rec);
     return ngan::launch_status("ngan_bn_moments(finish)");
 }
 

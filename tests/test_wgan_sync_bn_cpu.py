@@ -91,6 +91,9 @@ def test_sync_entry_points_validate_on_the_host(lib):
     assert b"null" in lib.ngan_last_error()
     assert lib.ngan_bn_act_bwd_merged(one, one, one, one, one, one, one, 1, 0.2, 64, 8, None, 2, 0, one, one, None, None, one, None) < 0
     assert b"null" in lib.ngan_last_error()
+    # the moments' workspace holds doubles
+    assert lib.ngan_bn_moments(one, 64, 8, one, ctypes.c_void_p(20), None) < 0
+    assert b"8-byte aligned" in lib.ngan_last_error()
     # running mean without running variance
     assert lib.ngan_bn_merge_fold(one, 2, 8, one, one, one, one, one, one, one, None, None, 0.1, 1e-5, one, None) < 0
     assert b"go together" in lib.ngan_last_error()
