@@ -248,6 +248,8 @@ int ngan_wloss_head_bwd(const float* scores, int n_real, int n_fake, float drift
 #include "ngan_penalty.h"
 /* ---- launch plan of the folded critic first block as a host query: declared in ngan_first_block.h, an extension section likewise ---- */
 #include "ngan_first_block.h"
+/* ---- spectral regularisation of the generator (opt-in): declared in ngan_spectral.h, an extension section likewise ---- */
+#include "ngan_spectral.h"
 
 /* ---- latent projection: utils.py:77-78 (clamp(-c, c), L2-normalise each row), in place on (rows, dim) normal draws ---------- */
 int ngan_latent_normalize(float* z, int rows, int dim, float clamp, void* stream);

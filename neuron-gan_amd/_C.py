@@ -183,6 +183,18 @@ FIRST_BLOCK_NON_STATUS = {
     "ngan_first_block_plan": ([_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)], _I),
 }
 
+# include/ngan_spectral.h, the sixth extension section: the spectral regularisation of the generator (ops.SpectralLoss); listed by
+# `spectral_symbols`, like the tables above
+SPECTRAL_SIGNATURES = {
+    "ngan_specloss_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ngan_specloss_head": [_P, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P],
+    "ngan_specloss_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+}
+SPECTRAL_NON_STATUS = {
+    "ngan_specloss_fwd_workspace_bytes": ([_I, _I, _I], _Z),
+    "ngan_specloss_bwd_workspace_bytes": ([_I, _I, _I], _Z),
+}
+
 NON_STATUS = {
     "ngan_version": ([], ctypes.c_char_p),
     "ngan_last_error": ([], ctypes.c_char_p),
@@ -229,11 +241,13 @@ def lib():
                                f"or `make -C neuron-gan_amd/csrc`; there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(MBSTD_SIGNATURES.items())
-                               + list(GEOAUG_SIGNATURES.items()) + list(PENALTY_SIGNATURES.items())):
+                               + list(GEOAUG_SIGNATURES.items()) + list(PENALTY_SIGNATURES.items())
+                               + list(SPECTRAL_SIGNATURES.items())):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
-        for name, (argtypes, restype) in list(NON_STATUS.items()) + list(MBSTD_NON_STATUS.items()) + list(FIRST_BLOCK_NON_STATUS.items()):
+        for name, (argtypes, restype) in (list(NON_STATUS.items()) + list(MBSTD_NON_STATUS.items()) + list(FIRST_BLOCK_NON_STATUS.items())
+                                          + list(SPECTRAL_NON_STATUS.items())):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -259,6 +273,10 @@ def geoaug_symbols():
 
 def penalty_symbols():
     return list(PENALTY_SIGNATURES)
+
+
+def spectral_symbols():
+    return list(SPECTRAL_SIGNATURES) + list(SPECTRAL_NON_STATUS)
 
 
 def first_block_symbols():

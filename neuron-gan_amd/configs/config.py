@@ -34,6 +34,7 @@ _DEFAULTS = dict(
     # the checkpoint metrics: <prefix>_period, _images (or _pairs), _seed and the metric's own options, row by row
     **{name: default for m in METRICS for name, _, default, _ in settings(m)},
     diffaug='', diffaug_p=1.0, diffaug_seed=0, lsgan=False, mbstd_group=0, grad_pen_mode='gp', grad_pen_interval=1,
+    spec_loss_lambda=0.0, spec_loss_floor=1e-3, spec_loss_images=256, spec_loss_seed=0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -131,6 +132,20 @@ def validate_configs(create_dirs=False):
         raise ValueError(f"grad_pen_interval={g['grad_pen_interval']!r} must be an integer >= 1")
     if (g['grad_pen_mode'] != 'gp' or g['grad_pen_interval'] != 1) and g['wgan']:
         raise ValueError("grad_pen_mode / grad_pen_interval other than 'gp' / 1 are not available for the WGAN nets (wgan=True)")
+    # spectral regularisation of the generator (an addition of this implementation; Durall et al. 2020): spec_loss_lambda 0 is off,
+    # otherwise the weight of the term; spec_loss_floor the floor on the ratio of the spectra; the data's mean radial spectrum is taken
+    # over spec_loss_images images per stage, drawn with spec_loss_seed
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v)      # noqa: E731
+    if not (number(g['spec_loss_lambda']) and g['spec_loss_lambda'] >= 0):
+        raise ValueError(f"spec_loss_lambda={g['spec_loss_lambda']!r} must be a finite number >= 0 (0: off)")
+    if not (number(g['spec_loss_floor']) and g['spec_loss_floor'] > 0):
+        raise ValueError(f"spec_loss_floor={g['spec_loss_floor']!r} must be a finite number > 0")
+    if isinstance(g['spec_loss_images'], bool) or not (isinstance(g['spec_loss_images'], int) and g['spec_loss_images'] >= 1):
+        raise ValueError(f"spec_loss_images={g['spec_loss_images']!r} must be an integer >= 1")
+    if isinstance(g['spec_loss_seed'], bool) or not (isinstance(g['spec_loss_seed'], int) and g['spec_loss_seed'] >= 0):
+        raise ValueError(f"spec_loss_seed={g['spec_loss_seed']!r} must be an integer >= 0")
+    if g['spec_loss_lambda'] and g['wgan']:
+        raise ValueError("spec_loss_lambda > 0 is not available for the WGAN nets (wgan=True)")
     if g['pggan']:
         err_msg = 'The number of layers in the generator and discriminator must match.'
         assert len(g['N_gen_features']) == len(g['N_dis_features']), err_msg

@@ -5,10 +5,13 @@
     D_grad_pen_loss(G, D, Lambda)(real)      -> loss   (create_graph double-backward through the critic)
     D_LS_loss(G, D, real)                    -> (loss, score_real, score_fake)   least squares, Mao et al. 2017; functions, as in the
     G_LS_loss(G, D, real)                    -> (loss, score_fake)               reference, which ships them and never calls them
+    G_spectral_loss(images, target, Lambda)  -> loss   spectral regularisation of a generator's images (Durall et al. 2020); an addition
 
 Latents come from `utils.sample_latent_vec` unless a tensor is passed through the optional `z=` / `epsilon=`
 keywords (how the parity tests inject the reference's draws).  Every loss takes an optional `augment=` hook (`DiffAugmentHook`, an
-addition of this implementation: differentiable augmentation of everything the critic sees); None is the reference's path.  NaN handling: the reference dumps locals and
+addition of this implementation: differentiable augmentation of everything the critic sees); None is the reference's path.  The
+generator losses a trainer holds (G_W_loss, G_LS_module) also take a `spectral=` hook (`SpectralHook`: the spectral regularisation of
+G_spectral_loss on the generator's raw images) and then return the term as a third value.  NaN handling: the reference dumps locals and
 raises `ValueError` (loss_functions.py:35-41, 70-72); here the check is optional (`check_nan`) because
 `torch.isnan(...)` in an `if` is a host sync on the GPU -- the training loop checks once per epoch instead.
 """
@@ -82,6 +85,32 @@ class DiffAugmentHook:
         return fake if self.gen is None else ops.DiffAugment.apply(fake, self.gen, self.colour, self.fill)
 
 
+def G_spectral_loss(images, target, Lambda=1.0, floor=1e-3, global_batch=None):
+    """Spectral regularisation of a generator (Durall et al. 2020): Lambda / global_batch * sum_b l[b] with
+    l[b] = mean_{k=1..R/2} ln((S[b][k] / target[k] + floor) / (1 + floor))^2, S the Hann-windowed radial power spectrum of image b
+    (metrics.radial_spectrum, the same bits) and target the data's mean radial spectrum at this size (metrics.spectral_target), fp64
+    (R/2 + 1,).  images: (B, 1, R, R) fp32 on the GPU, R a power of two in 16 .. 1024.  The loss is per sample, so an image's value
+    does not depend on the rest of the batch; global_batch (default B) is the divisor of a batch shared between ranks.  An fp32 scalar,
+    differentiable once in the images (ops.SpectralLoss: the adjoint transform on HIP)."""
+    target = torch.as_tensor(target, dtype=torch.float64, device=images.device)
+    b = images.shape[0] if global_batch is None else int(global_batch)
+    return ops.SpectralLoss.apply(images, target, float(Lambda) / b, float(floor))[1]
+
+
+class SpectralHook:
+    """The `spectral=` hook of the generator losses: taps the generator's raw images -- before any DiffAugment transform: the data's
+    spectrum is that of un-augmented samples -- and holds the term.  target: fp64 (R/2 + 1,) on the device; scale: Lambda / batch."""
+
+    def __init__(self, target, scale, floor=1e-3):
+        self.target, self.scale, self.floor = target, float(scale), float(floor)
+
+    def tap(self, images):
+        """(images passed through, the term): the gradient of what follows arrives at the pass-through and is added on the adjoint's
+        store"""
+        images, term, _ = ops.SpectralLoss.apply(images, self.target, self.scale, self.floor)
+        return images, term
+
+
 class D_W_loss(nn.Module):
     def __init__(self, generator_net, discriminator_net, drift_epsilon=0.0, check_nan=True):
         super().__init__()
@@ -119,17 +148,20 @@ class G_W_loss(nn.Module):
         self.discriminator_net = discriminator_net
         self.check_nan = check_nan
 
-    def forward(self, real_images_batch, z=None, augment=None):
+    def forward(self, real_images_batch, z=None, augment=None, spectral=None):
+        """spectral (a SpectralHook): the return value gains the spectral term, (loss, z, term); None is the reference's path"""
         batch_size, device = real_images_batch.size(0), real_images_batch.device
         z_latent = _latents(self.generator_net, batch_size, device, z)
         fake_images = self.generator_net(z_latent)
+        if spectral is not None:
+            fake_images, term = spectral.tap(fake_images)
         if augment is not None:
             fake_images = augment.generated(fake_images)      # D(T(G(z))): the generator is trained through the transform
         with ops.first_order_only():      # differentiated once (train.py:384)
             G_loss = ops.WLossHead.apply(self.discriminator_net(fake_images), batch_size, 0.0)[0]       # -mean(D(G(z)))
         if self.check_nan and torch.isnan(G_loss):
             raise ValueError('Generator loss is nan.')
-        return G_loss, z_latent
+        return (G_loss, z_latent) if spectral is None else (G_loss, z_latent, term)
 
 
 # The reference's coding of the least-squares targets (loss_functions.py:99, 133): the critic pulls real scores to 1 and generated ones to
@@ -164,9 +196,17 @@ def D_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, 
 def G_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, *, z=None, augment=None, check_nan=True):
     """mean((D(G(z)) - 1)^2) (loss_functions.py:117-143) -> (G_loss, Score_fake_avg).  One deliberate departure: the reference detaches
     the generated images (loss_functions.py:125), so its generator would receive no gradient at all and could not be trained with
-    this loss; here the value is the same and the gradient flows into the generator (through `augment`'s transform when given)."""
+    this loss; here the value is the same and the gradient flows into the generator (through `augment`'s transform when given).
+    (The signature is the reference's plus the W losses' keyword extras; the `spectral=` hook is G_LS_module's.)"""
+    return _g_ls_loss(generator_net, discriminator_net, real_images_batch, z, augment, check_nan, None)
+
+
+def _g_ls_loss(generator_net, discriminator_net, real_images_batch, z, augment, check_nan, spectral):
+    """G_LS_loss's body; spectral (a SpectralHook): the return value gains the spectral term, (G_loss, Score_fake_avg, term)"""
     batch_size, device = real_images_batch.size(0), real_images_batch.device
     fake_images = generator_net(_latents(generator_net, batch_size, device, z))
+    if spectral is not None:
+        fake_images, term = spectral.tap(fake_images)
     if augment is not None:
         fake_images = augment.generated(fake_images)
     with ops.first_order_only():
@@ -176,7 +216,7 @@ def G_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, 
             raise ValueError('Fake loss is nan.')
         if torch.isnan(G_loss):
             raise ValueError('D loss is nan.')
-    return G_loss, Score_fake_avg
+    return (G_loss, Score_fake_avg) if spectral is None else (G_loss, Score_fake_avg, term)
 
 
 class D_LS_module(nn.Module):
@@ -198,11 +238,11 @@ class G_LS_module(nn.Module):
         super().__init__()
         self.generator_net, self.discriminator_net, self.check_nan = generator_net, discriminator_net, check_nan
 
-    def forward(self, real_images_batch, z=None, augment=None):
+    def forward(self, real_images_batch, z=None, augment=None, spectral=None):
+        """spectral (a SpectralHook): the return value gains the spectral term, (loss, z, term)"""
         z_latent = _latents(self.generator_net, real_images_batch.size(0), real_images_batch.device, z)
-        G_loss, _ = G_LS_loss(self.generator_net, self.discriminator_net, real_images_batch, z=z_latent, augment=augment,
-                              check_nan=self.check_nan)
-        return G_loss, z_latent
+        out = _g_ls_loss(self.generator_net, self.discriminator_net, real_images_batch, z_latent, augment, self.check_nan, spectral)
+        return (out[0], z_latent) if spectral is None else (out[0], z_latent, out[2])
 
 
 PENALTY_MODES = ("gp", "lp", "r1")      # D_grad_pen_loss(mode=)

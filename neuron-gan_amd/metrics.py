@@ -708,6 +708,27 @@ def evaluate_spectrum(generator, dataset, n_images=8192, batch_size=64, seed=0, 
     return (metric.result(), metric) if return_metric else metric.result()
 
 
+def spectral_target(dataset, image_size, n_images=256, seed=0, batch_size=64, device="cuda"):
+    """The data's mean radial spectrum at `image_size`, fp64 (R/2 + 1,) on `device`: the target of the generator's spectral loss
+    (loss_functions.G_spectral_loss).  Taken the way evaluate_spectrum takes its data side: n_images images through the data set's
+    own augmentation chain, its indices cycled, its random draws from a private generator seeded seed + 1, its image size and its
+    own generator restored afterwards; torch's global and device generators are never consumed.  Every rank of a data-parallel run
+    computes the same bits from the whole data set."""
+    size, n_images, batch_size = int(image_size), int(n_images), int(batch_size)
+    if n_images < 1 or batch_size < 1:
+        raise ValueError(f"n_images={n_images} and batch_size={batch_size} must be positive")
+    if size < SPECTRUM_MIN or size > SPECTRUM_MAX or size & (size - 1):
+        raise ValueError(f"image_size={size}: the kernels transform powers of two from {SPECTRUM_MIN} to {SPECTRUM_MAX}")
+    total = None
+    with _private_stream(dataset, size, seed):
+        for i in range(0, n_images, batch_size):
+            b = min(batch_size, n_images - i)
+            x = _real_batch(dataset, [(i + j) % len(dataset) for j in range(b)], torch.device(device))
+            s = radial_spectrum(channels_last(x.to(device)), True).sum(0)
+            total = s if total is None else total + s
+    return total / n_images
+
+
 def format_spectrum(result, title="Radial power spectrum"):
     """the table eval.py prints: data, generated and their ratio in dB at the octave edges k = 1, 2, 4, ..., R/2, the two summaries
     below it"""

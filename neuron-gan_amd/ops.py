@@ -1848,3 +1848,67 @@ class DiffGeometry(Function):
         gx = torch.empty_like(gy)
         _C.call("ngan_diffgeo_bwd", gy, table, gx, b, c, h, w, table.shape[0])
         return gx, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------
+# spectral regularisation of the generator (include/ngan_spectral.h; csrc/specloss.hip)
+# ---------------------------------------------------------------------------------------------------------
+SPECLOSS_MIN, SPECLOSS_MAX = 16, 1024        # image sizes the kernels transform
+
+
+def _specloss_check(images, target):
+    if images.dim() != 4 or images.shape[1] != 1 or images.shape[2] != images.shape[3]:
+        raise ValueError(f"SpectralLoss: planar greyscale images (B, 1, R, R) expected, got {tuple(images.shape)}")
+    if images.dtype != torch.float32:
+        raise NotImplementedError(f"SpectralLoss: the kernels read fp32 images, got {images.dtype}")
+    r = images.shape[2]
+    if target.dtype != torch.float64 or tuple(target.shape) != (r // 2 + 1,) or target.device != images.device:
+        raise ValueError(f"SpectralLoss: the target must be fp64 ({r // 2 + 1},) on {images.device}, got {target.dtype} "
+                         f"{tuple(target.shape)} on {target.device}")
+
+
+class SpectralLoss(Function):
+    """A tap on the generator's images: (images, L, per_image) = SpectralLoss.apply(images, target, scale, floor) with images passed
+    through, L = scale * sum_b l[b] (fp32 scalar) and per_image = l (fp64, not differentiable), l[b] the mean over k = 1 .. R/2 of
+    ln((S[b][k] / target[k] + floor) / (1 + floor))^2 and S the windowed radial spectrum of metrics.radial_spectrum (the same bits).
+    scale is lambda / global batch.  Four launches forward (the metric's three and the head); backward two: the adjoint transform
+    with the ring coefficients and the window folded in, the gradient arriving at the images added on its store and the one arriving
+    at L read from the device.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, images, target, scale, floor):
+        ctx.set_materialize_grads(False)
+        _specloss_check(images, target)
+        x, target = _c(images), target.contiguous()
+        b, r = x.shape[0], x.shape[2]
+        k = r // 2 + 1
+        lib, dev = _C.lib(), x.device
+        radial = torch.empty(b, k, device=dev, dtype=torch.float64)
+        transform = torch.empty(b, k, r, 2, device=dev, dtype=torch.float32)
+        ws = torch.empty(max(1, lib.ngan_specloss_fwd_workspace_bytes(b, r, 1) // 8), device=dev, dtype=torch.float64)
+        ring_norm = torch.empty(k, device=dev, dtype=torch.float64)
+        _C.call("ngan_specloss_fwd", x, radial, transform, ring_norm, ws, b, r, 1, 1)
+        per_image = torch.empty(b, device=dev, dtype=torch.float64)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        dradial = torch.empty(b, k, device=dev, dtype=torch.float32)
+        coef = torch.empty(b, k, device=dev, dtype=torch.float32)
+        skipped = torch.empty(1, device=dev, dtype=torch.int32)
+        _C.call("ngan_specloss_head", radial, target, ring_norm, b, r, float(scale), float(floor), per_image, loss, dradial, coef, skipped)
+        ctx.save_for_backward(transform, coef)
+        ctx.shape = (b, r)
+        ctx.mark_non_differentiable(per_image)
+        return images.view_as(images), loss, per_image
+
+    @staticmethod
+    def backward(ctx, g_images, g_loss, _g_per_image):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("second derivative through the spectral loss is not built: it is a generator-side term")
+        if g_loss is None:
+            return g_images, None, None, None
+        transform, coef = ctx.saved_tensors
+        b, r = ctx.shape
+        grad = torch.empty(b, 1, r, r, device=transform.device, dtype=torch.float32)
+        ws = torch.empty(max(1, _C.lib().ngan_specloss_bwd_workspace_bytes(b, r, 1) // 8), device=transform.device, dtype=torch.float64)
+        addend = None if g_images is None else _c(g_images)
+        _C.call("ngan_specloss_bwd", transform, coef, _c(g_loss), addend, grad, ws, b, r, 1, 1)
+        return grad, None, None, None

@@ -27,7 +27,8 @@ import torch.distributed as dist
 
 from . import _C, ops, wgan_ops
 from .launch import check_sharding, epoch_batches, longest_share, shard_bounds
-from .loss_functions import PENALTY_MODES, D_LS_module, D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_LS_module, G_W_loss
+from .loss_functions import (PENALTY_MODES, D_LS_module, D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_LS_module, G_W_loss,
+                             SpectralHook)
 from .metric_table import METRICS, settings
 from .scoring import (score_branches, score_due, score_morph, score_msssim, score_sholl, score_skeleton,  # noqa: F401
                       score_spectrum, score_swd)
@@ -378,6 +379,16 @@ def _check_ema_beta(ema_beta):
     if not 0.0 < float(ema_beta) < 1.0:
         raise ValueError(f"ema_beta must be 0 (off) or lie in (0, 1), got {ema_beta}")
     return float(ema_beta)
+
+
+def check_spec_loss(lam, floor):
+    """(spec_loss_lambda, spec_loss_floor) of the trainer arguments: a weight >= 0 and a floor > 0, both finite"""
+    ok = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)      # noqa: E731
+    if not ok(lam) or lam < 0:
+        raise ValueError(f"spec_loss_lambda must be a finite number >= 0, got {lam!r}")
+    if not ok(floor) or floor <= 0:
+        raise ValueError(f"spec_loss_floor must be a finite number > 0, got {floor!r}")
+    return float(lam), float(floor)
 
 
 def check_grad_pen(mode, interval):
@@ -838,7 +849,7 @@ class PGGANTrainer(_Trainer):
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
                  rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, objective="wasserstein",
-                 grad_pen_mode="gp", grad_pen_interval=1):
+                 grad_pen_mode="gp", grad_pen_interval=1, spec_loss_lambda=0.0, spec_loss_floor=1e-3):
         """optimizer: "adam" -- optim.Adam(params, lr, betas=(beta1, 0.999)), the reference's default -- or "rmsprop" --
         optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps), what the reference's RMSprop switch selects (train.py:220-225);
         beta1 only matters for Adam
@@ -864,7 +875,14 @@ class PGGANTrainer(_Trainer):
         `grad_pen_iteration` is a multiple of k, with weight k * grad_pen_lambda, and not at all in the others (no latents, no
         launches; D_grad_pen is then the zero scalar of the lambda = 0 path).  train_iteration, replay and step advance the count;
         d_step / d_compute on their own read the phase as it stands; capture() leaves it where it was.  With k > 1 the graphs are
-        kept per phase (`_graph_key`)."""
+        kept per phase (`_graph_key`).
+        spec_loss_lambda: 0 -- off (no buffer, no launch: the code path of a build without the feature); > 0 -- the weight of the
+        spectral regularisation of the generator (Durall et al. 2020; loss_functions.G_spectral_loss): the
+        generator's raw images, before any DiffAugment transform, have their radial power spectrum pulled towards the data's, which
+        `set_spectral_target` hands over per image size.  spec_loss_floor: the floor on the ratio of the spectra (1e-3: -30 dB).
+        The term is a per-sample mean like every loss here, so the share weight of a data-parallel step applies to it as it
+        stands.  The generator's image tensor is fp32 in every conv precision, the "bf16" storage mode included, so the term
+        runs in all of them.  A stage below 16 x 16 has no ring to score: the term is off there and `spectral_note` says so."""
         if objective not in OBJECTIVES:
             raise ValueError(f"objective must be one of {list(OBJECTIVES)}, got {objective!r}")
         grad_pen_mode, grad_pen_interval = check_grad_pen(grad_pen_mode, grad_pen_interval)
@@ -872,6 +890,7 @@ class PGGANTrainer(_Trainer):
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
         ema_beta = _check_ema_beta(ema_beta)
         aug_mask, aug_p, aug_seed = _check_diffaug(diffaug, diffaug_p, diffaug_seed)
+        spec_loss_lambda, spec_loss_floor = check_spec_loss(spec_loss_lambda, spec_loss_floor)
         if getattr(discriminator, 'mbstd_group', 0) > 0 and ops.get_conv_precision() == "bf16":
             raise NotImplementedError('a critic with mbstd_group > 0 is built for fp32 activation storage (conv precisions "f32" and '
                                       '"bf16x3"), not for the "bf16" storage mode')
@@ -914,8 +933,54 @@ class PGGANTrainer(_Trainer):
         if aug_mask:
             rank = dist.get_rank(process_group) if self.world > 1 else 0     # every rank draws a stream of its own
             self._aug = _DiffAugTables(aug_mask, aug_p, aug_seed, self.device, rank)
+        self.spec_loss_lambda, self.spec_loss_floor = spec_loss_lambda, spec_loss_floor
+        self._spec_targets = {} if spec_loss_lambda > 0 else None      # image size -> the static fp64 target buffer of that stage
+        self.spectral_note = None                                       # what a stage below 16 x 16 said (once per size)
         self.refresh_stage()
         ops.bump_weight_epoch()
+
+    # ---- spectral regularisation of the generator ----------------------------------------------------------------
+    @property
+    def spectral_enabled(self):
+        return self._spec_targets is not None
+
+    def set_spectral_target(self, image_size, target):
+        """The data's mean radial spectrum at `image_size` (metrics.spectral_target: fp64, R/2 + 1 bins) into the static device
+        buffer of that size.  The captured graphs of the stage read the buffer, so a refreshed target needs no re-capture."""
+        if self._spec_targets is None:
+            raise ValueError("set_spectral_target on a trainer with spec_loss_lambda = 0: there is no spectral term")
+        size = int(image_size)
+        target = torch.as_tensor(target, dtype=torch.float64)
+        if size < ops.SPECLOSS_MIN or size > ops.SPECLOSS_MAX or size & (size - 1) or tuple(target.shape) != (size // 2 + 1,):
+            raise ValueError(f"a target of {size // 2 + 1} bins for a power-of-two image size from {ops.SPECLOSS_MIN} to "
+                             f"{ops.SPECLOSS_MAX} expected, got image_size={image_size} and shape {tuple(target.shape)}")
+        if not bool(torch.isfinite(target).all()):
+            raise ValueError("the spectral target holds values that are not finite")
+        if size not in self._spec_targets:
+            self._spec_targets[size] = torch.empty(size // 2 + 1, device=self.device, dtype=torch.float64)
+        self._spec_targets[size].copy_(target)
+
+    def spectral_target_checksum(self, image_size):
+        """an integer every rank must agree on (_Ranks.assert_same): the target's fp64 bit patterns, summed modulo 2^24"""
+        bits = self._spec_targets[int(image_size)].cpu().view(torch.int64)
+        return int(((bits & 0xffffff).sum() + ((bits >> 24) & 0xffffff).sum() + ((bits >> 48) & 0xffff).sum()) % (1 << 24))
+
+    def _spectral_hook(self, b):
+        """the `spectral=` hook of this step's generator loss; None with the switch off and at a stage below 16 x 16"""
+        if self._spec_targets is None:
+            return None
+        size = int(self.G.image_size)
+        if size < ops.SPECLOSS_MIN:
+            note = f"{size} x {size} images are below {ops.SPECLOSS_MIN} x {ops.SPECLOSS_MIN}: no ring to score, the spectral term is off at this stage"
+            if self.spectral_note != note:
+                self.spectral_note = note
+                print(note)
+            return None
+        if size not in self._spec_targets:
+            raise RuntimeError(f"spec_loss_lambda={self.spec_loss_lambda:g} but no spectral target for {size} x {size} images: call "
+                               f"set_spectral_target({size}, metrics.spectral_target(dataset, {size})) first (the epoch driver does, at "
+                               f"the start and after every growth event)")
+        return SpectralHook(self._spec_targets[size], self.spec_loss_lambda / b, self.spec_loss_floor)
 
     # ---- differentiable augmentation ---------------------------------------------------------------------------
     @property
@@ -1090,19 +1155,28 @@ class PGGANTrainer(_Trainer):
             if self._aug is not None:
                 hook = DiffAugmentHook(gen=self._aug.gen(b, self.n_critic), colour=self._aug.colour,
                                        geo_gen=self._aug.geo_gen(b, self.n_critic))
-            loss, self.last_z_g = self.g_loss(real, z=self._latent(b, z), augment=hook)  # train.py:376
+            spectral, term = self._spectral_hook(b), None
+            if spectral is None:
+                loss, self.last_z_g = self.g_loss(real, z=self._latent(b, z), augment=hook)  # train.py:376
+            else:
+                loss, self.last_z_g, term = self.g_loss(real, z=self._latent(b, z), augment=hook, spectral=spectral)
             # the stem hands over factors instead of a gradient when they are exchanged (data parallel) or go straight to Adam
             self._stem_sink_active = self.stem is not None and (self._stem_for_exchange or self._stem_grad_skipped)
             ops.linear_grad_sink = self.stem.sink if self._stem_sink_active else None
             try:
                 with ops.deferred_wgrad():
-                    loss.backward(gradient=self._root)  # train.py:384
+                    if term is None:
+                        loss.backward(gradient=self._root)  # train.py:384
+                    else:       # one pass: the critic's image gradient meets the spectral one on the adjoint's store
+                        torch.autograd.backward([loss, term], [self._root, self._root])
             finally:
                 ops.linear_grad_sink = None
         finally:
             for p in d_params:
                 p.requires_grad_(True)
-        return {"G_loss": loss.detach()}
+        if self._spec_targets is None:
+            return {"G_loss": loss.detach()}
+        return {"G_loss": loss.detach(), "G_spec_loss": term.detach() if term is not None else torch.zeros((), device=self.device)}
 
     def materialize_stem_grad(self):
         """After a g_step that skipped the stem's gradient (fused_stem), write it into the stem weight's .grad from that step's
@@ -1698,7 +1772,11 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     cfg.<prefix>_period > 0, for a row of metric_table.METRICS: rank 0 scores every checkpoint whose epoch is a multiple of it
     (scoring.score_due, in table order) before it is written; the other ranks wait at the checkpoint's barrier.
     draws(epoch, k, n_global) -> {"z_d", "z_gp", "eps", "z_g"}: optional global latent / epsilon tensors of batch k of the epoch
-    (host or device), sliced like the images -- a reproducible run, comparable between rank counts."""
+    (host or device), sliced like the images -- a reproducible run, comparable between rank counts.
+    A trainer with spec_loss_lambda > 0: the data's mean radial spectrum (metrics.spectral_target over cfg.spec_loss_images images,
+    seed cfg.spec_loss_seed) is computed and handed to the trainer at the start and whenever a growth event changed the image size
+    -- by every rank from the whole data set, a checksum of it guarded by `assert_same` -- and G_spec_loss is a sixth monitor: in
+    the sums, the series and the status line.  With the switch off there are five, as ever."""
     import time
     from .utils import Calculate_D_steps, plot_gen_samples
     adapt_period = 100                                                # Disc_adapt_update_period, train.py:190
@@ -1713,6 +1791,24 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     if ranks.rank != 0:
         log = lambda *a, **k: None    # noqa: E731
     names = ["score_real", "score_fake", "D_loss", "G_loss", "D_grad_pen"]
+    spectral = bool(getattr(trainer, "spectral_enabled", False))
+    if spectral:
+        names.append("G_spec_loss")
+    target_size = [None]              # the image size the trainer's spectral target was last computed for
+
+    def refresh_spectral_target():
+        size = int(G.image_size)
+        if not spectral or size == target_size[0]:
+            return
+        target_size[0] = size
+        if size < ops.SPECLOSS_MIN:
+            return                    # (the trainer says so itself, once)
+        from . import metrics
+        trainer.set_spectral_target(size, metrics.spectral_target(dataset, size, n_images=int(getattr(cfg, 'spec_loss_images', 256)),
+                                                                  seed=int(getattr(cfg, 'spec_loss_seed', 0)), device=dev))
+        ranks.assert_same(trainer.spectral_target_checksum(size), "the spectral target")
+        log("spectral target at {}x{}: mean radial spectrum of {} images, weight {:g}, floor {:g}".format(
+            size, size, int(getattr(cfg, 'spec_loss_images', 256)), trainer.spec_loss_lambda, trainer.spec_loss_floor))
     on_gpu = dev.type == "cuda"       # (a CPU device: the stub trainers of the host tests; monitors are then read synchronously)
     pinned = torch.zeros(2, len(names), pin_memory=on_gpu)
     events = [None, None]
@@ -1725,6 +1821,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
             name = "Samples_{}{}_{:d}.png".format("ema_" if averaged else "", cfg.ID, epoch)
             plot_gen_samples(G, N_images=16, seed=0, filename=os.path.join(samples_dir, name))
     dataset.set_image_size(G.image_size)
+    refresh_spectral_target()
     start_time = time.time()
 
     def consume(slot):
@@ -1748,12 +1845,13 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
                 "Loss_fake (<D(G(z))>):{: >#7.4g}, G_loss:{: >#7.4g}, D_loss:{: >#7.4g}, D_grad_pen:{: >#7.4g}".format(
                     ep, "{:.3f}".format((time.time() - start_time) / done) if done > 0 else "----",
                     trainer.opt_g.param_groups[0]["lr"], G.alpha_value(), G.image_size, G.image_size, vals[0], vals[1], vals[3],
-                    vals[2], vals[4]))
+                    vals[2], vals[4]) + (", G_spec_loss:{: >#7.4g}".format(vals[5]) if spectral else ""))
 
     for epoch in range(epoch_init, epoch_final):
         if trainer.start_epoch(epoch, cfg.transit_sch):
             dataset.set_image_size(G.image_size)
             ranks.assert_same(G.image_size, "the image size after a growth event")
+            refresh_spectral_target()
         if on_epoch is not None:
             on_epoch(epoch, trainer)
         if getattr(trainer, "diffaug_enabled", False):                # the private stream restarts from (seed, epoch, rank): resumable
@@ -1772,10 +1870,10 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
             stats, own = _run_batch(trainer, images, n, ranks, use_graph and (draws is None or n_d_steps == 1), own, statics)
             g_loss = _monitored_g_loss(stats, own, trainer, ranks, images, n, sim_lambda)
             acc += images.size(0) * torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss,
-                                                 stats["D_grad_pen"].float()])
+                                                 stats["D_grad_pen"].float()] + ([stats["G_spec_loss"]] if spectral else []))
         slot = epoch & 1
         consume(slot)
-        ranks.sum_(acc)                                                # N ranks: ONE all-reduce per epoch, of the five sums
+        ranks.sum_(acc)                                                # N ranks: ONE all-reduce per epoch, of the five (or six) sums
         pinned[slot].copy_(acc / n_images, non_blocking=True)
         events[slot] = torch.cuda.Event() if on_gpu else True
         if on_gpu:
@@ -1935,6 +2033,13 @@ def build_arg_parser():
                    help='form of the gradient penalty: gp, the two-sided one on interpolates; lp, one-sided; r1, zero-centred on the reals')
     p.add_argument('--grad_pen_interval', type=int, default=1, help='apply the penalty every K-th iteration with K times the weight '
                                                                     '(lazy regularisation); 1: every iteration')
+    p.add_argument('--spec_loss_lambda', type=float, default=0.0, help='weight of the spectral regularisation of the PG generator: '
+                                                                       'its images\' radial power spectrum is pulled towards the '
+                                                                       'data\'s (Durall et al. 2020); 0: off')
+    p.add_argument('--spec_loss_floor', type=float, default=1e-3, help='floor on the ratio of the spectra inside the logarithm '
+                                                                       '(1e-3: -30 dB)')
+    p.add_argument('--spec_loss_images', type=int, default=256, help='images the data\'s mean radial spectrum is taken over, per stage')
+    p.add_argument('--spec_loss_seed', type=int, default=0, help='seed of the private augmentation stream those images are drawn with')
     for m in METRICS:                                                    # one group of integer flags per checkpoint metric
         for name, _, default, text in settings(m):
             p.add_argument('--' + name, type=int, default=default, help=text)
@@ -1975,6 +2080,7 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     wgan without pggan: a WGANTrainer (weight clipping at 0.01, reference train.py:489-490); wgan with pggan is refused.
     config.lsgan: the PG trainer's objective is "lsgan" instead of "wasserstein" (refused for the WGAN nets).
     config.grad_pen_mode / config.grad_pen_interval: the PG trainer's penalty form and lazy-regularisation interval (likewise refused).
+    config.spec_loss_lambda / config.spec_loss_floor: the PG trainer's spectral regularisation of the generator (likewise refused).
     distributed: a launched rank -- the trainer exchanges over `process_group` (None: the default group); the WGAN nets then train
     with synchronised BatchNorm."""
     if config.wgan and config.pggan:
@@ -1983,7 +2089,10 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
                diffaug_seed=getattr(config, 'diffaug_seed', 0))
     lsgan = bool(getattr(config, 'lsgan', False))
     pen = (getattr(config, 'grad_pen_mode', 'gp'), getattr(config, 'grad_pen_interval', 1))
+    spec_lambda = getattr(config, 'spec_loss_lambda', 0.0)
     if config.wgan:
+        if spec_lambda:
+            raise ValueError("spec_loss_lambda > 0 is not available for the WGAN nets (wgan=True, pggan=False)")
         if lsgan:
             raise ValueError("lsgan=True is not available for the WGAN nets (wgan=True, pggan=False)")
         if getattr(config, 'mbstd_group', 0):
@@ -2003,6 +2112,8 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
         kw["objective"] = "lsgan"
     if pen != ("gp", 1):                # (the defaults are left to the trainer, like the objective's)
         kw["grad_pen_mode"], kw["grad_pen_interval"] = pen
+    if spec_lambda:                     # (likewise)
+        kw["spec_loss_lambda"], kw["spec_loss_floor"] = spec_lambda, getattr(config, 'spec_loss_floor', 1e-3)
     if config.RMSprop:
         return PGGANTrainer(G, D, optimizer="rmsprop", **kw)
     return PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)

@@ -47,7 +47,8 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # per-tensor step counts (the reference does not save optimiser state at all).  A trainer that keeps an averaged generator
 # (train.py, `ema_beta`) adds 'Generator_ema_state': the averaged weights under the keys of 'Generator_state', tensors only.  The
 # A PGGANTrainer writes 'objective' ("wasserstein" or "lsgan", train.py `objective=`) beside it; a file without the key is Wasserstein.  It
-# also writes 'grad_pen_mode', 'grad_pen_interval' and 'grad_pen_iteration' (PENALTY_KEYS; a file without them is 'gp' / 1 / 0).  A
+# also writes 'grad_pen_mode', 'grad_pen_interval' and 'grad_pen_iteration' (PENALTY_KEYS; a file without them is 'gp' / 1 / 0), and
+# 'spec_loss_lambda' and 'spec_loss_floor' (SPECTRAL_KEYS; a file without them is 0 / 1e-3; resuming under other values is logged).  A
 # critic built with mbstd_group > 0 lists 'mbstd_group' in 'Discriminator_attrs' and holds 'layers.<k>.weight_std' in its state; a file
 # without the attribute holds the reference's critic.  The
 # reference's loaders read the keys they know and ignore the rest (utils.py:185-199 index five series keys and the two attribute
@@ -98,6 +99,9 @@ OBJECTIVE_KEY = 'objective'      # of the trainer that wrote the file; a file wi
 # of a PGGANTrainer's penalty (train.py `grad_pen_mode=`, `grad_pen_interval=`) and its count of iterations; the values of a file without
 # the keys
 PENALTY_KEYS = {'grad_pen_mode': 'gp', 'grad_pen_interval': 1, 'grad_pen_iteration': 0}
+# of a PGGANTrainer's spectral regularisation of the generator (train.py `spec_loss_lambda=`, `spec_loss_floor=`); the values of a file
+# without the keys.  Weights like grad_pen_lambda: a run may be resumed under other values, which is logged
+SPECTRAL_KEYS = {'spec_loss_lambda': 0.0, 'spec_loss_floor': 1e-3}
 SWD_KEY, MSSSIM_KEY, SPECTRUM_KEY, MORPH_KEY, SKELETON_KEY, SHOLL_KEY, BRANCH_KEY = (m.key for m in METRICS)
 
 
@@ -142,6 +146,9 @@ class Checkpointer:
             if hasattr(self.trainer, 'grad_pen_mode'):
                 for key, default in PENALTY_KEYS.items():
                     checkpoint_dict[key] = type(default)(getattr(self.trainer, key))
+            if hasattr(self.trainer, 'spec_loss_lambda'):
+                for key in SPECTRAL_KEYS:
+                    checkpoint_dict[key] = float(getattr(self.trainer, key))
         for m in METRICS:
             if getattr(self, m.key):
                 checkpoint_dict[m.key] = [dict(entry) for entry in getattr(self, m.key)]
@@ -169,6 +176,12 @@ class Checkpointer:
             if saved != own:
                 raise ValueError('{} was trained with grad_pen_mode={}, grad_pen_interval={} and cannot be resumed with grad_pen_mode={}, '
                                  'grad_pen_interval={}'.format(source, saved[0], saved[1], own[0], own[1]))
+        if filename is None and hasattr(self.trainer, 'spec_loss_lambda'):
+            saved = tuple(float(checkpoint_dict.get(k, d)) for k, d in SPECTRAL_KEYS.items())
+            own = (float(self.trainer.spec_loss_lambda), float(self.trainer.spec_loss_floor))
+            if saved != own:
+                print('{} was trained with spec_loss_lambda={:g}, spec_loss_floor={:g}; the run goes on with spec_loss_lambda={:g}, '
+                      'spec_loss_floor={:g}'.format(source, saved[0], saved[1], own[0], own[1]))
         # the critic's minibatch standard-deviation group (models.Discriminator_PG(mbstd_group=); a file without the key is 0, off) changes
         # the head's parameters and its equalised-LR constant: the file's weights mean something else under another value
         saved_group = int(checkpoint_dict.get('Discriminator_attrs', {}).get('mbstd_group', 0))
