@@ -238,7 +238,7 @@ int ngan_wloss_head_bwd(const float* scores, int n_real, int n_fake, float drift
                         const float* g_fake, float* g_scores, void* stream);
 
 /* ---- scalar heads of the objectives beside the Wasserstein one (least squares): declared in ngan_objectives.h, which this header
- * includes -- the table of this file, 165 entry points, is pinned by the suite as it stands; objectives are an extension section ---- */
+ * includes -- one ABI: a caller includes ngan.h alone, and _C.py binds this file and its extension sections from one table ---- */
 #include "ngan_objectives.h"
 /* ---- minibatch standard deviation of the PG critic's head (opt-in): declared in ngan_mbstd.h, an extension section likewise ---- */
 #include "ngan_mbstd.h"

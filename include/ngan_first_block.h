@@ -1,5 +1,5 @@
 /* ngan_first_block.h -- extension section of ngan.h (which includes it: include ngan.h, not this file): the launch plan of the folded
- * critic first block (ngan_first_block_fwd / _bwd / _dx of ngan.h) as a host query.  Python binding: _C.FIRST_BLOCK_NON_STATUS.
+ * critic first block (ngan_first_block_fwd / _bwd / _dx of ngan.h) as a host query.  Python binding: _C.NON_STATUS.
  *
  * ngan_first_block_plan makes no HIP call and launches nothing.  out4 = { workgroups along x (256 / (N/4) pixels each), image rows
  * per workgroup of bwd's sums kernel, row chunks per sample, slabs = their product with B }.  The rows start at 8 and double until the

@@ -1,7 +1,7 @@
 /* ngan_geoaug.h -- extension section of ngan.h (which includes it: include ngan.h, not this file): the geometric groups of the
  * differentiable augmentation -- mirror and quarter turns ("blit"), isotropic scale and rotation ("geometry") -- as one bilinear
  * resampling per sample, and its adjoint.  Same conventions as ngan.h: status-returning, the trailing void* is the hipStream_t,
- * device pointers, no state between calls.  Python binding: _C.GEOAUG_SIGNATURES.
+ * device pointers, no state between calls.  Python binding: _C.SIGNATURES.
  *
  * Images are contiguous fp32 (B, C, R, R), square, R a multiple of 4 (4 .. 16384), fp32 in every arithmetic mode.  Sample n has a
  * 32-byte row of eight floats {a00, a01, a02, a10, a11, a12, 0, 0} that maps output pixel (row i, column j) to a source position in

@@ -1,7 +1,7 @@
 /* ngan_mbstd.h -- extension section of ngan.h (which includes it: include ngan.h, not this file): the minibatch standard-deviation
  * layer of the PG critic's head (Karras et al. 2018, section 3), closed under double-backward.  Same conventions as ngan.h:
  * status-returning, the trailing void* is the hipStream_t, device pointers, fp32 channels-last tensors, no state between calls.
- * Python binding: _C.MBSTD_SIGNATURES / _C.MBSTD_NON_STATUS.
+ * Python binding: _C.SIGNATURES / _C.NON_STATUS.
  *
  * x is (B, H, W, C), C a multiple of 4, J = H W C.  The batch holds `segments` critic calls of B / segments samples each; inside a
  * segment, consecutive runs of G_eff samples form a group (G_eff divides B / segments, so no group spans two segments).  Per group g

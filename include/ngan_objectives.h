@@ -1,6 +1,6 @@
 /* ngan_objectives.h -- extension section of ngan.h (which includes it: include ngan.h, not this file): the scalar heads of the
  * objectives a trainer can select besides the Wasserstein one.  Same conventions as ngan.h: status-returning, the trailing void* is the
- * hipStream_t, device pointers, no state between calls.  Python binding: _C.OBJECTIVE_SIGNATURES. */
+ * hipStream_t, device pointers, no state between calls.  Python binding: _C.SIGNATURES. */
 #ifndef NGAN_OBJECTIVES_H
 #define NGAN_OBJECTIVES_H
 

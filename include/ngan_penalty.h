@@ -1,6 +1,6 @@
 /* ngan_penalty.h -- extension section of ngan.h (which includes it: include ngan.h, not this file): the selectable forms of the
  * gradient penalty beside the reference's two-sided one.  Same conventions as ngan.h: status-returning, the trailing void* is the
- * hipStream_t, device pointers, no state between calls.  Python binding: _C.PENALTY_SIGNATURES.
+ * hipStream_t, device pointers, no state between calls.  Python binding: _C.SIGNATURES.
  *
  * form 1, one-sided (WGAN-LP, Petzka et al. 2018):   phi(n) = max(0, n - 1)^2
  * form 2, zero-centred (R1, Mescheder et al. 2018):  phi(n) = n^2 / 2

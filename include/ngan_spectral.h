@@ -1,7 +1,7 @@
 /* ngan_spectral.h -- extension section of ngan.h (which includes it: include ngan.h, not this file): the spectral regularisation of
  * the generator (Durall et al. 2020), a loss on the radial power spectrum of ngan_spectrum_radial.  Same conventions as ngan.h:
  * status-returning, the trailing void* is the hipStream_t, device pointers, no state between calls, fixed summation order, no atomics.
- * Python binding: _C.SPECTRAL_SIGNATURES / _C.SPECTRAL_NON_STATUS; kernels: csrc/specloss.hip.
+ * Python binding: _C.SIGNATURES / _C.NON_STATUS; kernels: csrc/specloss.hip.
  *
  * Images are fp32 (B, 1, R, R) -- one colour channel, so planar and channels-last coincide -- R a power of two in 16 .. 1024,
  * B = 1 .. 65535, K = R/2 + 1.  With S the radial spectrum (window as ngan_spectrum_radial's), a target t[k], a floor d > 0:

@@ -15,7 +15,8 @@ _P, _I, _L, _F, _Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_floa
 _D = ctypes.c_double
 CONV_SKIP_BORDER = 1     # NGAN_CONV_SKIP_BORDER (include/ngan.h): per-call flag of ngan_conv3x3_fwd / _fwd_ex
 
-# name -> argument types (the trailing void* stream included), mirroring include/ngan.h
+# The whole C ABI (include/ngan.h and the ngan_*.h it includes) in two tables; tests/test_host_cpu.py holds every row to its prototype.
+# name -> argument types (the trailing void* stream included) of the status-returning entry points
 SIGNATURES = {
     "ngan_conv3x3_pack_weights": [_P, _P, _I, _I, _I, _F, _I, _P],
     "ngan_conv3x3_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _P],
@@ -128,6 +129,27 @@ SIGNATURES = {
     "ngan_geom_sholl": [_P, _P, _P, _P, _P, _I, _I, _P],
     # arbor branches (include/ngan.h, last section; metrics.py)
     "ngan_branch_graph": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    # selectable objectives (include/ngan_objectives.h; the least-squares heads of loss_functions)
+    "ngan_lsloss_head": [_P, _I, _I, _F, _F, _P, _P, _P, _P],
+    "ngan_lsloss_head_bwd": [_P, _I, _I, _F, _F, _P, _P, _P, _P, _P],
+    # minibatch standard deviation of the critic head (include/ngan_mbstd.h; ops.MinibatchStd, ops.StdField*)
+    "ngan_mbstd_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ngan_mbstd_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ngan_mbstd_bwdbwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ngan_stdfield_add": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "ngan_stdfield_ds": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "ngan_stdfield_dw": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
+    # geometric groups of the differentiable augmentation (include/ngan_geoaug.h; ops.DiffGeometry)
+    "ngan_diffgeo_params": [_P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "ngan_diffgeo_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "ngan_diffgeo_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    # one-sided and zero-centred gradient penalties (include/ngan_penalty.h; ops.PenaltyHead)
+    "ngan_penalty_head": [_P, _I, _L, _I, _F, _P, _P, _P, _P],
+    "ngan_penalty_bwd": [_P, _P, _I, _L, _I, _F, _P, _P, _P],
+    # spectral regularisation of the generator (include/ngan_spectral.h; ops.SpectralLoss)
+    "ngan_specloss_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ngan_specloss_head": [_P, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P],
+    "ngan_specloss_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
 }
 # "bf16 activation storage" section of include/ngan.h: ngan_bf16_<op> has the argument list of ngan_<op> (the activation pointers are
 # bf16 tensors); the two convolution entry points carry no precision / flags arguments
@@ -141,60 +163,7 @@ for _op in ("lrelu_pixelnorm_fwd", "lrelu_pixelnorm_bwd", "lrelu_pixelnorm_bwd2"
 SIGNATURES["ngan_bf16_conv3x3_fwd"] = [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P]
 SIGNATURES["ngan_bf16_conv3x3_wgrad"] = [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]
 
-# include/ngan_objectives.h, the extension section of the header: the scalar heads of the selectable objectives (status-returning,
-# called through `call` like the entries above; listed by `objective_symbols`, not by `exported_symbols`, which is ngan.h's own table)
-OBJECTIVE_SIGNATURES = {
-    "ngan_lsloss_head": [_P, _I, _I, _F, _F, _P, _P, _P, _P],
-    "ngan_lsloss_head_bwd": [_P, _I, _I, _F, _F, _P, _P, _P, _P, _P],
-}
-
-# include/ngan_mbstd.h, the second extension section: the critic head's minibatch standard deviation (ops.MinibatchStd, ops.StdField*);
-# listed by `mbstd_symbols`, like the objectives' table
-MBSTD_SIGNATURES = {
-    "ngan_mbstd_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ngan_mbstd_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ngan_mbstd_bwdbwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ngan_stdfield_add": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "ngan_stdfield_ds": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "ngan_stdfield_dw": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
-}
-MBSTD_NON_STATUS = {
-    "ngan_mbstd_workspace_doubles": ([_I, _I, _I, _I, _I], _L),
-}
-
-# include/ngan_geoaug.h, the third extension section: the geometric groups of the differentiable augmentation (ops.DiffGeometry);
-# listed by `geoaug_symbols`, like the tables above
-GEOAUG_SIGNATURES = {
-    "ngan_diffgeo_params": [_P, _P, _I, _I, _I, _I, _I, _F, _P],
-    "ngan_diffgeo_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    "ngan_diffgeo_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-}
-
-# include/ngan_penalty.h, the fourth extension section: the one-sided and zero-centred forms of the gradient penalty (ops.PenaltyHead);
-# listed by `penalty_symbols`, like the tables above
-PENALTY_SIGNATURES = {
-    "ngan_penalty_head": [_P, _I, _L, _I, _F, _P, _P, _P, _P],
-    "ngan_penalty_bwd": [_P, _P, _I, _L, _I, _F, _P, _P, _P],
-}
-
-# include/ngan_first_block.h, the fifth extension section: the launch plan of the folded critic first block as a host query
-# (ops.first_block_fusable); listed by `first_block_symbols`, like the tables above
-FIRST_BLOCK_NON_STATUS = {
-    "ngan_first_block_plan": ([_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)], _I),
-}
-
-# include/ngan_spectral.h, the sixth extension section: the spectral regularisation of the generator (ops.SpectralLoss); listed by
-# `spectral_symbols`, like the tables above
-SPECTRAL_SIGNATURES = {
-    "ngan_specloss_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "ngan_specloss_head": [_P, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P],
-    "ngan_specloss_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-}
-SPECTRAL_NON_STATUS = {
-    "ngan_specloss_fwd_workspace_bytes": ([_I, _I, _I], _Z),
-    "ngan_specloss_bwd_workspace_bytes": ([_I, _I, _I], _Z),
-}
-
+# name -> (argument types, return type): host-side queries and the entry points that return no status
 NON_STATUS = {
     "ngan_version": ([], ctypes.c_char_p),
     "ngan_last_error": ([], ctypes.c_char_p),
@@ -227,6 +196,11 @@ NON_STATUS = {
     "ngan_morph_workspace_bytes": ([_I, _I], _Z),
     "ngan_geom_workspace_bytes": ([_I, _I], _Z),
     "ngan_branch_workspace_bytes": ([_I, _I], _Z),
+    "ngan_mbstd_workspace_doubles": ([_I, _I, _I, _I, _I], _L),
+    # the launch plan of the folded critic first block as a host query (include/ngan_first_block.h; ops.first_block_fusable)
+    "ngan_first_block_plan": ([_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)], _I),
+    "ngan_specloss_fwd_workspace_bytes": ([_I, _I, _I], _Z),
+    "ngan_specloss_bwd_workspace_bytes": ([_I, _I, _I], _Z),
 }
 
 _lib = None
@@ -240,14 +214,11 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                f"or `make -C neuron-gan_amd/csrc`; there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in (list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(MBSTD_SIGNATURES.items())
-                               + list(GEOAUG_SIGNATURES.items()) + list(PENALTY_SIGNATURES.items())
-                               + list(SPECTRAL_SIGNATURES.items())):
+        for name, argtypes in SIGNATURES.items():
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
-        for name, (argtypes, restype) in (list(NON_STATUS.items()) + list(MBSTD_NON_STATUS.items()) + list(FIRST_BLOCK_NON_STATUS.items())
-                                          + list(SPECTRAL_NON_STATUS.items())):
+        for name, (argtypes, restype) in NON_STATUS.items():
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -257,30 +228,6 @@ def lib():
 
 def exported_symbols():
     return list(SIGNATURES) + list(NON_STATUS)
-
-
-def objective_symbols():
-    return list(OBJECTIVE_SIGNATURES)
-
-
-def mbstd_symbols():
-    return list(MBSTD_SIGNATURES) + list(MBSTD_NON_STATUS)
-
-
-def geoaug_symbols():
-    return list(GEOAUG_SIGNATURES)
-
-
-def penalty_symbols():
-    return list(PENALTY_SIGNATURES)
-
-
-def spectral_symbols():
-    return list(SPECTRAL_SIGNATURES) + list(SPECTRAL_NON_STATUS)
-
-
-def first_block_symbols():
-    return list(FIRST_BLOCK_NON_STATUS)
 
 
 def mbstd_workspace_doubles(B, H, W, C, G_eff) -> int:

@@ -131,6 +131,21 @@ def _k(name, *acts):
             return "ngan_bf16_" + name[5:]
     return name
 
+
+def _conv_launch(x, packed, bias, y, rn, ay, arn, yp, b, h, w, k, n, resample, epilogue, out_mode, slope, eps, prec, flags=0):
+    """one launch of the extended 3x3 convolution entry point for x's storage type: the bf16 one is a single kernel family and takes
+    no precision / flags arguments (include/ngan.h)"""
+    if x.dtype == torch.bfloat16:
+        _C.call("ngan_bf16_conv3x3_fwd", x, packed, bias, y, rn, ay, arn, yp, b, h, w, k, n, resample, epilogue, out_mode, slope, eps)
+    else:
+        _C.call("ngan_conv3x3_fwd_ex", x, packed, bias, y, rn, ay, arn, yp, b, h, w, k, n, resample, epilogue, out_mode, slope, eps, prec, flags)
+
+
+def _check_handoff(ay, gx):
+    """the linked producer's output has to be the tensor whose gradient gx is"""
+    if tuple(ay.shape) != tuple(gx.shape):
+        raise RuntimeError(f"PixelNorm hand-off: producer output {tuple(ay.shape)} is not the conv input {tuple(gx.shape)}")
+
 PIXELNORM_EPS = 1e-8  # models.py:105 of the reference
 
 # ---------------------------------------------------------------------------------------------------------
@@ -295,6 +310,11 @@ def _bf16_prec(b, h, w, k, n, resample):
     return 5
 
 
+def _conv_prec(x, b, h, w, k, n, resample):
+    """precision code to pack with and to launch with for a conv on the activations x: by storage type, then by mode and shape"""
+    return _bf16_prec(b, h, w, k, n, resample) if x.dtype == torch.bfloat16 else _C.conv3x3_algorithm(b, h, w, k, n, resample, _conv_precision)
+
+
 def _n_chunks(n):
     """Output-channel counts one kernel launch takes are 16, 32, 64 and 128 (include/ngan.h); any other multiple of 16 -- the
     reference's wide presets have 256-channel blocks, configs/config.py:87-98 -- is computed in chunks of those sizes, largest
@@ -339,17 +359,15 @@ def _run_conv(x, weight, bias, resample, scale, epilogue, slope, keep_pooled=Non
         if epilogue:
             _C.call(_k("ngan_lrelu_pixelnorm_fwd", y), y, None, y, rn, b * h * w, cout, float(slope), PIXELNORM_EPS)
         return y, rn
-    if bf:      # bf16 activation storage: one kernel family, resampling (pool / bilinear) while the tile is staged
-        _C.call("ngan_bf16_conv3x3_fwd", x, _packed(weight, 0, scale, _bf16_prec(b, h, w, cin, cout, resample)), bias, y, rn, None, None, None,
-                b, h, w, cin, cout, resample, epilogue, 0, float(slope), PIXELNORM_EPS)
-        return y, rn
-    prec = _C.conv3x3_algorithm(b, h, w, cin, cout, resample, _conv_precision)
+    prec = _conv_prec(x, b, h, w, cin, cout, resample)
     packed = _packed(weight, 0, scale, prec)
-    if pool_out and epilogue == EPI_LRELU_PN and _pool_out_allowed and _C.conv3x3_pooled_output(b, h, w, cin, cout, resample, prec):
+    yp = None
+    if not bf and pool_out and epilogue == EPI_LRELU_PN and _pool_out_allowed and _C.conv3x3_pooled_output(b, h, w, cin, cout, resample, prec):
         yp = torch.empty((b, h // 2, w // 2, cout), device=x.device, dtype=torch.float32)
-        _C.call("ngan_conv3x3_fwd_ex", x, packed, bias, y, rn, None, None, yp, b, h, w, cin, cout, resample, epilogue, 0, float(slope),
-                PIXELNORM_EPS, prec, 0)
-        y._ngan_pooled = (yp, y._version)       # valid for exactly this tensor object in exactly this state: _pooled_side
+    if bf or yp is not None:    # (bf16 activation storage: one kernel family, resampling (pool / bilinear) while the tile is staged)
+        _conv_launch(x, packed, bias, y, rn, None, None, yp, b, h, w, cin, cout, resample, epilogue, 0, float(slope), PIXELNORM_EPS, prec)
+        if yp is not None:
+            y._ngan_pooled = (yp, y._version)       # valid for exactly this tensor object in exactly this state: _pooled_side
         return y, rn
     _C.call("ngan_conv3x3_fwd", x, packed, bias, y, rn, b, h, w, cin, cout, resample, epilogue, 0, float(slope), PIXELNORM_EPS, prec,
             _C.CONV_SKIP_BORDER if prec == 3 else 0)
@@ -382,55 +400,29 @@ def _run_dgrad(g, weight, resample, scale, link=None):
                 _C.call(_k("ngan_up2_adjoint", full), full, gx, b, h // 2, w // 2, cin)
             return gx
         if link is not None:
-            if tuple(ay.shape) != tuple(full.shape):
-                raise RuntimeError(f"PixelNorm hand-off: producer output {tuple(ay.shape)} is not the conv input {tuple(full.shape)}")
+            _check_handoff(ay, full)
             _C.call(_k("ngan_lrelu_pixelnorm_bwd", full), full, None, ay, arn, full, b * oh * ow, cin, slope)
         return full
-    epi = EPI_PN_BWD if link is not None else EPI_NONE
-    if g.dtype == torch.bfloat16:
-        packed = _packed(weight, 1, scale, _bf16_prec(b, h, w, cout, cin, 0))
-        if link is not None and ay.dtype != g.dtype:
-            raise RuntimeError("PixelNorm hand-off: producer output and gradient differ in storage type")
-        if resample == RES_UP2:
-            gfull = torch.empty((b, h, w, cin), device=g.device, dtype=g.dtype)
-            _C.call("ngan_bf16_conv3x3_fwd", g, packed, None, gfull, None, None, None, None, b, h, w, cout, cin, 0, EPI_NONE, 0, 0.0, 0.0)
-            gx = torch.empty((b, h // 2, w // 2, cin), device=g.device, dtype=g.dtype)
-            if link is not None:
-                if tuple(ay.shape) != tuple(gx.shape):
-                    raise RuntimeError(f"PixelNorm hand-off: producer output {tuple(ay.shape)} is not the conv input {tuple(gx.shape)}")
-                _C.call("ngan_bf16_up2_adjoint_pnbwd", gfull, ay, arn, gx, b, h // 2, w // 2, cin, slope)
-            else:
-                _C.call("ngan_bf16_up2_adjoint", gfull, gx, b, h // 2, w // 2, cin)
-            return gx
-        pool = resample == RES_POOL2
-        gx = torch.empty((b, 2 * h, 2 * w, cin) if pool else (b, h, w, cin), device=g.device, dtype=g.dtype)
-        if link is not None and tuple(ay.shape) != tuple(gx.shape):
-            raise RuntimeError(f"PixelNorm hand-off: producer output {tuple(ay.shape)} is not the conv input {tuple(gx.shape)}")
-        _C.call("ngan_bf16_conv3x3_fwd", g, packed, None, gx, None, ay, arn, None, b, h, w, cout, cin, 0, epi, 1 if pool else 0, slope, 0.0)
-        return gx
-    prec = _C.conv3x3_algorithm(b, h, w, cout, cin, 0, _conv_precision)
+    prec = _conv_prec(g, b, h, w, cout, cin, 0)
     packed = _packed(weight, 1, scale, prec)
-    if resample == RES_POOL2:
-        gx = torch.empty((b, 2 * h, 2 * w, cin), device=g.device, dtype=torch.float32)
-        if link is not None and tuple(ay.shape) != tuple(gx.shape):
-            raise RuntimeError(f"PixelNorm hand-off: producer output {tuple(ay.shape)} is not the conv input {tuple(gx.shape)}")
-        _C.call("ngan_conv3x3_fwd_ex", g, packed, None, gx, None, ay, arn, None, b, h, w, cout, cin, 0, epi, 1, slope, 0.0, prec, 0)
-        return gx
-    if resample == RES_UP2:
-        gfull = torch.empty((b, h, w, cin), device=g.device, dtype=torch.float32)
-        _C.call("ngan_conv3x3_fwd_ex", g, packed, None, gfull, None, None, None, None, b, h, w, cout, cin, 0, EPI_NONE, 0, 0.0, 0.0, prec, 0)
-        gx = torch.empty((b, h // 2, w // 2, cin), device=g.device, dtype=torch.float32)
+    if link is not None and g.dtype == torch.bfloat16 and ay.dtype != g.dtype:
+        raise RuntimeError("PixelNorm hand-off: producer output and gradient differ in storage type")
+    if resample == RES_UP2:     # the conv at full size, then the adjoint of the bilinear x2 (with the producer's PixelNorm backward)
+        gfull = torch.empty((b, h, w, cin), device=g.device, dtype=g.dtype)
+        _conv_launch(g, packed, None, gfull, None, None, None, None, b, h, w, cout, cin, 0, EPI_NONE, 0, 0.0, 0.0, prec)
+        gx = torch.empty((b, h // 2, w // 2, cin), device=g.device, dtype=g.dtype)
         if link is not None:
-            if tuple(ay.shape) != tuple(gx.shape):
-                raise RuntimeError(f"PixelNorm hand-off: producer output {tuple(ay.shape)} is not the conv input {tuple(gx.shape)}")
-            _C.call("ngan_up2_adjoint_pnbwd", gfull, ay, arn, gx, b, h // 2, w // 2, cin, slope)
+            _check_handoff(ay, gx)
+            _C.call(_k("ngan_up2_adjoint_pnbwd", gfull), gfull, ay, arn, gx, b, h // 2, w // 2, cin, slope)
         else:
-            _C.call("ngan_up2_adjoint", gfull, gx, b, h // 2, w // 2, cin)
+            _C.call(_k("ngan_up2_adjoint", gfull), gfull, gx, b, h // 2, w // 2, cin)
         return gx
-    gx = torch.empty((b, h, w, cin), device=g.device, dtype=torch.float32)
-    if link is not None and tuple(ay.shape) != tuple(gx.shape):
-        raise RuntimeError(f"PixelNorm hand-off: producer output {tuple(ay.shape)} is not the conv input {tuple(gx.shape)}")
-    _C.call("ngan_conv3x3_fwd_ex", g, packed, None, gx, None, ay, arn, None, b, h, w, cout, cin, 0, epi, 0, slope, 0.0, prec, 0)
+    pool = resample == RES_POOL2    # out_mode 1: the adjoint of the 2x2 average in the kernel's store
+    gx = torch.empty((b, 2 * h, 2 * w, cin) if pool else (b, h, w, cin), device=g.device, dtype=g.dtype)
+    if link is not None:
+        _check_handoff(ay, gx)
+    _conv_launch(g, packed, None, gx, None, ay, arn, None, b, h, w, cout, cin, 0, EPI_PN_BWD if link is not None else EPI_NONE,
+                 1 if pool else 0, slope, 0.0, prec)
     return gx
 
 
@@ -638,13 +630,9 @@ class ConvLReLUPNToImage(Function):
         y = torch.empty((b, h, w, cout), device=x.device, dtype=x.dtype) if keep else None
         rn = torch.empty((b, h, w), device=x.device, dtype=torch.float32) if keep else None
         t = torch.empty((b, h, w, 1), device=x.device, dtype=torch.float32)
-        if x.dtype == torch.bfloat16:
-            _C.call("ngan_bf16_conv3x3_fwd", x, _packed(weight, 0, scale, _bf16_prec(b, h, w, cin, cout, resample)), bias, y, rn,
-                    w_img.detach().reshape(-1), None, t, b, h, w, cin, cout, resample, EPI_TO_IMAGE, 0, float(slope), PIXELNORM_EPS)
-        else:
-            prec = _C.conv3x3_algorithm(b, h, w, cin, cout, resample, _conv_precision)
-            _C.call("ngan_conv3x3_fwd_ex", x, _packed(weight, 0, scale, prec), bias, y, rn, w_img.detach().reshape(-1), None, t,
-                    b, h, w, cin, cout, resample, EPI_TO_IMAGE, 0, float(slope), PIXELNORM_EPS, prec, 0)
+        prec = _conv_prec(x, b, h, w, cin, cout, resample)
+        _conv_launch(x, _packed(weight, 0, scale, prec), bias, y, rn, w_img.detach().reshape(-1), None, t,
+                     b, h, w, cin, cout, resample, EPI_TO_IMAGE, 0, float(slope), PIXELNORM_EPS, prec)
         if keep:
             ctx.save_for_backward(x, weight, y, rn, t, w_img)
         ctx.has_bias = bias is not None

@@ -184,8 +184,7 @@ def test_entry_points_are_bound_and_validate_on_the_host(ngan):
     one = ctypes.c_void_p(64)            # any non-null, 16-byte aligned address: every check below comes before the launch
     odd = ctypes.c_void_p(68)
     N = None
-    assert ngan._C.geoaug_symbols() == ["ngan_diffgeo_params", "ngan_diffgeo_fwd", "ngan_diffgeo_bwd"]
-    assert not set(ngan._C.geoaug_symbols()) & set(ngan._C.exported_symbols()) and len(ngan._C.exported_symbols()) == 165
+    assert {"ngan_diffgeo_params", "ngan_diffgeo_fwd", "ngan_diffgeo_bwd"} <= set(ngan._C.exported_symbols())
     for fn in (lambda *a: lib.ngan_diffgeo_fwd(*a[:-1], 0.0, a[-1]), lib.ngan_diffgeo_bwd):     # (fwd: fill in front of the stream)
         for args in ((N, one, one), (one, N, one), (one, one, N)):
             assert fn(*args, 2, 1, 16, 16, 2, None) == -1 and b"null" in err()

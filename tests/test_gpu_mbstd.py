@@ -124,8 +124,8 @@ def test_host_side_checks(ngan):
     with pytest.raises(RuntimeError, match="16-byte"):
         call("ngan_mbstd_fwd", x.reshape(-1)[1:33].reshape(2, 2, 2, 4), s, w, 2, 2, 2, 4, 1, 2)
     assert lib.ngan_mbstd_workspace_doubles(8, 2, 2, 4, 3) == 0
-    assert set(ngan._C.mbstd_symbols()) == {"ngan_mbstd_fwd", "ngan_mbstd_bwd", "ngan_mbstd_bwdbwd", "ngan_stdfield_add", "ngan_stdfield_ds",
-                                           "ngan_stdfield_dw", "ngan_mbstd_workspace_doubles"}
+    assert {"ngan_mbstd_fwd", "ngan_mbstd_bwd", "ngan_mbstd_bwdbwd", "ngan_stdfield_add", "ngan_stdfield_ds", "ngan_stdfield_dw",
+            "ngan_mbstd_workspace_doubles"} <= set(ngan._C.exported_symbols())
 
 
 def test_operators_close_under_double_backward(ngan):

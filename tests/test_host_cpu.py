@@ -20,15 +20,135 @@ def built(ngan):
     return ngan
 
 
+_INT_OUT = ctypes.POINTER(ctypes.c_int)
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+
+
+def _abi_prototypes():
+    """{name: (return type, [(type, parameter name), ...])} of every prototype of include/ngan.h and the ngan_*.h it includes, types
+    without `const` and with the `*` attached ("float*").  Every `ngan_...(` of the headers has to be one of them."""
+    inc = os.path.join(ROOT, "include")
+    text = open(os.path.join(inc, "ngan.h")).read()
+    sections = re.findall(r'#include\s+"(ngan_[a-z0-9_]+\.h)"', text)
+    assert len(sections) == len(set(sections)) == 6, sections
+    text += "".join(open(os.path.join(inc, h)).read() for h in sections)
+    mentioned = set(re.findall(r"\b(ngan_[a-z0-9_]+)\s*\(", text))          # the name-only view: comments and macros included
+    code = re.sub(r"(?m)^\s*#.*$", " ", re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S)))
+
+    def ctype(t):
+        t = " ".join(re.sub(r"\bconst\b", " ", t).replace("*", " * ").split())
+        return t.replace(" *", "*")
+
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[\s*]+)(ngan_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code):
+        assert name not in protos, f"{name} is declared twice"
+        plist = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"\s*(.*[\s*])([A-Za-z_]\w*)\s*", p, flags=re.S)
+            assert m and ctype(m.group(1)), f"{name}: cannot parse the parameter {p!r}"
+            plist.append((ctype(m.group(1)), m.group(2)))
+        protos[name] = (ctype(ret), plist)
+    assert len(re.findall(r"\bngan_[a-z0-9_]+\s*\(", code)) == len(protos), "a declaration of the headers did not parse as a prototype"
+    assert mentioned == set(protos), f"named with a '(' in the headers but not declared: {sorted(mentioned - set(protos))}"
+    return protos
+
+
+def _abi_mismatches(protos, signatures, non_status, exported):
+    """One line per disagreement between the headers' prototypes, the two ctypes tables and the library's dynamic symbols; each line
+    starts with the offending name."""
+    bad = []
+    table = dict({n: (a, ctypes.c_int) for n, a in signatures.items()}, **non_status)
+    for n in sorted(set(signatures) & set(non_status)):
+        bad.append(f"{n}: in both SIGNATURES and NON_STATUS")
+    for n in sorted(set(protos) ^ set(table)):
+        bad.append(f"{n}: " + ("declared but in no table" if n in protos else "in a table but not declared"))
+    for n in sorted((set(protos) | set(table)) ^ set(exported)):
+        bad.append(f"{n}: " + ("exported by the library only" if n in exported else "not exported by the library"))
+    for n in sorted(set(protos) & set(table)):
+        (ret, params), (argtypes, restype) = protos[n], table[n]
+        takes_stream = bool(params) and params[-1] == ("void*", "stream")
+        if (n in signatures) != (ret == "int" and takes_stream):
+            bad.append(f"{n}: SIGNATURES holds exactly the int-returning entry points whose last parameter is `void* stream`; "
+                       f"the header has {ret} (..., {' '.join(params[-1]) if params else 'void'})")
+        want_ret = ctypes.c_char_p if ret == "char*" else _SCALARS.get(ret)
+        if want_ret is None or restype is not want_ret:
+            bad.append(f"{n}: returns {ret} in the header, {getattr(restype, '__name__', restype)} in the table")
+        if len(params) != len(argtypes):
+            bad.append(f"{n}: {len(params)} parameters in the header, {len(argtypes)} in the table")
+            continue
+        for i, ((t, pname), got) in enumerate(zip(params, argtypes)):
+            if t.endswith("*"):
+                want = ctypes.c_char_p if t == "char*" else _INT_OUT if (got is _INT_OUT and t == "int*") else ctypes.c_void_p
+            else:
+                want = _SCALARS.get(t)
+            if want is None or got is not want:
+                bad.append(f"{n}: parameter {i} is `{t} {pname}` in the header, {getattr(got, '__name__', got)} in the table")
+    return bad
+
+
+def _dynamic_symbols(path):
+    """names the shared library defines in its dynamic symbol table (ELF64, little endian: the .dynsym section)"""
+    import struct
+    blob = open(path, "rb").read()
+    assert blob[:6] == b"\x7fELF\x02\x01", "not a little-endian ELF64 file"
+    shoff, = struct.unpack_from("<Q", blob, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
+    heads = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, sh_type, _, _, off, size, link, _, _, entsize in heads:
+        if sh_type == 11:                                                    # SHT_DYNSYM; `link` is its string table
+            stroff = heads[link][4]
+            for o in range(off, off + size, entsize):
+                st_name, _, _, shndx = struct.unpack_from("<IBBH", blob, o)
+                if shndx != 0:
+                    names.add(blob[stroff + st_name:blob.index(b"\0", stroff + st_name)].decode())
+    return names
+
+
 def test_library_exports_every_declared_symbol(built):
-    header = open(os.path.join(ROOT, "include", "ngan.h")).read()
-    declared = set(re.findall(r"\b(ngan_[a-z0-9_]+)\s*\(", header))
-    assert len(declared) >= 32
-    lib = ctypes.CDLL(built._C.LIB_PATH)
-    for name in sorted(declared):
-        assert hasattr(lib, name), f"{name} is declared in include/ngan.h but not exported"
-    assert declared == set(built._C.exported_symbols()), "ctypes signature table and header disagree"
-    assert built._C.version().startswith("ngan-hip")
+    """One ABI, one table, checked by prototype: every entry point the headers declare is exported by the library and bound by
+    _C.SIGNATURES / _C.NON_STATUS with the argument list and return type of its prototype -- and nothing else is."""
+    C = built._C
+    protos = _abi_prototypes()
+    exported = {n for n in _dynamic_symbols(C.LIB_PATH) if n.startswith("ngan_")}
+    assert _abi_mismatches(protos, C.SIGNATURES, C.NON_STATUS, exported) == []
+    assert len(C.exported_symbols()) == 185 and set(C.exported_symbols()) == set(protos)
+    assert len(C.SIGNATURES) == 150 and len(C.NON_STATUS) == 35
+    lib = C.lib()
+    for name in C.exported_symbols():
+        assert getattr(lib, name).argtypes == (C.SIGNATURES.get(name) or C.NON_STATUS[name][0]), name
+    assert C.version().startswith("ngan-hip")
+
+
+@pytest.mark.parametrize("name, perturb, word", [
+    ("ngan_conv3x3_fwd_ex", lambda row: row[:8] + row[9:], "20 in the table"),                                   # one int dropped
+    ("ngan_specloss_head", lambda row: [ctypes.c_float if t is ctypes.c_double else t for t in row], "`double "),   # a double as float
+    ("ngan_lrelu_pixelnorm_fwd", lambda row: [ctypes.c_int if t is ctypes.c_long else t for t in row], "`long "),  # a long as int
+    ("ngan_gp_head", lambda row: row[:2] + [ctypes.c_double] + row[3:], "`float "),                              # a float as double
+    ("ngan_adam_step", lambda row: row[:-1], "14 in the table"),                                                 # the stream dropped
+])
+def test_a_drifted_table_row_is_reported(built, name, perturb, word):
+    """the comparison of the test above can fail: a row that no longer follows its prototype is reported, by name, and no other is"""
+    C = built._C
+    protos = _abi_prototypes()
+    drifted = dict(C.SIGNATURES, **{name: perturb(list(C.SIGNATURES[name]))})
+    assert drifted[name] != C.SIGNATURES[name]
+    bad = _abi_mismatches(protos, drifted, C.NON_STATUS, set(protos))
+    assert bad and all(line.startswith(name + ":") for line in bad) and any(word in line for line in bad), bad
+
+
+def test_other_kinds_of_abi_drift_are_reported(built):
+    """a wrong return type, an out-array bound where the header has no int*, a row in the wrong table, a name the library lacks"""
+    C = built._C
+    protos = _abi_prototypes()
+    ret = dict(C.NON_STATUS, ngan_conv3x3_packed_floats=(C.NON_STATUS["ngan_conv3x3_packed_floats"][0], ctypes.c_int))
+    assert [b.split(":")[0] for b in _abi_mismatches(protos, C.SIGNATURES, ret, set(protos))] == ["ngan_conv3x3_packed_floats"]
+    out = dict(C.NON_STATUS, ngan_msssim_window=([_INT_OUT], ctypes.c_int))
+    assert [b.split(":")[0] for b in _abi_mismatches(protos, C.SIGNATURES, out, set(protos))] == ["ngan_msssim_window"]
+    moved = dict(C.SIGNATURES, ngan_spectrum_window=C.NON_STATUS["ngan_spectrum_window"][0])
+    rest = {n: v for n, v in C.NON_STATUS.items() if n != "ngan_spectrum_window"}
+    assert [b.split(":")[0] for b in _abi_mismatches(protos, moved, rest, set(protos))] == ["ngan_spectrum_window"]
+    assert [b.split(":")[0] for b in _abi_mismatches(protos, C.SIGNATURES, C.NON_STATUS, set(protos) - {"ngan_version"})] == ["ngan_version"]
 
 
 def test_invalid_arguments_return_status_not_crash(built):

@@ -139,7 +139,8 @@ def test_header_table_and_refusals(ngan):
     main = open(os.path.join(root, "include", "ngan.h")).read()
     declared = set(re.findall(r"\b(ngan_[a-z0-9_]+)\s*\(", open(os.path.join(root, "include", "ngan_spectral.h")).read()))
     assert '#include "ngan_spectral.h"' in main
-    assert declared == set(ngan._C.spectral_symbols()) and not declared & set(ngan._C.exported_symbols())
+    assert declared == {"ngan_specloss_fwd", "ngan_specloss_head", "ngan_specloss_bwd", "ngan_specloss_fwd_workspace_bytes",
+                        "ngan_specloss_bwd_workspace_bytes"} and declared <= set(ngan._C.exported_symbols())
     lib = ngan._C.lib()
     q = lib.ngan_specloss_fwd_workspace_bytes
     assert q(0, 32, 1) == q(1, 48, 1) == q(1, 8, 1) == q(1, 2048, 1) == q(1, 32, 3) == q(65536, 32, 1) == 0
