@@ -203,6 +203,19 @@ NON_STATUS = {
     "ngan_specloss_bwd_workspace_bytes": ([_I, _I, _I], _Z),
 }
 
+# Extension entry points (include/nganx.h, which ngan.h does not include: the core ABI above is frozen and additions outside the
+# reference are declared there, prefix nganx_).  Same library, same conventions; tests/test_simloss_host_cpu.py holds every row to its
+# prototype.  exported_symbols() stays the core tables.
+EXT_SIGNATURES = {
+    # pairwise similarity loss of the generator (ops.SimilarityLoss)
+    "nganx_pair_gram": [_P, _P, _P, _P, _I, _L, _P],
+    "nganx_simloss_head": [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _P],
+    "nganx_pair_mix": [_P, _P, _P, _P, _P, _P, _I, _L, _P],
+}
+EXT_NON_STATUS = {
+    "nganx_pair_gram_workspace_bytes": ([_I, _L], _Z),
+}
+
 _lib = None
 
 
@@ -214,11 +227,11 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                f"or `make -C neuron-gan_amd/csrc`; there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
-        for name, (argtypes, restype) in NON_STATUS.items():
+        for name, (argtypes, restype) in list(NON_STATUS.items()) + list(EXT_NON_STATUS.items()):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype

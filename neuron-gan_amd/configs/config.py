@@ -34,7 +34,7 @@ _DEFAULTS = dict(
     # the checkpoint metrics: <prefix>_period, _images (or _pairs), _seed and the metric's own options, row by row
     **{name: default for m in METRICS for name, _, default, _ in settings(m)},
     diffaug='', diffaug_p=1.0, diffaug_seed=0, lsgan=False, mbstd_group=0, grad_pen_mode='gp', grad_pen_interval=1,
-    spec_loss_lambda=0.0, spec_loss_floor=1e-3, spec_loss_images=256, spec_loss_seed=0,
+    spec_loss_lambda=0.0, spec_loss_floor=1e-3, spec_loss_images=256, spec_loss_seed=0, sim_loss_on='real', sim_loss_center=False,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -146,6 +146,16 @@ def validate_configs(create_dirs=False):
         raise ValueError(f"spec_loss_seed={g['spec_loss_seed']!r} must be an integer >= 0")
     if g['spec_loss_lambda'] and g['wgan']:
         raise ValueError("spec_loss_lambda > 0 is not available for the WGAN nets (wgan=True)")
+    # the similarity loss (sim_loss_lambda, the reference's switch): sim_loss_on 'real' is the reference's path -- the term is taken on
+    # the real batch and only monitored; 'generated' takes it on the generator's images, where it trains the generator (an addition of
+    # this implementation).  sim_loss_center: cosines of the images less their own means.  'generated' with sim_loss_lambda = 0 is
+    # accepted and inert
+    if g['sim_loss_on'] not in ('real', 'generated'):
+        raise ValueError(f"sim_loss_on={g['sim_loss_on']!r} must be 'real' or 'generated'")
+    if not isinstance(g['sim_loss_center'], bool):
+        raise ValueError(f"sim_loss_center={g['sim_loss_center']!r} must be a bool")
+    if g['sim_loss_on'] == 'generated' and g['wgan']:
+        raise ValueError("sim_loss_on='generated' is not available for the WGAN nets (wgan=True)")
     if g['pggan']:
         err_msg = 'The number of layers in the generator and discriminator must match.'
         assert len(g['N_gen_features']) == len(g['N_dis_features']), err_msg

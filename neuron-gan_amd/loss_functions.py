@@ -6,12 +6,14 @@
     D_LS_loss(G, D, real)                    -> (loss, score_real, score_fake)   least squares, Mao et al. 2017; functions, as in the
     G_LS_loss(G, D, real)                    -> (loss, score_fake)               reference, which ships them and never calls them
     G_spectral_loss(images, target, Lambda)  -> loss   spectral regularisation of a generator's images (Durall et al. 2020); an addition
+    G_similarity_loss(images, z, Lambda)     -> loss   the reference's similarity_loss on GENERATED images, differentiable; an addition
 
 Latents come from `utils.sample_latent_vec` unless a tensor is passed through the optional `z=` / `epsilon=`
 keywords (how the parity tests inject the reference's draws).  Every loss takes an optional `augment=` hook (`DiffAugmentHook`, an
 addition of this implementation: differentiable augmentation of everything the critic sees); None is the reference's path.  The
 generator losses a trainer holds (G_W_loss, G_LS_module) also take a `spectral=` hook (`SpectralHook`: the spectral regularisation of
-G_spectral_loss on the generator's raw images) and then return the term as a third value.  NaN handling: the reference dumps locals and
+G_spectral_loss on the generator's raw images) and then return the term as a third value, and a `similarity=` hook (`SimilarityHook`:
+G_similarity_loss on the same images and the step's latents), whose term is returned last.  NaN handling: the reference dumps locals and
 raises `ValueError` (loss_functions.py:35-41, 70-72); here the check is optional (`check_nan`) because
 `torch.isnan(...)` in an `if` is a host sync on the GPU -- the training loop checks once per epoch instead.
 """
@@ -111,6 +113,40 @@ class SpectralHook:
         return images, term
 
 
+def G_similarity_loss(images, z, Lambda=1.0, center=False):
+    """The reference's similarity_loss (loss_functions.py:183-205) on a generator's images, so that it trains the generator as its
+    comment intends (the reference's loop hands it the real batch, train.py:379-381, where it reaches neither network):
+    Lambda / (B (B - 1)) * sum_{i != j} (T_ij - S_ij)^2 with S the pairwise cosines of the flattened images and T those of the latents
+    (include/nganx.h).  center: the cosines are those of the images less their own means -- on micrographs the
+    raw ones sit at 0.9 because the black background dominates; the latents are never centred.  images: (B, ...) fp32 on the GPU,
+    2 .. 64 rows of a multiple of 4 values; z: (B, latent_dim) fp32.  Lambda: a float, or an fp32 scalar on the device (read by the
+    kernel at launch time: a captured graph follows it).  No epsilon: an image of zero (centred) norm gives NaN, as the reference's
+    division does.  B = 1 has no pair and gives the zero scalar.  An fp32 scalar, differentiable once in the images
+    (ops.SimilarityLoss); no gradient flows to z or Lambda."""
+    lam = Lambda if isinstance(Lambda, torch.Tensor) else torch.full((), float(Lambda), device=images.device, dtype=torch.float32)
+    return ops.SimilarityLoss.apply(images, z, lam, bool(center))[1]
+
+
+class SimilarityHook:
+    """The `similarity=` hook of the generator losses: taps the generator's raw images -- before the spectral tap and before any
+    DiffAugment transform -- together with the latents they were generated from, and holds the term.  lam: the fp32 device scalar the
+    head launch reads; center: G_similarity_loss's."""
+
+    def __init__(self, lam, center=False):
+        self.lam, self.center = lam, bool(center)
+
+    def tap(self, images, z):
+        """(images passed through, the term): the gradient of what follows arrives at the pass-through and is added on the mix
+        launch's store"""
+        images, term, _ = ops.SimilarityLoss.apply(images, z, self.lam, self.center)
+        return images, term
+
+
+def _hook_returns(head, spectral, similarity, spec_term, sim_term):
+    """head, then the spectral term (with that hook), then the similarity term (with that hook)"""
+    return head + (() if spectral is None else (spec_term,)) + (() if similarity is None else (sim_term,))
+
+
 class D_W_loss(nn.Module):
     def __init__(self, generator_net, discriminator_net, drift_epsilon=0.0, check_nan=True):
         super().__init__()
@@ -148,11 +184,15 @@ class G_W_loss(nn.Module):
         self.discriminator_net = discriminator_net
         self.check_nan = check_nan
 
-    def forward(self, real_images_batch, z=None, augment=None, spectral=None):
-        """spectral (a SpectralHook): the return value gains the spectral term, (loss, z, term); None is the reference's path"""
+    def forward(self, real_images_batch, z=None, augment=None, spectral=None, similarity=None):
+        """spectral (a SpectralHook): the return value gains the spectral term, (loss, z, term); None is the reference's path.
+        similarity (a SimilarityHook): the return value gains that term, last; it taps the raw images first."""
         batch_size, device = real_images_batch.size(0), real_images_batch.device
         z_latent = _latents(self.generator_net, batch_size, device, z)
         fake_images = self.generator_net(z_latent)
+        term = sim_term = None
+        if similarity is not None:
+            fake_images, sim_term = similarity.tap(fake_images, z_latent)
         if spectral is not None:
             fake_images, term = spectral.tap(fake_images)
         if augment is not None:
@@ -161,7 +201,7 @@ class G_W_loss(nn.Module):
             G_loss = ops.WLossHead.apply(self.discriminator_net(fake_images), batch_size, 0.0)[0]       # -mean(D(G(z)))
         if self.check_nan and torch.isnan(G_loss):
             raise ValueError('Generator loss is nan.')
-        return (G_loss, z_latent) if spectral is None else (G_loss, z_latent, term)
+        return _hook_returns((G_loss, z_latent), spectral, similarity, term, sim_term)
 
 
 # The reference's coding of the least-squares targets (loss_functions.py:99, 133): the critic pulls real scores to 1 and generated ones to
@@ -198,13 +238,18 @@ def G_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, 
     the generated images (loss_functions.py:125), so its generator would receive no gradient at all and could not be trained with
     this loss; here the value is the same and the gradient flows into the generator (through `augment`'s transform when given).
     (The signature is the reference's plus the W losses' keyword extras; the `spectral=` hook is G_LS_module's.)"""
-    return _g_ls_loss(generator_net, discriminator_net, real_images_batch, z, augment, check_nan, None)
+    return _g_ls_loss(generator_net, discriminator_net, real_images_batch, z, augment, check_nan, None)[:2]
 
 
-def _g_ls_loss(generator_net, discriminator_net, real_images_batch, z, augment, check_nan, spectral):
-    """G_LS_loss's body; spectral (a SpectralHook): the return value gains the spectral term, (G_loss, Score_fake_avg, term)"""
+def _g_ls_loss(generator_net, discriminator_net, real_images_batch, z, augment, check_nan, spectral, similarity=None):
+    """G_LS_loss's body; spectral (a SpectralHook): the return value gains the spectral term, (G_loss, Score_fake_avg, term);
+    similarity (a SimilarityHook): it gains that term, last"""
     batch_size, device = real_images_batch.size(0), real_images_batch.device
-    fake_images = generator_net(_latents(generator_net, batch_size, device, z))
+    z = _latents(generator_net, batch_size, device, z)
+    fake_images = generator_net(z)
+    term = sim_term = None
+    if similarity is not None:
+        fake_images, sim_term = similarity.tap(fake_images, z)
     if spectral is not None:
         fake_images, term = spectral.tap(fake_images)
     if augment is not None:
@@ -216,7 +261,7 @@ def _g_ls_loss(generator_net, discriminator_net, real_images_batch, z, augment, 
             raise ValueError('Fake loss is nan.')
         if torch.isnan(G_loss):
             raise ValueError('D loss is nan.')
-    return (G_loss, Score_fake_avg) if spectral is None else (G_loss, Score_fake_avg, term)
+    return _hook_returns((G_loss, Score_fake_avg), spectral, similarity, term, sim_term)
 
 
 class D_LS_module(nn.Module):
@@ -238,11 +283,13 @@ class G_LS_module(nn.Module):
         super().__init__()
         self.generator_net, self.discriminator_net, self.check_nan = generator_net, discriminator_net, check_nan
 
-    def forward(self, real_images_batch, z=None, augment=None, spectral=None):
-        """spectral (a SpectralHook): the return value gains the spectral term, (loss, z, term)"""
+    def forward(self, real_images_batch, z=None, augment=None, spectral=None, similarity=None):
+        """spectral (a SpectralHook): the return value gains the spectral term, (loss, z, term); similarity (a SimilarityHook): it
+        gains that term, last"""
         z_latent = _latents(self.generator_net, real_images_batch.size(0), real_images_batch.device, z)
-        out = _g_ls_loss(self.generator_net, self.discriminator_net, real_images_batch, z_latent, augment, self.check_nan, spectral)
-        return (out[0], z_latent) if spectral is None else (out[0], z_latent, out[2])
+        out = _g_ls_loss(self.generator_net, self.discriminator_net, real_images_batch, z_latent, augment, self.check_nan, spectral,
+                         similarity)
+        return (out[0], z_latent) + tuple(out[2:])
 
 
 PENALTY_MODES = ("gp", "lp", "r1")      # D_grad_pen_loss(mode=)

@@ -1900,3 +1900,83 @@ class SpectralLoss(Function):
         addend = None if g_images is None else _c(g_images)
         _C.call("ngan_specloss_bwd", transform, coef, _c(g_loss), addend, grad, ws, b, r, 1, 1)
         return grad, None, None, None
+
+
+# ---- pairwise similarity loss of the generator (include/nganx.h; csrc/simloss.hip) -------------------------------------------------
+SIMLOSS_MAX_BATCH = 64       # rows of a call: the head is one workgroup, a lane per column
+
+
+def _simloss_check(images, z, lam):
+    if images.dim() < 2 or z.dim() < 2 or z.shape[0] != images.shape[0]:
+        raise ValueError(f"SimilarityLoss: a batch of images and one latent row per image expected, got {tuple(images.shape)} and {tuple(z.shape)}")
+    if images.dtype != torch.float32 or z.dtype != torch.float32:
+        raise NotImplementedError(f"SimilarityLoss: the kernels read fp32 images and latents, got {images.dtype} and {z.dtype}")
+    b = images.shape[0]
+    if b > SIMLOSS_MAX_BATCH:
+        raise ValueError(f"SimilarityLoss: a batch of {b} is above the {SIMLOSS_MAX_BATCH} rows a call takes")
+    if not (isinstance(lam, torch.Tensor) and lam.dtype == torch.float32 and lam.numel() == 1 and lam.device == images.device):
+        raise ValueError("SimilarityLoss: lambda must be an fp32 scalar tensor on the images' device (a captured graph reads it live)")
+    if z.device != images.device:
+        raise ValueError(f"SimilarityLoss: latents on {z.device}, images on {images.device}")
+
+
+def pair_gram(rows):
+    """(gram (B, B), sums (B,)) in fp64 of fp32 rows (B, N): nganx_pair_gram, two launches"""
+    rows = _c(rows)
+    b, n = rows.shape[0], rows[0].numel()
+    nbytes = _C.lib().nganx_pair_gram_workspace_bytes(b, n)
+    if nbytes == 0:
+        raise ValueError(f"pair_gram: {b} rows of {n} values are outside the kernels' domain (2 .. {SIMLOSS_MAX_BATCH} rows; a multiple "
+                         f"of 4 values, at least 16)")
+    gram = torch.empty(b, b, device=rows.device, dtype=torch.float64)
+    sums = torch.empty(b, device=rows.device, dtype=torch.float64)
+    ws = torch.empty(nbytes // 8, device=rows.device, dtype=torch.float64)
+    _C.call("nganx_pair_gram", rows, gram, sums, ws, b, n)
+    return gram, sums
+
+
+class SimilarityLoss(Function):
+    """A tap on the generator's images: (images, L, S) = SimilarityLoss.apply(images, z, lam, center) with images passed through,
+    L = lam / (B (B - 1)) sum_{i != j} (T_ij - S_ij)^2 (fp32 scalar), S the pairwise cosines of the flattened images (fp64 (B, B), not
+    differentiable; of the images less their own means with `center`) and T those of the latents z, never centred (include/nganx.h;
+    DESIGN.md section 7).  lam is an fp32 DEVICE scalar, read by the head launch: a captured graph follows its value.  Five launches
+    forward (two Gram calls of two, the head); backward one, the gradient arriving at the pass-through added on its store and the one
+    arriving at L read from the device.  No gradient flows to z or lam.  Differentiable once.  B = 1 has no pair: L is the zero scalar
+    and nothing is launched."""
+
+    @staticmethod
+    def forward(ctx, images, z, lam, center):
+        ctx.set_materialize_grads(False)
+        _simloss_check(images, z, lam)
+        b = images.shape[0]
+        dev = images.device
+        ctx.pairs = b > 1
+        if b == 1:
+            sim = torch.ones(1, 1, device=dev, dtype=torch.float64)
+            ctx.mark_non_differentiable(sim)
+            return images.view_as(images), torch.zeros((), device=dev, dtype=torch.float32), sim
+        x = _c(images)
+        n = x[0].numel()
+        gx, sx = pair_gram(x.view(b, n))
+        gz, _ = pair_gram(z.detach().reshape(b, -1))
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        sim = torch.empty(b, b, device=dev, dtype=torch.float64)
+        mix = torch.empty(b, b, device=dev, dtype=torch.float32)
+        shift = torch.empty(b, device=dev, dtype=torch.float32)
+        _C.call("nganx_simloss_head", gx, sx, gz, lam, b, n, 1 if center else 0, loss, sim, mix, shift)
+        ctx.save_for_backward(x, mix, shift)
+        ctx.mark_non_differentiable(sim)
+        return images.view_as(images), loss, sim
+
+    @staticmethod
+    def backward(ctx, g_images, g_loss, _g_sim):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("second derivative through the similarity loss is not built: it is a generator-side term")
+        if g_loss is None or not ctx.pairs:
+            return g_images, None, None, None
+        x, mix, shift = ctx.saved_tensors
+        b, n = x.shape[0], x[0].numel()
+        grad = torch.empty_like(x)
+        addend = None if g_images is None else _c(g_images)
+        _C.call("nganx_pair_mix", x, mix, shift, _c(g_loss), addend, grad, b, n)
+        return grad, None, None, None

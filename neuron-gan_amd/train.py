@@ -28,7 +28,7 @@ import torch.distributed as dist
 from . import _C, ops, wgan_ops
 from .launch import check_sharding, epoch_batches, longest_share, shard_bounds
 from .loss_functions import (PENALTY_MODES, D_LS_module, D_W_loss, D_grad_pen_loss, DiffAugmentHook, G_LS_module, G_W_loss,
-                             SpectralHook)
+                             SimilarityHook, SpectralHook)
 from .metric_table import METRICS, settings
 from .scoring import (score_branches, score_due, score_morph, score_msssim, score_sholl, score_skeleton,  # noqa: F401
                       score_spectrum, score_swd)
@@ -379,6 +379,18 @@ def _check_ema_beta(ema_beta):
     if not 0.0 < float(ema_beta) < 1.0:
         raise ValueError(f"ema_beta must be 0 (off) or lie in (0, 1), got {ema_beta}")
     return float(ema_beta)
+
+
+SIM_LOSS_ON = ("real", "generated")      # PGGANTrainer(sim_loss_on=)
+
+
+def check_sim_loss(on, center):
+    """(sim_loss_on, sim_loss_center) of the trainer arguments"""
+    if on not in SIM_LOSS_ON:
+        raise ValueError(f"sim_loss_on must be one of {list(SIM_LOSS_ON)}, got {on!r}")
+    if not isinstance(center, (bool, int)) or center not in (0, 1, False, True):
+        raise ValueError(f"sim_loss_center must be a bool, got {center!r}")
+    return on, bool(center)
 
 
 def check_spec_loss(lam, floor):
@@ -849,7 +861,8 @@ class PGGANTrainer(_Trainer):
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, grad_pen_lambda=10.0, drift_epsilon=0.001,
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
                  rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, objective="wasserstein",
-                 grad_pen_mode="gp", grad_pen_interval=1, spec_loss_lambda=0.0, spec_loss_floor=1e-3):
+                 grad_pen_mode="gp", grad_pen_interval=1, spec_loss_lambda=0.0, spec_loss_floor=1e-3, sim_loss_on="real",
+                 sim_loss_center=False):
         """optimizer: "adam" -- optim.Adam(params, lr, betas=(beta1, 0.999)), the reference's default -- or "rmsprop" --
         optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps), what the reference's RMSprop switch selects (train.py:220-225);
         beta1 only matters for Adam
@@ -882,7 +895,20 @@ class PGGANTrainer(_Trainer):
         `set_spectral_target` hands over per image size.  spec_loss_floor: the floor on the ratio of the spectra (1e-3: -30 dB).
         The term is a per-sample mean like every loss here, so the share weight of a data-parallel step applies to it as it
         stands.  The generator's image tensor is fp32 in every conv precision, the "bf16" storage mode included, so the term
-        runs in all of them.  A stage below 16 x 16 has no ring to score: the term is off there and `spectral_note` says so."""
+        runs in all of them.  A stage below 16 x 16 has no ring to score: the term is off there and `spectral_note` says so.
+        sim_loss_on: "real" -- the reference's path: its similarity loss is evaluated on the real batch by the epoch driver, a
+        monitored number that reaches neither network; the trainer allocates, launches and holds nothing for it (the code path of a
+        build without the feature).  "generated" -- the term is taken on the generator's raw images and the step's latents
+        (loss_functions.G_similarity_loss), before the spectral tap and before any DiffAugment transform, and
+        trains the generator.  Its weight is a device scalar that starts at 0 and that `set_sim_lambda` writes (the epoch driver does,
+        once per epoch, decay included); the captured graphs read it, so a new weight needs no re-capture, and with the weight at 0
+        the tap stays in the graph and contributes exact zeros.  g_compute then returns G_sim_loss beside G_loss.  A batch above 64
+        per rank is refused at the first step.  sim_loss_center: the images' cosines are taken after subtracting each image's own
+        mean.  Data parallel: a rank's term is the mean over the pairs INSIDE its own share, lambda / (n_r (n_r - 1)), and the share
+        weight applies on top -- a departure from "all pairs of the global batch": every pair is an independent draw, so each rank's
+        mean estimates the same expectation; nothing is gathered and the statistics stay local to a rank, as for the minibatch
+        standard deviation.  A share of 1 has no pair and contributes 0."""
+        sim_loss_on, sim_loss_center = check_sim_loss(sim_loss_on, sim_loss_center)
         if objective not in OBJECTIVES:
             raise ValueError(f"objective must be one of {list(OBJECTIVES)}, got {objective!r}")
         grad_pen_mode, grad_pen_interval = check_grad_pen(grad_pen_mode, grad_pen_interval)
@@ -936,8 +962,38 @@ class PGGANTrainer(_Trainer):
         self.spec_loss_lambda, self.spec_loss_floor = spec_loss_lambda, spec_loss_floor
         self._spec_targets = {} if spec_loss_lambda > 0 else None      # image size -> the static fp64 target buffer of that stage
         self.spectral_note = None                                       # what a stage below 16 x 16 said (once per size)
+        if sim_loss_on == "generated":      # ("real": the class attributes below stand; the instance gains nothing)
+            self.sim_loss_on, self.sim_loss_center = sim_loss_on, sim_loss_center
+            self._sim_lambda = torch.zeros((), device=self.device, dtype=torch.float32)
         self.refresh_stage()
         ops.bump_weight_epoch()
+
+    # ---- similarity loss on the generated images ------------------------------------------------------------------
+    sim_loss_on, sim_loss_center, _sim_lambda = "real", False, None        # what a trainer built with sim_loss_on="real" reads
+
+    @property
+    def similarity_enabled(self):
+        return self._sim_lambda is not None
+
+    def set_sim_lambda(self, value):
+        """The weight of the similarity term into the device scalar the head launch reads.  Like `_set_share` the write is never
+        captured (a capture would freeze its value): the graphs replay with the weight of the moment."""
+        if self._sim_lambda is None:
+            raise ValueError('set_sim_lambda on a trainer with sim_loss_on="real": there is no similarity term to weigh')
+        value = float(value)
+        if not (math.isfinite(value) and value >= 0):
+            raise ValueError(f"the similarity weight must be a finite number >= 0, got {value!r}")
+        if not (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            self._sim_lambda.fill_(value)
+
+    def _similarity_hook(self, b):
+        """the `similarity=` hook of this step's generator loss; None with sim_loss_on="real" """
+        if self._sim_lambda is None:
+            return None
+        if b > ops.SIMLOSS_MAX_BATCH:
+            raise ValueError(f'sim_loss_on="generated" takes at most {ops.SIMLOSS_MAX_BATCH} images per rank and step, got {b}: lower '
+                             f"the batch size, train on more ranks, or keep sim_loss_on=\"real\"")
+        return SimilarityHook(self._sim_lambda, self.sim_loss_center)
 
     # ---- spectral regularisation of the generator ----------------------------------------------------------------
     @property
@@ -1156,27 +1212,37 @@ class PGGANTrainer(_Trainer):
                 hook = DiffAugmentHook(gen=self._aug.gen(b, self.n_critic), colour=self._aug.colour,
                                        geo_gen=self._aug.geo_gen(b, self.n_critic))
             spectral, term = self._spectral_hook(b), None
-            if spectral is None:
+            similarity, sim_term = self._similarity_hook(b), None
+            if spectral is None and similarity is None:
                 loss, self.last_z_g = self.g_loss(real, z=self._latent(b, z), augment=hook)  # train.py:376
-            else:
+            elif similarity is None:
                 loss, self.last_z_g, term = self.g_loss(real, z=self._latent(b, z), augment=hook, spectral=spectral)
+            else:
+                out = self.g_loss(real, z=self._latent(b, z), augment=hook, spectral=spectral, similarity=similarity)
+                loss, self.last_z_g, sim_term = out[0], out[1], out[-1]
+                term = out[2] if spectral is not None else None
             # the stem hands over factors instead of a gradient when they are exchanged (data parallel) or go straight to Adam
             self._stem_sink_active = self.stem is not None and (self._stem_for_exchange or self._stem_grad_skipped)
             ops.linear_grad_sink = self.stem.sink if self._stem_sink_active else None
             try:
                 with ops.deferred_wgrad():
-                    if term is None:
+                    if term is None and sim_term is None:
                         loss.backward(gradient=self._root)  # train.py:384
-                    else:       # one pass: the critic's image gradient meets the spectral one on the adjoint's store
-                        torch.autograd.backward([loss, term], [self._root, self._root])
+                    else:       # one pass over all roots: the critic's image gradient meets the spectral one on the adjoint's store,
+                        #         and their sum the similarity term's on the mix launch's
+                        roots = [loss] + [t for t in (term, sim_term) if t is not None]
+                        torch.autograd.backward(roots, [self._root] * len(roots))
             finally:
                 ops.linear_grad_sink = None
         finally:
             for p in d_params:
                 p.requires_grad_(True)
-        if self._spec_targets is None:
-            return {"G_loss": loss.detach()}
-        return {"G_loss": loss.detach(), "G_spec_loss": term.detach() if term is not None else torch.zeros((), device=self.device)}
+        stats = {"G_loss": loss.detach()}
+        if self._spec_targets is not None:
+            stats["G_spec_loss"] = term.detach() if term is not None else torch.zeros((), device=self.device)
+        if sim_term is not None:
+            stats["G_sim_loss"] = sim_term.detach()
+        return stats
 
     def materialize_stem_grad(self):
         """After a g_step that skipped the stem's gradient (fused_stem), write it into the stem weight's .grad from that step's
@@ -1776,7 +1842,12 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     A trainer with spec_loss_lambda > 0: the data's mean radial spectrum (metrics.spectral_target over cfg.spec_loss_images images,
     seed cfg.spec_loss_seed) is computed and handed to the trainer at the start and whenever a growth event changed the image size
     -- by every rank from the whole data set, a checksum of it guarded by `assert_same` -- and G_spec_loss is a sixth monitor: in
-    the sums, the series and the status line.  With the switch off there are five, as ever."""
+    the sums, the series and the status line.  With the switch off there are five, as ever.
+    A trainer with sim_loss_on="generated": the epoch's similarity weight -- cfg.sim_loss_lambda, decayed by
+    cfg.sim_loss_lambda_decay_rate and cut to 0 below 1e-5 as train.py:343-348 does -- goes to `set_sim_lambda` at every epoch start;
+    the graphs read it from the device.  In an epoch whose weight is 0 the tap stays in the graph and contributes exact zeros: nothing
+    is re-captured.  `_monitored_g_loss` is not used: the monitored G_loss is G_loss + G_sim_loss, as the reference sums them, and
+    G_sim_loss is one more monitor, printed in the status line when it is not zero, as the reference prints it."""
     import time
     from .utils import Calculate_D_steps, plot_gen_samples
     adapt_period = 100                                                # Disc_adapt_update_period, train.py:190
@@ -1794,6 +1865,9 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     spectral = bool(getattr(trainer, "spectral_enabled", False))
     if spectral:
         names.append("G_spec_loss")
+    sim_generated = bool(getattr(trainer, "similarity_enabled", False))
+    if sim_generated:
+        names.append("G_sim_loss")
     target_size = [None]              # the image size the trainer's spectral target was last computed for
 
     def refresh_spectral_target():
@@ -1845,7 +1919,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
                 "Loss_fake (<D(G(z))>):{: >#7.4g}, G_loss:{: >#7.4g}, D_loss:{: >#7.4g}, D_grad_pen:{: >#7.4g}".format(
                     ep, "{:.3f}".format((time.time() - start_time) / done) if done > 0 else "----",
                     trainer.opt_g.param_groups[0]["lr"], G.alpha_value(), G.image_size, G.image_size, vals[0], vals[1], vals[3],
-                    vals[2], vals[4]) + (", G_spec_loss:{: >#7.4g}".format(vals[5]) if spectral else ""))
+                    vals[2], vals[4]) + (", G_spec_loss:{: >#7.4g}".format(vals[5]) if spectral else "")
+                + (", G_sim_loss:{: >#7.4g}".format(vals[-1]) if sim_generated and vals[-1] != 0 else ""))
 
     for epoch in range(epoch_init, epoch_final):
         if trainer.start_epoch(epoch, cfg.transit_sch):
@@ -1863,14 +1938,20 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
             n_d_steps = cfg.n_critic
         if sim_decay > 0 and sim_lambda > 0:                          # train.py:343-348
             sim_lambda = cfg.sim_loss_lambda * (1 - sim_decay) ** (epoch - 1) if sim_lambda > 1e-5 else 0.0
+        if sim_generated:
+            trainer.set_sim_lambda(sim_lambda)                        # a device scalar the graphs read: no re-capture, at 0 neither
         acc = torch.zeros(len(names), device=dev)
         for k, n, lo, hi, images in _epoch_batches(ranks, dataset, cfg, epoch, dev):
             trainer.n_critic = n_d_steps
             own = None if draws is None else _slice_draws(draws, epoch, k, n, lo, hi, dev)
             stats, own = _run_batch(trainer, images, n, ranks, use_graph and (draws is None or n_d_steps == 1), own, statics)
-            g_loss = _monitored_g_loss(stats, own, trainer, ranks, images, n, sim_lambda)
+            if sim_generated:                                          # train.py:381: G_loss_val += G_sim_loss
+                g_loss = stats["G_loss"] + stats["G_sim_loss"]
+            else:
+                g_loss = _monitored_g_loss(stats, own, trainer, ranks, images, n, sim_lambda)
             acc += images.size(0) * torch.stack([stats["score_real"], stats["score_fake"], stats["D_loss"], g_loss,
-                                                 stats["D_grad_pen"].float()] + ([stats["G_spec_loss"]] if spectral else []))
+                                                 stats["D_grad_pen"].float()] + ([stats["G_spec_loss"]] if spectral else [])
+                                                + ([stats["G_sim_loss"]] if sim_generated else []))
         slot = epoch & 1
         consume(slot)
         ranks.sum_(acc)                                                # N ranks: ONE all-reduce per epoch, of the five (or six) sums
@@ -2040,6 +2121,12 @@ def build_arg_parser():
                                                                        '(1e-3: -30 dB)')
     p.add_argument('--spec_loss_images', type=int, default=256, help='images the data\'s mean radial spectrum is taken over, per stage')
     p.add_argument('--spec_loss_seed', type=int, default=0, help='seed of the private augmentation stream those images are drawn with')
+    p.add_argument('--sim_loss_on', type=str, default='real', choices=list(SIM_LOSS_ON),
+                   help='which images the similarity loss (--sim_loss_lambda) is taken on: real, the reference\'s path, where it is a '
+                        'monitored number that reaches neither network; generated, the PG generator\'s images, where it trains the '
+                        'generator')
+    p.add_argument('--sim_loss_center', action='store_true', help='similarity loss on generated images: cosines of the images less '
+                                                                  'their own means (the black background otherwise dominates them)')
     for m in METRICS:                                                    # one group of integer flags per checkpoint metric
         for name, _, default, text in settings(m):
             p.add_argument('--' + name, type=int, default=default, help=text)
@@ -2081,6 +2168,8 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     config.lsgan: the PG trainer's objective is "lsgan" instead of "wasserstein" (refused for the WGAN nets).
     config.grad_pen_mode / config.grad_pen_interval: the PG trainer's penalty form and lazy-regularisation interval (likewise refused).
     config.spec_loss_lambda / config.spec_loss_floor: the PG trainer's spectral regularisation of the generator (likewise refused).
+    config.sim_loss_on / config.sim_loss_center: "generated" -- the PG trainer takes the similarity loss on the generator's images, its
+    weight starting at config.sim_loss_lambda (0 is accepted and inert); likewise refused for the WGAN nets.
     distributed: a launched rank -- the trainer exchanges over `process_group` (None: the default group); the WGAN nets then train
     with synchronised BatchNorm."""
     if config.wgan and config.pggan:
@@ -2090,7 +2179,10 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     lsgan = bool(getattr(config, 'lsgan', False))
     pen = (getattr(config, 'grad_pen_mode', 'gp'), getattr(config, 'grad_pen_interval', 1))
     spec_lambda = getattr(config, 'spec_loss_lambda', 0.0)
+    sim_on = getattr(config, 'sim_loss_on', 'real')
     if config.wgan:
+        if sim_on != 'real':
+            raise ValueError("sim_loss_on='generated' is not available for the WGAN nets (wgan=True, pggan=False)")
         if spec_lambda:
             raise ValueError("spec_loss_lambda > 0 is not available for the WGAN nets (wgan=True, pggan=False)")
         if lsgan:
@@ -2114,9 +2206,15 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
         kw["grad_pen_mode"], kw["grad_pen_interval"] = pen
     if spec_lambda:                     # (likewise)
         kw["spec_loss_lambda"], kw["spec_loss_floor"] = spec_lambda, getattr(config, 'spec_loss_floor', 1e-3)
+    if sim_on != 'real':                # (likewise)
+        kw["sim_loss_on"], kw["sim_loss_center"] = sim_on, bool(getattr(config, 'sim_loss_center', False))
     if config.RMSprop:
-        return PGGANTrainer(G, D, optimizer="rmsprop", **kw)
-    return PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
+        trainer = PGGANTrainer(G, D, optimizer="rmsprop", **kw)
+    else:
+        trainer = PGGANTrainer(G, D, optimizer="adam", beta1=config.beta1, **kw)
+    if sim_on != 'real':
+        trainer.set_sim_lambda(float(getattr(config, 'sim_loss_lambda', 0.0) or 0.0))
+    return trainer
 
 
 def main(argv=None):

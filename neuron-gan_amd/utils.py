@@ -48,7 +48,8 @@ def sample_latent_vec_device(size: tuple, device, generator=None):
 # (train.py, `ema_beta`) adds 'Generator_ema_state': the averaged weights under the keys of 'Generator_state', tensors only.  The
 # A PGGANTrainer writes 'objective' ("wasserstein" or "lsgan", train.py `objective=`) beside it; a file without the key is Wasserstein.  It
 # also writes 'grad_pen_mode', 'grad_pen_interval' and 'grad_pen_iteration' (PENALTY_KEYS; a file without them is 'gp' / 1 / 0), and
-# 'spec_loss_lambda' and 'spec_loss_floor' (SPECTRAL_KEYS; a file without them is 0 / 1e-3; resuming under other values is logged).  A
+# 'spec_loss_lambda' and 'spec_loss_floor' (SPECTRAL_KEYS; a file without them is 0 / 1e-3; resuming under other values is logged), and
+# 'sim_loss_on' and 'sim_loss_center' (SIMILARITY_KEYS; a file without them is 'real' / False; likewise logged).  A
 # critic built with mbstd_group > 0 lists 'mbstd_group' in 'Discriminator_attrs' and holds 'layers.<k>.weight_std' in its state; a file
 # without the attribute holds the reference's critic.  The
 # reference's loaders read the keys they know and ignore the rest (utils.py:185-199 index five series keys and the two attribute
@@ -102,6 +103,9 @@ PENALTY_KEYS = {'grad_pen_mode': 'gp', 'grad_pen_interval': 1, 'grad_pen_iterati
 # of a PGGANTrainer's spectral regularisation of the generator (train.py `spec_loss_lambda=`, `spec_loss_floor=`); the values of a file
 # without the keys.  Weights like grad_pen_lambda: a run may be resumed under other values, which is logged
 SPECTRAL_KEYS = {'spec_loss_lambda': 0.0, 'spec_loss_floor': 1e-3}
+# of a PGGANTrainer's similarity term (train.py `sim_loss_on=`, `sim_loss_center=`); the values of a file without the keys.  Resuming
+# under other values is allowed and logged, as for the spectral keys
+SIMILARITY_KEYS = {'sim_loss_on': 'real', 'sim_loss_center': False}
 SWD_KEY, MSSSIM_KEY, SPECTRUM_KEY, MORPH_KEY, SKELETON_KEY, SHOLL_KEY, BRANCH_KEY = (m.key for m in METRICS)
 
 
@@ -149,6 +153,9 @@ class Checkpointer:
             if hasattr(self.trainer, 'spec_loss_lambda'):
                 for key in SPECTRAL_KEYS:
                     checkpoint_dict[key] = float(getattr(self.trainer, key))
+            if hasattr(self.trainer, 'sim_loss_on'):
+                for key, default in SIMILARITY_KEYS.items():
+                    checkpoint_dict[key] = type(default)(getattr(self.trainer, key))
         for m in METRICS:
             if getattr(self, m.key):
                 checkpoint_dict[m.key] = [dict(entry) for entry in getattr(self, m.key)]
@@ -182,6 +189,12 @@ class Checkpointer:
             if saved != own:
                 print('{} was trained with spec_loss_lambda={:g}, spec_loss_floor={:g}; the run goes on with spec_loss_lambda={:g}, '
                       'spec_loss_floor={:g}'.format(source, saved[0], saved[1], own[0], own[1]))
+        if filename is None and hasattr(self.trainer, 'sim_loss_on'):
+            saved = tuple(type(d)(checkpoint_dict.get(k, d)) for k, d in SIMILARITY_KEYS.items())
+            own = (self.trainer.sim_loss_on, bool(self.trainer.sim_loss_center))
+            if saved != own:
+                print('{} was trained with sim_loss_on={}, sim_loss_center={}; the run goes on with sim_loss_on={}, '
+                      'sim_loss_center={}'.format(source, saved[0], saved[1], own[0], own[1]))
         # the critic's minibatch standard-deviation group (models.Discriminator_PG(mbstd_group=); a file without the key is 0, off) changes
         # the head's parameters and its equalised-LR constant: the file's weights mean something else under another value
         saved_group = int(checkpoint_dict.get('Discriminator_attrs', {}).get('mbstd_group', 0))
