@@ -35,6 +35,7 @@ _DEFAULTS = dict(
     **{name: default for m in METRICS for name, _, default, _ in settings(m)},
     diffaug='', diffaug_p=1.0, diffaug_seed=0, lsgan=False, mbstd_group=0, grad_pen_mode='gp', grad_pen_interval=1,
     spec_loss_lambda=0.0, spec_loss_floor=1e-3, spec_loss_images=256, spec_loss_seed=0, sim_loss_on='real', sim_loss_center=False,
+    ada_target=0.0, ada_interval=4, ada_kimg=500.0, ada_p_init=0.0,
     # dataset
     dataset_name='science_2022', translation=0.05, image_preprocessing='cpu',
     # architecture
@@ -113,6 +114,22 @@ def validate_configs(create_dirs=False):
         raise ValueError(f"diffaug_seed={g['diffaug_seed']!r} must be an integer >= 0")
     if any(groups) and g['wgan'] and not g['pggan']:
         raise ValueError(f"diffaug={g['diffaug']!r} is not available for the WGAN nets (wgan=True, pggan=False)")
+    # adaptive augmentation probability (an addition of this implementation; Karras et al. 2020): ada_target 0 is off, otherwise the
+    # value r_t = E[sign(D(real) - t)] is held at (0.6 recommended) by moving the probability of the diffaug groups, every
+    # ada_interval-th iteration, at a rate of 0 -> 1 over 1000 ada_kimg real images, from ada_p_init; diffaug_p is then the upper clamp
+    real = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v)      # noqa: E731
+    if not (real(g['ada_target']) and 0 <= g['ada_target'] < 1):
+        raise ValueError(f"ada_target={g['ada_target']!r} must be 0 (off) or lie in (0, 1)")
+    if isinstance(g['ada_interval'], bool) or not (isinstance(g['ada_interval'], int) and g['ada_interval'] >= 1):
+        raise ValueError(f"ada_interval={g['ada_interval']!r} must be an integer >= 1")
+    if not (real(g['ada_kimg']) and g['ada_kimg'] > 0):
+        raise ValueError(f"ada_kimg={g['ada_kimg']!r} must be a finite number > 0")
+    if not (real(g['ada_p_init']) and 0 <= g['ada_p_init'] <= g['diffaug_p']):
+        raise ValueError(f"ada_p_init={g['ada_p_init']!r} must lie in [0, diffaug_p = {g['diffaug_p']!r}]")
+    if g['ada_target'] and not any(groups):
+        raise ValueError(f"ada_target={g['ada_target']!r} adapts the probability of a diffaug policy, and none is named (diffaug='')")
+    if g['ada_target'] and g['wgan'] and not g['pggan']:
+        raise ValueError("ada_target > 0 is not available for the WGAN nets (wgan=True, pggan=False)")
     # the least-squares objective (an addition of this implementation: the reference ships its two losses and never calls them)
     if not isinstance(g['lsgan'], bool):
         raise ValueError(f"lsgan={g['lsgan']!r} must be True or False")

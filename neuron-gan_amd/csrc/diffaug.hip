@@ -17,6 +17,7 @@
 // explicit fmaf, and k_n / r_n are formed in double and rounded once.
 #include <cstdint>
 #include "ngan_common.h"
+#include "../../include/ngada.h"
 
 #pragma clang fp contract(off)
 
@@ -35,10 +36,13 @@ static_assert(sizeof(Row) == 32, "the parameter row is 32 bytes");
 // min(n - 1, floor(u n)) in fp32: u = 1 - 2^-24 times n can round up to n
 __device__ __forceinline__ int draw_int(float u, int n) { return min(n - 1, (int)floorf(u * (float)n)); }
 
+// LIVE: the probability is the device scalar p_live[0] (include/ngada.h), read by every thread; otherwise the argument p_value
+template <bool LIVE>
 __global__ __launch_bounds__(256) void params_kernel(const float* __restrict__ u, Row* __restrict__ rows, int B, int R, int S, int K,
-                                                     int policy, float p) {
+                                                     int policy, float p_value, const float* __restrict__ p_live) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= B) return;
+    const float p = LIVE ? p_live[0] : p_value;
     const float* q = u + (long)n * 8;
     Row r{0.f, 1.f, 0, 0, 0, 0, 0, 0};                                      // every group's identity
     if ((policy & POLICY_COLOR) && q[0] < p) {
@@ -213,9 +217,22 @@ extern "C" int ngan_diffaug_params(const float* uniforms, void* table, int B, in
     NGAN_REQUIRE(policy >= 0 && policy < 8, NGAN_ERR_ARG, "diffaug_params: policy mask %d (bits 1 colour, 2 translation, 4 cutout)", policy);
     NGAN_REQUIRE(p >= 0.f && p <= 1.f, NGAN_ERR_ARG, "diffaug_params: p=%g must lie in [0, 1]", (double)p);
     const int S = (int)(H * 0.125 + 0.5), K = (int)(H * 0.5 + 0.5);
-    hipLaunchKernelGGL(params_kernel, dim3(ngan::ceil_div(B, 256)), dim3(256), 0, (hipStream_t)stream, uniforms,
-                       reinterpret_cast<Row*>(table), B, H, S, K, policy, p);
+    hipLaunchKernelGGL(params_kernel<false>, dim3(ngan::ceil_div(B, 256)), dim3(256), 0, (hipStream_t)stream, uniforms,
+                       reinterpret_cast<Row*>(table), B, H, S, K, policy, p, (const float*)nullptr);
     return ngan::launch_status("ngan_diffaug_params");
+}
+
+// the same mapping with the probability in device memory (include/ngada.h): no range check, the host does not know the value
+extern "C" int ngada_diffaug_params(const float* uniforms, void* table, int B, int H, int W, int table_rows, int policy, const float* p,
+                                    void* stream) {
+    NGAN_REQUIRE(uniforms && table, NGAN_ERR_ARG, "ngada_diffaug_params: null pointer");
+    NGAN_REQUIRE(p, NGAN_ERR_ARG, "ngada_diffaug_params: p is a null pointer");
+    if (int st = check_shape("ngada_diffaug_params", B, 1, H, W, table_rows)) return st;
+    NGAN_REQUIRE(policy >= 0 && policy < 8, NGAN_ERR_ARG, "ngada_diffaug_params: policy mask %d (bits 1 colour, 2 translation, 4 cutout)", policy);
+    const int S = (int)(H * 0.125 + 0.5), K = (int)(H * 0.5 + 0.5);
+    hipLaunchKernelGGL(params_kernel<true>, dim3(ngan::ceil_div(B, 256)), dim3(256), 0, (hipStream_t)stream, uniforms,
+                       reinterpret_cast<Row*>(table), B, H, S, K, policy, 0.f, p);
+    return ngan::launch_status("ngada_diffaug_params");
 }
 
 extern "C" int ngan_diffaug_fwd(const float* x, const void* table, float* y, void* workspace, int B, int C, int H, int W,

@@ -14,6 +14,7 @@
 #include <cstdint>
 #include "ngan_common.h"
 #include "../../include/ngan_geoaug.h"
+#include "../../include/ngada.h"
 
 #pragma clang fp contract(off)
 #include "diffgeo_bits.h"
@@ -23,11 +24,13 @@ namespace {
 constexpr int FWD_TILE = 1024;             // elements per workgroup of the forward pass: 256 threads x 1 float4
 constexpr int BWD_TILE = 256;              // elements per workgroup of the adjoint: one per thread
 
+// LIVE: the probability is the device scalar p_live[0] (include/ngada.h), read by every thread; otherwise the argument p_value
+template <bool LIVE>
 __global__ __launch_bounds__(256) void params_kernel(const float* __restrict__ u, geo::Row* __restrict__ rows, int B, int R, int policy,
-                                                     float p) {
+                                                     float p_value, const float* __restrict__ p_live) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= B) return;
-    rows[n] = geo::geo_params(u + (long)n * 8, R, policy, p);
+    rows[n] = geo::geo_params(u + (long)n * 8, R, policy, LIVE ? p_live[0] : p_value);
 }
 
 __global__ __launch_bounds__(256) void fwd_kernel(const float* __restrict__ x, const geo::Row* __restrict__ rows, float* __restrict__ y,
@@ -84,9 +87,22 @@ extern "C" int ngan_diffgeo_params(const float* uniforms, void* table, int B, in
     NGAN_REQUIRE(aligned16(table), NGAN_ERR_ARG, "diffgeo_params: the table must start on a 16-byte boundary");
     NGAN_REQUIRE(policy >= 0 && policy < 4, NGAN_ERR_ARG, "diffgeo_params: policy mask %d (bits 1 blit, 2 geometry)", policy);
     NGAN_REQUIRE(p >= 0.f && p <= 1.f, NGAN_ERR_ARG, "diffgeo_params: p=%g must lie in [0, 1]", (double)p);
-    hipLaunchKernelGGL(params_kernel, dim3(ngan::ceil_div(B, 256)), dim3(256), 0, (hipStream_t)stream, uniforms,
-                       reinterpret_cast<geo::Row*>(table), B, H, policy, p);
+    hipLaunchKernelGGL(params_kernel<false>, dim3(ngan::ceil_div(B, 256)), dim3(256), 0, (hipStream_t)stream, uniforms,
+                       reinterpret_cast<geo::Row*>(table), B, H, policy, p, (const float*)nullptr);
     return ngan::launch_status("ngan_diffgeo_params");
+}
+
+// the same mapping with the probability in device memory (include/ngada.h): no range check, the host does not know the value
+extern "C" int ngada_diffgeo_params(const float* uniforms, void* table, int B, int H, int W, int table_rows, int policy, const float* p,
+                                    void* stream) {
+    NGAN_REQUIRE(uniforms && table, NGAN_ERR_ARG, "ngada_diffgeo_params: null pointer");
+    NGAN_REQUIRE(p, NGAN_ERR_ARG, "ngada_diffgeo_params: p is a null pointer");
+    if (int st = check_shape("ngada_diffgeo_params", B, 1, H, W, table_rows)) return st;
+    NGAN_REQUIRE(aligned16(table), NGAN_ERR_ARG, "ngada_diffgeo_params: the table must start on a 16-byte boundary");
+    NGAN_REQUIRE(policy >= 0 && policy < 4, NGAN_ERR_ARG, "ngada_diffgeo_params: policy mask %d (bits 1 blit, 2 geometry)", policy);
+    hipLaunchKernelGGL(params_kernel<true>, dim3(ngan::ceil_div(B, 256)), dim3(256), 0, (hipStream_t)stream, uniforms,
+                       reinterpret_cast<geo::Row*>(table), B, H, policy, 0.f, p);
+    return ngan::launch_status("ngada_diffgeo_params");
 }
 
 extern "C" int ngan_diffgeo_fwd(const float* x, const void* table, float* y, int B, int C, int H, int W, int table_rows, float fill,

@@ -155,7 +155,9 @@ class D_W_loss(nn.Module):
         self.drift_epsilon = drift_epsilon
         self.check_nan = check_nan
 
-    def forward(self, real_images, z=None, fake_images=None, augment=None):
+    def forward(self, real_images, z=None, fake_images=None, augment=None, score_tap=None):
+        """score_tap(scores, n_real): optional observer of the pass's per-sample scores [real | fake] before the head reduces them (the
+        trainer's adaptive augmentation counts them); it carries no gradient and changes nothing"""
         batch_size, device = real_images.size(0), real_images.device
         if fake_images is None:
             z = _latents(self.generator_net, batch_size, device, z)
@@ -167,6 +169,8 @@ class D_W_loss(nn.Module):
         with ops.first_order_only(), ops.mbstd_segments(2):      # differentiated once (train.py:365): fused PixelNorm-backward epilogues apply
             both = torch.cat([real_images, fake_images], dim=0) if augment is None else augment.critic_batch(real_images, fake_images)
             scores = self.discriminator_net(both)
+        if score_tap is not None:
+            score_tap(scores, batch_size)
         # -mean(real) + mean(fake) + drift * mean(real^2) (loss_functions.py:22, 29, 33, 45) as one launch each way
         D_loss, score_real, score_fake = ops.WLossHead.apply(scores, batch_size, float(self.drift_epsilon) if self.drift_epsilon > 0 else 0.0)
         if self.check_nan:
@@ -214,6 +218,11 @@ def D_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, 
     reference's unused argument.  One critic pass over [real | fake], differentiated once, and one launch for the scalar chain each way,
     as D_W_loss.forward; the drift term does not enter, as in the reference's function.  z= / fake_images= / augment= / check_nan=:
     the keyword extras of the W losses (module docstring)."""
+    return _d_ls_loss(generator_net, discriminator_net, real_images_batch, z, fake_images, augment, check_nan, None)
+
+
+def _d_ls_loss(generator_net, discriminator_net, real_images_batch, z, fake_images, augment, check_nan, score_tap):
+    """D_LS_loss's body; score_tap as D_W_loss.forward's (D_LS_module passes it on)"""
     batch_size, device = real_images_batch.size(0), real_images_batch.device
     if fake_images is None:
         z = _latents(generator_net, batch_size, device, z)
@@ -222,6 +231,8 @@ def D_LS_loss(generator_net, discriminator_net, real_images_batch, Lambda=None, 
     with ops.first_order_only(), ops.mbstd_segments(2):
         both = torch.cat([real_images_batch, fake_images], dim=0) if augment is None else augment.critic_batch(real_images_batch, fake_images)
         scores = discriminator_net(both)
+    if score_tap is not None:
+        score_tap(scores, batch_size)
     D_loss, Score_real_avg, Score_fake_avg = ops.LSLossHead.apply(scores, batch_size, LS_TARGET_REAL, LS_TARGET_FAKE)
     if check_nan:
         if torch.isnan(Score_real_avg):
@@ -271,9 +282,8 @@ class D_LS_module(nn.Module):
         super().__init__()
         self.generator_net, self.discriminator_net, self.check_nan = generator_net, discriminator_net, check_nan
 
-    def forward(self, real_images, z=None, fake_images=None, augment=None):
-        return D_LS_loss(self.generator_net, self.discriminator_net, real_images, z=z, fake_images=fake_images, augment=augment,
-                         check_nan=self.check_nan)
+    def forward(self, real_images, z=None, fake_images=None, augment=None, score_tap=None):
+        return _d_ls_loss(self.generator_net, self.discriminator_net, real_images, z, fake_images, augment, self.check_nan, score_tap)
 
 
 class G_LS_module(nn.Module):

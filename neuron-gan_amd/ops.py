@@ -1980,3 +1980,67 @@ class SimilarityLoss(Function):
         addend = None if g_images is None else _c(g_images)
         _C.call("nganx_pair_mix", x, mix, shift, _c(g_loss), addend, grad, b, n)
         return grad, None, None, None
+
+
+# ---- adaptive discriminator augmentation (include/ngada.h; csrc/ada.hip) -------------------------------------------------------------
+ADA_MODE_THRESHOLD, ADA_MODE_MIDPOINT = 0, 1     # ngada_accumulate's mode: the threshold argument / the midpoint of the two batch means
+ADA_MAX_SCORES = 65536                            # scores per side of one call
+
+
+def ada_state(device, p_init=0.0):
+    """(counters, p) of a fresh controller: int64[4] = {pos, neg, n, updates} zeros and fp32[2] = {p_init, 0}; allocate once, captured
+    graphs hold the addresses"""
+    counters = torch.zeros(4, device=device, dtype=torch.int64)
+    p = torch.tensor([float(p_init), 0.0], device=device, dtype=torch.float32)
+    return counters, p
+
+
+def _ada_check(counters, p=None):
+    if counters.dtype != torch.int64 or counters.numel() != 4:
+        raise ValueError(f"ada: counters must be int64[4] = {{pos, neg, n, updates}}, got {counters.dtype} {tuple(counters.shape)}")
+    if p is not None and (p.dtype != torch.float32 or p.numel() != 2):
+        raise ValueError(f"ada: p must be fp32[2] = {{p, last_r}}, got {p.dtype} {tuple(p.shape)}")
+
+
+def _ada_scores(t, name):
+    if t.dtype != torch.float32:
+        raise NotImplementedError(f"ada_accumulate: the kernel reads fp32 scores, {name} is {t.dtype}")
+    return _c(t.detach())
+
+
+def ada_accumulate(real_scores, fake_scores, counters, mode=ADA_MODE_THRESHOLD, threshold=0.0):
+    """counters += (real scores above t, below t, seen) on the device (ngada_accumulate, one launch of one workgroup).  mode 0: t =
+    threshold and fake_scores may be None; mode 1: t is the midpoint of the two batch means."""
+    _ada_check(counters)
+    real = _ada_scores(real_scores, "real_scores")
+    fake = None if fake_scores is None else _ada_scores(fake_scores, "fake_scores")
+    _C.call("ngada_accumulate", real, fake, real.numel(), 0 if fake is None else fake.numel(), int(mode), float(threshold), counters)
+    return counters
+
+
+def ada_update(counters, p, target, span, p_max=1.0):
+    """one step of the controller on the device (ngada_update, one thread): p[0] moves by n / span towards the value that holds
+    r = (pos - neg) / n at `target`, clamped to [0, p_max]; p[1] = r; the counts are reset and `updates` advances"""
+    _ada_check(counters, p)
+    _C.call("ngada_update", counters, p, float(target), float(span), float(p_max))
+    return p
+
+
+def _live_p(p):
+    if not (isinstance(p, torch.Tensor) and p.dtype == torch.float32 and p.numel() >= 1):
+        raise ValueError("the live parameter mappings read p from an fp32 device tensor (its first element)")
+    return p
+
+
+def diffaug_params_live(uniforms, table, image_size, policy_mask, p):
+    """diffaug_params with the probability read from the device tensor p (its first element; ngada_diffaug_params)"""
+    _C.call("ngada_diffaug_params", _c(uniforms), table, uniforms.shape[0], int(image_size), int(image_size), table.shape[0],
+            int(policy_mask) & 7, _live_p(p))
+    return table
+
+
+def diffgeo_params_live(uniforms, table, image_size, policy_mask, p):
+    """diffgeo_params with the probability read from the device tensor p (its first element; ngada_diffgeo_params)"""
+    _C.call("ngada_diffgeo_params", _c(uniforms), table, uniforms.shape[0], int(image_size), int(image_size), table.shape[0],
+            (int(policy_mask) >> 3) & 3, _live_p(p))
+    return table

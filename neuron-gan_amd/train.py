@@ -420,14 +420,74 @@ def grad_pen_due(iteration, interval):
 DIFFAUG_ROWS = 16384  # rows of a trainer's parameter tables (512 KB, and as much again for the uniforms): n_critic x 3 b + b of them serve an iteration
 
 
-def _check_diffaug(policy, p, seed):
-    """(policy mask, p, seed) of the trainer arguments; mask 0 is off -- also for p = 0, which closes every gate"""
+def _check_diffaug(policy, p, seed, adaptive=False):
+    """(policy mask, p, seed) of the trainer arguments; mask 0 is off -- also for p = 0, which closes every gate, unless the probability
+    is `adaptive` (ada_target > 0): p is then the upper clamp of a value that lives on the device, and the policy stays on"""
     mask = ops.diffaug_policy_mask(policy)
     if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) <= 1.0:
         raise ValueError(f"diffaug_p must lie in [0, 1], got {p!r}")
     if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
         raise ValueError(f"diffaug_seed must be an integer >= 0, got {seed!r}")
-    return (mask if float(p) > 0.0 else 0), float(p), int(seed)
+    return (mask if float(p) > 0.0 or adaptive else 0), float(p), int(seed)
+
+
+ADA_DEFAULTS = {"ada_target": 0.0, "ada_interval": 4, "ada_kimg": 500.0, "ada_p_init": 0.0}     # PGGANTrainer(ada_*=); target 0: off
+
+
+def check_ada(target, interval, kimg, p_init, diffaug="", diffaug_p=1.0):
+    """(ada_target, ada_interval, ada_kimg, ada_p_init) of the trainer arguments: a target in [0, 1) (0: off), an integer interval
+    >= 1, a finite ada_kimg > 0 and a start value in [0, diffaug_p]; a target > 0 needs a diffaug policy to act on"""
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)      # noqa: E731
+    if not num(target) or not 0.0 <= target < 1.0:
+        raise ValueError(f"ada_target must be 0 (off) or lie in (0, 1), got {target!r}")
+    if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+        raise ValueError(f"ada_interval must be an integer >= 1, got {interval!r}")
+    if not num(kimg) or kimg <= 0:
+        raise ValueError(f"ada_kimg must be a finite number > 0, got {kimg!r}")
+    p_max = float(diffaug_p) if num(diffaug_p) else 1.0       # (diffaug_p has its own check)
+    if not num(p_init) or not 0.0 <= p_init <= p_max:
+        raise ValueError(f"ada_p_init must lie in [0, diffaug_p = {p_max:g}], got {p_init!r}")
+    if target > 0 and not ops.diffaug_policy_mask(diffaug):
+        raise ValueError(f"ada_target={target:g} adapts the probability of a diffaug policy, and none is named (diffaug={diffaug!r})")
+    return float(target), int(interval), float(kimg), float(p_init)
+
+
+class _AdaController:
+    """A trainer's adaptive augmentation probability (`ada_target > 0`; Karras et al. 2020, section 3): the device
+    state -- counters int64[4] = {pos, neg, n, updates}, p fp32[2] = {p, last_r}; allocated once, captured graphs hold the addresses
+    -- the settings, and the host count of iterations.  `accumulate` is what the critic step issues on its scores (captured with the
+    step); `after_iteration` is the eager tail of an iteration: every `interval`-th, the counts are summed over the ranks and one
+    thread moves p by n / (1000 kimg) towards the value that holds r at the target.  Nothing here reads the device."""
+
+    def __init__(self, target, interval, kimg, p_init, p_max, objective, device):
+        self.target, self.interval, self.kimg, self.p_max = target, interval, kimg, p_max
+        self.counters, self.p = ops.ada_state(device, p_init)
+        # the Wasserstein critic's zero is not calibrated (the drift term only bounds it): the midpoint of the two batch means is the
+        # threshold; the least-squares critic has targets 1 and 0, so 0.5 is
+        self.mode, self.threshold = (ops.ADA_MODE_MIDPOINT, 0.0) if objective == "wasserstein" else (ops.ADA_MODE_THRESHOLD, 0.5)
+        self.iteration = 0
+
+    @property
+    def span(self):
+        return 1000.0 * self.kimg
+
+    def accumulate(self, scores, n_real):
+        s = scores.detach().reshape(-1)
+        ops.ada_accumulate(s[:n_real], s[n_real:] if self.mode == ops.ADA_MODE_MIDPOINT else None, self.counters, self.mode, self.threshold)
+
+    def state(self):
+        return {"ada_target": self.target, "ada_interval": self.interval, "ada_kimg": self.kimg, "ada_iteration": self.iteration,
+                "ada_counters": self.counters.detach().cpu().clone(), "ada_p": self.p.detach().cpu().clone()}
+
+    def load_state(self, state):
+        """the count, the counters and p of a checkpoint (`state()`); p is clamped to this run's p_max; the settings stay this run's"""
+        self.iteration = int(state.get("ada_iteration", 0))
+        if "ada_counters" in state:
+            self.counters.copy_(torch.as_tensor(state["ada_counters"], dtype=torch.int64).reshape(4))
+        if "ada_p" in state:
+            p = torch.as_tensor(state["ada_p"], dtype=torch.float32).reshape(2).clone()
+            p[0] = min(max(float(p[0]), 0.0), self.p_max) if math.isfinite(float(p[0])) else 0.0
+            self.p.copy_(p)
 
 
 def diffaug_stream_seed(seed, epoch, rank):
@@ -468,8 +528,9 @@ class _DiffAugTables:
     same private stream, and each draw is made only when one of its groups is named -- a policy without the new groups consumes
     the stream as it always did.  `table` is None without one of the older groups: their launches are then not issued."""
 
-    def __init__(self, mask, p, seed, device, rank):
+    def __init__(self, mask, p, seed, device, rank, live_p=None):
         self.mask, self.p, self.seed, self.rank = mask, p, seed, rank
+        self.live_p = live_p        # adaptive (ada_target > 0): the device scalar the gates compare against; p is then its upper clamp
         self.colour = bool(mask & ops.DIFFAUG_GROUPS["color"])
         self.table = self.uniforms = self.geo_table = self.geo_uniforms = None
         if mask & 7:
@@ -497,10 +558,16 @@ class _DiffAugTables:
         if tables is None:
             if self.table is not None:
                 torch.rand((n, 8), generator=self.generator, out=self.uniforms[:n])
-                ops.diffaug_params(self.uniforms[:n], self.table, image_size, self.mask, self.p)
+                if self.live_p is None:
+                    ops.diffaug_params(self.uniforms[:n], self.table, image_size, self.mask, self.p)
+                else:
+                    ops.diffaug_params_live(self.uniforms[:n], self.table, image_size, self.mask, self.live_p)
             if self.geo_table is not None:
                 torch.rand((n, 8), generator=self.generator, out=self.geo_uniforms[:n])
-                ops.diffgeo_params(self.geo_uniforms[:n], self.geo_table, image_size, self.mask, self.p)
+                if self.live_p is None:
+                    ops.diffgeo_params(self.geo_uniforms[:n], self.geo_table, image_size, self.mask, self.p)
+                else:
+                    ops.diffgeo_params_live(self.geo_uniforms[:n], self.geo_table, image_size, self.mask, self.live_p)
             return
         for prefix, table in (("", self.table), ("geo_", self.geo_table)):
             if table is None:
@@ -862,7 +929,7 @@ class PGGANTrainer(_Trainer):
                  n_critic=1, alpha_step=1e-4, process_group=None, device_latents=False, fused_stem=None, optimizer="adam",
                  rmsprop_alpha=0.99, rmsprop_eps=1e-8, ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, objective="wasserstein",
                  grad_pen_mode="gp", grad_pen_interval=1, spec_loss_lambda=0.0, spec_loss_floor=1e-3, sim_loss_on="real",
-                 sim_loss_center=False):
+                 sim_loss_center=False, ada_target=0.0, ada_interval=4, ada_kimg=500.0, ada_p_init=0.0):
         """optimizer: "adam" -- optim.Adam(params, lr, betas=(beta1, 0.999)), the reference's default -- or "rmsprop" --
         optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps), what the reference's RMSprop switch selects (train.py:220-225);
         beta1 only matters for Adam
@@ -907,15 +974,25 @@ class PGGANTrainer(_Trainer):
         mean.  Data parallel: a rank's term is the mean over the pairs INSIDE its own share, lambda / (n_r (n_r - 1)), and the share
         weight applies on top -- a departure from "all pairs of the global batch": every pair is an independent draw, so each rank's
         mean estimates the same expectation; nothing is gathered and the statistics stay local to a rank, as for the minibatch
-        standard deviation.  A share of 1 has no pair and contributes 0."""
+        standard deviation.  A share of 1 has no pair and contributes 0.
+        ada_target: 0 -- off (no buffer, no launch: the code path of a build without the feature); in (0, 1) -- adaptive discriminator
+        augmentation (Karras et al. 2020, section 3): the probability of the diffaug policy's groups lives on
+        the device, starts at ada_p_init, and every ada_interval-th iteration moves by (real images seen since) / (1000 ada_kimg)
+        towards the value that holds r = E[sign(D(real) - t)] at the target; diffaug_p becomes its upper clamp.  t is the midpoint of
+        the batch's two score means under the Wasserstein objective (its zero is not calibrated) and 0.5 under the least-squares one.
+        Every critic step counts (the monitoring-only pass at n_critic = 0 too), inside the captured graphs; the update is eager, after
+        the iteration, and reads nothing back.  `ada_iteration` counts iterations like `grad_pen_iteration`; capture() leaves it,
+        the counters and p as it found them.  Data parallel: the counts are summed over the ranks before the update, so every rank
+        holds the same p bit for bit; each rank's midpoint is that of its own share.  0.6, 4 and 500 are Karras et al.'s values."""
         sim_loss_on, sim_loss_center = check_sim_loss(sim_loss_on, sim_loss_center)
+        ada_target, ada_interval, ada_kimg, ada_p_init = check_ada(ada_target, ada_interval, ada_kimg, ada_p_init, diffaug, diffaug_p)
         if objective not in OBJECTIVES:
             raise ValueError(f"objective must be one of {list(OBJECTIVES)}, got {objective!r}")
         grad_pen_mode, grad_pen_interval = check_grad_pen(grad_pen_mode, grad_pen_interval)
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, got {optimizer!r}")
         ema_beta = _check_ema_beta(ema_beta)
-        aug_mask, aug_p, aug_seed = _check_diffaug(diffaug, diffaug_p, diffaug_seed)
+        aug_mask, aug_p, aug_seed = _check_diffaug(diffaug, diffaug_p, diffaug_seed, adaptive=ada_target > 0)
         spec_loss_lambda, spec_loss_floor = check_spec_loss(spec_loss_lambda, spec_loss_floor)
         if getattr(discriminator, 'mbstd_group', 0) > 0 and ops.get_conv_precision() == "bf16":
             raise NotImplementedError('a critic with mbstd_group > 0 is built for fp32 activation storage (conv precisions "f32" and '
@@ -938,7 +1015,7 @@ class PGGANTrainer(_Trainer):
             self.d_loss = D_W_loss(generator, discriminator, drift_epsilon=drift_epsilon, check_nan=False)
             self.g_loss = G_W_loss(generator, discriminator, check_nan=False)
         self.grad_pen_mode, self.grad_pen_interval = grad_pen_mode, grad_pen_interval
-        self._phase_held = False        # capture(): its warm-up iterations and the capture itself leave the count where it was
+        self._iteration_counts_held = False        # capture(): its warm-up iterations and the capture itself leave the count where it was
         self.grad_pen_iteration = 0     # host count of training iterations, the same on every rank: due when a multiple of the interval
         if grad_pen_mode == "gp" and grad_pen_interval == 1:
             self.gp_loss = D_grad_pen_loss(generator, discriminator, Lambda=grad_pen_lambda)
@@ -956,9 +1033,12 @@ class PGGANTrainer(_Trainer):
         self.force_exchange = False
         self._aug = None
         self._aug_step = 0         # which critic step of the iteration d_compute serves (train_iteration counts)
+        if ada_target > 0:         # (0: the class attributes below stand; the instance gains nothing)
+            self._ada = _AdaController(ada_target, ada_interval, ada_kimg, ada_p_init, aug_p, objective, self.device)
         if aug_mask:
             rank = dist.get_rank(process_group) if self.world > 1 else 0     # every rank draws a stream of its own
-            self._aug = _DiffAugTables(aug_mask, aug_p, aug_seed, self.device, rank)
+            self._aug = _DiffAugTables(aug_mask, aug_p, aug_seed, self.device, rank,
+                                       live_p=self._ada.p if self._ada is not None else None)
         self.spec_loss_lambda, self.spec_loss_floor = spec_loss_lambda, spec_loss_floor
         self._spec_targets = {} if spec_loss_lambda > 0 else None      # image size -> the static fp64 target buffer of that stage
         self.spectral_note = None                                       # what a stage below 16 x 16 said (once per size)
@@ -967,6 +1047,56 @@ class PGGANTrainer(_Trainer):
             self._sim_lambda = torch.zeros((), device=self.device, dtype=torch.float32)
         self.refresh_stage()
         ops.bump_weight_epoch()
+
+    # ---- adaptive augmentation probability -------------------------------------------------------------------------
+    _ada = None                                                             # what a trainer built with ada_target = 0 reads
+
+    @property
+    def ada_enabled(self):
+        return self._ada is not None
+
+    @property
+    def ada_target(self):
+        return self._ada.target if self._ada is not None else 0.0
+
+    @property
+    def ada_iteration(self):
+        """host count of training iterations, the same on every rank: an update is due when it reaches a multiple of ada_interval"""
+        return self._ada.iteration if self._ada is not None else 0
+
+    def ada_state(self):
+        """the checkpoint keys of the controller (utils.ADA_KEYS): settings, the iteration count, the four counters and {p, last_r}"""
+        if self._ada is None:
+            raise ValueError("ada_state on a trainer with ada_target = 0: there is no controller")
+        return self._ada.state()
+
+    def load_ada_state(self, state):
+        if self._ada is None:
+            raise ValueError("load_ada_state on a trainer with ada_target = 0: there is no controller")
+        self._ada.load_state(state)
+
+    def ada_monitors(self):
+        """the device tensor {p, last_r}: the epoch driver copies it out with the epoch's other monitors"""
+        return self._ada.p
+
+    def _ada_after_iteration(self):
+        """The eager tail of an iteration (train_iteration, replay): advance the count and, when it reaches a multiple of the interval,
+        sum {pos, neg, n} over the ranks on the communication stream and launch the update.  Held during capture() like the penalty
+        phase: its warm-up iterations and the capture itself neither count nor update.  No host read."""
+        ada = self._ada
+        if ada is None or self._iteration_counts_held or (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            return
+        ada.iteration += 1
+        if ada.iteration % ada.interval:
+            return
+        if self.world > 1:
+            self._on_comm_stream(lambda: dist.all_reduce(ada.counters[:3], op=dist.ReduceOp.SUM, group=self.group), "ada")
+        ops.ada_update(ada.counters, ada.p, ada.target, ada.span, ada.p_max)
+
+    def _training_state(self):
+        """with the controller: its counters and p too, so that capture()'s warm-up iterations leave them as they were"""
+        bufs = super()._training_state()
+        return bufs + [self._ada.counters, self._ada.p] if self._ada is not None else bufs
 
     # ---- similarity loss on the generated images ------------------------------------------------------------------
     sim_loss_on, sim_loss_center, _sim_lambda = "real", False, None        # what a trainer built with sim_loss_on="real" reads
@@ -1077,16 +1207,19 @@ class PGGANTrainer(_Trainer):
         return key
 
     def _advance_penalty_phase(self):
-        if not self._phase_held:
+        if not self._iteration_counts_held:
             self.grad_pen_iteration += 1
 
     @contextlib.contextmanager
-    def _penalty_phase_held(self):
-        held, self._phase_held = self._phase_held, True
+    def _hold_iteration_counts(self):
+        """capture(): inside, neither `grad_pen_iteration` nor `ada_iteration` advances and no controller update is launched"""
+        held, self._iteration_counts_held = self._iteration_counts_held, True
         try:
             yield
         finally:
-            self._phase_held = held
+            self._iteration_counts_held = held
+
+    _penalty_phase_held = _hold_iteration_counts      # its name from before the controller's count joined the penalty's
 
     def enable_stem_exchange(self, for_exchange=True):
         """Exchange the stem's gradient as gathered factors; the all-reduce then skips its segment of the flat buffer."""
@@ -1171,7 +1304,10 @@ class PGGANTrainer(_Trainer):
                                   colour=self._aug.colour, geo_real=self._aug.geo_real(self._aug_step, b),
                                   geo_fake=cut(self._aug.geo_fake(self._aug_step, b)))
             hook.prepare(real, fakes)
-        loss, s_real, s_fake = self.d_loss(real, fake_images=fakes[:b], augment=hook)  # train.py:358
+        if self._ada is None:
+            loss, s_real, s_fake = self.d_loss(real, fake_images=fakes[:b], augment=hook)  # train.py:358
+        else:       # the per-sample scores of the pass are counted on their way to the loss head: one launch, same stream
+            loss, s_real, s_fake = self.d_loss(real, fake_images=fakes[:b], augment=hook, score_tap=self._ada.accumulate)
         if penalised or not self.gp_loss.Lambda > 0:
             gp = self.gp_loss(real, x_tilde=fakes[b:] if with_gp else None, epsilon=eps, augment=hook if penalised else None)  # train.py:361
         else:
@@ -1287,6 +1423,7 @@ class PGGANTrainer(_Trainer):
             stats.update(self.d_compute(real, z_d, z_gp, eps, global_batch))
         stats.update(self.g_step(real, z_g, global_batch))
         self._advance_penalty_phase()
+        self._ada_after_iteration()
         return stats
 
     def capture(self, real_example, warmup=1, draws=None, global_batch=None, tables=None):
@@ -1320,7 +1457,7 @@ class PGGANTrainer(_Trainer):
         self._set_share(static_real.size(0), global_batch)     # the write stays outside the captures
         n_packed_before = ops.registry_size()
         lr_g, lr_d = self.opt_g.param_groups[0]["lr"], self.opt_d.param_groups[0]["lr"]
-        with self._penalty_phase_held():       # every warm-up iteration runs in the phase that is being captured
+        with self._hold_iteration_counts():       # every warm-up iteration runs in the phase that is being captured
             self._warm_up_on_snapshot(lambda: self.train_iteration(static_real, *d_args, z_g, global_batch, tables), warmup,
                                       (self._aug.generator,) if self._aug is not None else ())
         assert (lr_g, lr_d) == (self.opt_g.param_groups[0]["lr"], self.opt_d.param_groups[0]["lr"])
@@ -1347,7 +1484,7 @@ class PGGANTrainer(_Trainer):
         # watchdog terminates the process); thread_local polices the capturing thread only.  The second rule (an event whose stream
         # is part of the capture) is what _on_comm_stream takes care of.  Both reproduced case by case: tools/capture_event_probe.py.
         mode = "thread_local" if self._comm_stream is not None else "global"
-        with _collector_off(), self._penalty_phase_held():
+        with _collector_off(), self._hold_iteration_counts():
             graphs, stats = self._capture_segments(segmented, mode, static_real, d_args, z_g, global_batch)
         # Two things the captured launches reference besides the static input: (a) the stem's factor tensors (`StemGradExchange.sink`
         # ran during THIS capture; another shape's capture overwrites stem.captured, and the eager `finish()` between replayed
@@ -1404,6 +1541,7 @@ class PGGANTrainer(_Trainer):
             self._exchange(self.flat_g)
             graphs[2].replay()
         self._advance_penalty_phase()
+        self._ada_after_iteration()
         return stats
 
     def _entry_for(self, real, global_batch=None):
@@ -1466,13 +1604,16 @@ class WGANTrainer(_Trainer):
 
     def __init__(self, generator, discriminator, learning_rate=1e-4, beta1=0.5, drift_epsilon=0.001, n_critic=1, clip=0.01,
                  optimizer="adam", rmsprop_alpha=0.99, rmsprop_eps=1e-8, device_latents=False, process_group=None, sync_batchnorm=False,
-                 ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, grad_pen_mode="gp", grad_pen_interval=1):
+                 ema_beta=0.0, diffaug="", diffaug_p=1.0, diffaug_seed=0, grad_pen_mode="gp", grad_pen_interval=1, ada_target=0.0):
         """ema_beta: as PGGANTrainer's -- the averaged generator's parameters; its BatchNorm buffers stay the live ones
         diffaug: must be empty -- differentiable augmentation is built for the PGGAN trainer only
+        ada_target: must be 0 -- there is no augmentation whose probability could adapt
         grad_pen_mode, grad_pen_interval: must be the defaults -- this loop clips weights and has no penalty"""
         if grad_pen_mode != "gp" or isinstance(grad_pen_interval, bool) or grad_pen_interval != 1:
             raise ValueError(f"grad_pen_mode={grad_pen_mode!r}, grad_pen_interval={grad_pen_interval!r}: the WGAN nets are trained with "
                              f"weight clipping, without a gradient penalty (PGGANTrainer only)")
+        if ada_target != 0:
+            raise ValueError(f"ada_target={ada_target!r}: adaptive augmentation is not available for the WGAN nets (PGGANTrainer only)")
         if ops.diffaug_policy_mask(diffaug):
             raise ValueError(f"diffaug={diffaug!r}: differentiable augmentation is not available for the WGAN nets (PGGANTrainer only)")
         if optimizer not in OPTIMIZERS:
@@ -1847,7 +1988,9 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     cfg.sim_loss_lambda_decay_rate and cut to 0 below 1e-5 as train.py:343-348 does -- goes to `set_sim_lambda` at every epoch start;
     the graphs read it from the device.  In an epoch whose weight is 0 the tap stays in the graph and contributes exact zeros: nothing
     is re-captured.  `_monitored_g_loss` is not used: the monitored G_loss is G_loss + G_sim_loss, as the reference sums them, and
-    G_sim_loss is one more monitor, printed in the status line when it is not zero, as the reference prints it."""
+    G_sim_loss is one more monitor, printed in the status line when it is not zero, as the reference prints it.
+    A trainer with ada_target > 0: its device pair {p, last_r} rides with the epoch's monitors through the same pinned copy -- no read
+    of its own -- and is printed as ada_p / ada_rt in the status line; (epoch, p, r_t) per monitored epoch is kept in checkpoint.ADA."""
     import time
     from .utils import Calculate_D_steps, plot_gen_samples
     adapt_period = 100                                                # Disc_adapt_update_period, train.py:190
@@ -1868,6 +2011,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
     sim_generated = bool(getattr(trainer, "similarity_enabled", False))
     if sim_generated:
         names.append("G_sim_loss")
+    adaptive = bool(getattr(trainer, "ada_enabled", False))
     target_size = [None]              # the image size the trainer's spectral target was last computed for
 
     def refresh_spectral_target():
@@ -1884,7 +2028,7 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
         log("spectral target at {}x{}: mean radial spectrum of {} images, weight {:g}, floor {:g}".format(
             size, size, int(getattr(cfg, 'spec_loss_images', 256)), trainer.spec_loss_lambda, trainer.spec_loss_floor))
     on_gpu = dev.type == "cuda"       # (a CPU device: the stub trainers of the host tests; monitors are then read synchronously)
-    pinned = torch.zeros(2, len(names), pin_memory=on_gpu)
+    pinned = torch.zeros(2, len(names) + (2 if adaptive else 0), pin_memory=on_gpu)   # (adaptive: p and r_t behind the monitors)
     events = [None, None]
     statics = {}                      # graph key -> the static draw tensors its graphs read
     pending = [None, None]
@@ -1906,6 +2050,10 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
         ep = pending[slot]
         vals = pinned[slot].tolist()
         events[slot] = None
+        if adaptive:
+            vals, (ada_p, ada_rt) = vals[:len(names)], vals[len(names):]
+            if checkpoint is not None:
+                checkpoint.ADA.append((ep, ada_p, ada_rt))
         if any(math.isnan(v) for v in vals):
             raise ValueError(f"NaN loss at epoch {ep}: " + ", ".join(f"{n}={v}" for n, v in zip(names, vals)))
         for n, v in zip(names, vals):
@@ -1920,7 +2068,8 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
                     ep, "{:.3f}".format((time.time() - start_time) / done) if done > 0 else "----",
                     trainer.opt_g.param_groups[0]["lr"], G.alpha_value(), G.image_size, G.image_size, vals[0], vals[1], vals[3],
                     vals[2], vals[4]) + (", G_spec_loss:{: >#7.4g}".format(vals[5]) if spectral else "")
-                + (", G_sim_loss:{: >#7.4g}".format(vals[-1]) if sim_generated and vals[-1] != 0 else ""))
+                + (", G_sim_loss:{: >#7.4g}".format(vals[-1]) if sim_generated and vals[-1] != 0 else "")
+                + (", ada_p:{: >#7.4g}, ada_rt:{: >#7.4g}".format(ada_p, ada_rt) if adaptive else ""))
 
     for epoch in range(epoch_init, epoch_final):
         if trainer.start_epoch(epoch, cfg.transit_sch):
@@ -1955,7 +2104,10 @@ def pggan_train(trainer, dataset, cfg, checkpoint=None, epoch_init=1, epoch_fina
         slot = epoch & 1
         consume(slot)
         ranks.sum_(acc)                                                # N ranks: ONE all-reduce per epoch, of the five (or six) sums
-        pinned[slot].copy_(acc / n_images, non_blocking=True)
+        if adaptive:                                                   # the same on every rank: it is not summed
+            pinned[slot].copy_(torch.cat([acc / n_images, trainer.ada_monitors()]), non_blocking=True)
+        else:
+            pinned[slot].copy_(acc / n_images, non_blocking=True)
         events[slot] = torch.cuda.Event() if on_gpu else True
         if on_gpu:
             events[slot].record()
@@ -2127,6 +2279,14 @@ def build_arg_parser():
                         'generator')
     p.add_argument('--sim_loss_center', action='store_true', help='similarity loss on generated images: cosines of the images less '
                                                                   'their own means (the black background otherwise dominates them)')
+    p.add_argument('--ada_target', type=float, default=0.0, help='adaptive discriminator augmentation (Karras et al. 2020): move the '
+                                                                 'probability of the --diffaug groups so that r_t = E[sign(D(real) - t)] '
+                                                                 'stays at this target; 0.6 is the recommended value, --diffaug_p '
+                                                                 'becomes the upper clamp; 0: off, the probability is fixed')
+    p.add_argument('--ada_interval', type=int, default=4, help='adaptive augmentation: update the probability every K-th iteration')
+    p.add_argument('--ada_kimg', type=float, default=500.0, help='adaptive augmentation: thousands of real images over which the '
+                                                                 'probability may travel from 0 to 1')
+    p.add_argument('--ada_p_init', type=float, default=0.0, help='adaptive augmentation: the probability a fresh run starts from')
     for m in METRICS:                                                    # one group of integer flags per checkpoint metric
         for name, _, default, text in settings(m):
             p.add_argument('--' + name, type=int, default=default, help=text)
@@ -2170,6 +2330,8 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     config.spec_loss_lambda / config.spec_loss_floor: the PG trainer's spectral regularisation of the generator (likewise refused).
     config.sim_loss_on / config.sim_loss_center: "generated" -- the PG trainer takes the similarity loss on the generator's images, its
     weight starting at config.sim_loss_lambda (0 is accepted and inert); likewise refused for the WGAN nets.
+    config.ada_target > 0: the PG trainer adapts the probability of its diffaug policy (ada_interval, ada_kimg, ada_p_init beside it;
+    diffaug_p becomes the upper clamp); likewise refused for the WGAN nets.
     distributed: a launched rank -- the trainer exchanges over `process_group` (None: the default group); the WGAN nets then train
     with synchronised BatchNorm."""
     if config.wgan and config.pggan:
@@ -2180,7 +2342,10 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
     pen = (getattr(config, 'grad_pen_mode', 'gp'), getattr(config, 'grad_pen_interval', 1))
     spec_lambda = getattr(config, 'spec_loss_lambda', 0.0)
     sim_on = getattr(config, 'sim_loss_on', 'real')
+    ada_target = getattr(config, 'ada_target', 0.0)
     if config.wgan:
+        if ada_target:
+            raise ValueError("ada_target > 0 is not available for the WGAN nets (wgan=True, pggan=False)")
         if sim_on != 'real':
             raise ValueError("sim_loss_on='generated' is not available for the WGAN nets (wgan=True, pggan=False)")
         if spec_lambda:
@@ -2208,6 +2373,8 @@ def make_trainer(config, G, D, process_group=None, distributed=False):
         kw["spec_loss_lambda"], kw["spec_loss_floor"] = spec_lambda, getattr(config, 'spec_loss_floor', 1e-3)
     if sim_on != 'real':                # (likewise)
         kw["sim_loss_on"], kw["sim_loss_center"] = sim_on, bool(getattr(config, 'sim_loss_center', False))
+    if ada_target:                      # (likewise)
+        kw.update({k: getattr(config, k, d) for k, d in ADA_DEFAULTS.items()})
     if config.RMSprop:
         trainer = PGGANTrainer(G, D, optimizer="rmsprop", **kw)
     else:

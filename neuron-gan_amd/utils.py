@@ -106,6 +106,12 @@ SPECTRAL_KEYS = {'spec_loss_lambda': 0.0, 'spec_loss_floor': 1e-3}
 # of a PGGANTrainer's similarity term (train.py `sim_loss_on=`, `sim_loss_center=`); the values of a file without the keys.  Resuming
 # under other values is allowed and logged, as for the spectral keys
 SIMILARITY_KEYS = {'sim_loss_on': 'real', 'sim_loss_center': False}
+# of a PGGANTrainer's adaptive augmentation probability (train.py `ada_target=` ...): the settings, the host count of iterations, the
+# device counters {pos, neg, n, updates} and {p, last_r}; a file without the keys was trained with it off.  Written only by a trainer
+# with ada_target > 0.  Resuming under another target, interval or kimg is allowed and logged; p carries over, clamped to the new
+# diffaug_p.  ADA_SERIES_KEY: (epoch, p, r_t) per monitored epoch
+ADA_KEYS = ('ada_target', 'ada_interval', 'ada_kimg', 'ada_iteration', 'ada_counters', 'ada_p')
+ADA_SERIES_KEY = 'ADA'
 SWD_KEY, MSSSIM_KEY, SPECTRUM_KEY, MORPH_KEY, SKELETON_KEY, SHOLL_KEY, BRANCH_KEY = (m.key for m in METRICS)
 
 
@@ -127,6 +133,7 @@ class Checkpointer:
         self.trainer = trainer      # optional PGGANTrainer: adds / restores 'optimizer_state' (and 'Generator_ema_state')
         for m in METRICS:           # self.SWD .. self.BRANCH: one entry per scored checkpoint (train.py, `<prefix>_period`), saved only
             setattr(self, m.key, [])    # when the list holds any
+        self.ADA = []               # (epoch, p, r_t) per monitored epoch of a trainer with ada_target > 0 (train.pggan_train), saved likewise
 
     def save_state(self, epoch):
         self.epoch = epoch
@@ -156,6 +163,10 @@ class Checkpointer:
             if hasattr(self.trainer, 'sim_loss_on'):
                 for key, default in SIMILARITY_KEYS.items():
                     checkpoint_dict[key] = type(default)(getattr(self.trainer, key))
+            if getattr(self.trainer, 'ada_enabled', False):
+                checkpoint_dict.update(self.trainer.ada_state())
+        if self.ADA:
+            checkpoint_dict[ADA_SERIES_KEY] = [tuple(entry) for entry in self.ADA]
         for m in METRICS:
             if getattr(self, m.key):
                 checkpoint_dict[m.key] = [dict(entry) for entry in getattr(self, m.key)]
@@ -210,6 +221,7 @@ class Checkpointer:
             self.Loss_D[:self.epoch] = checkpoint_dict['Loss_D']
             for m in METRICS:           # a resumed run continues the lists
                 setattr(self, m.key, [dict(entry) for entry in checkpoint_dict.get(m.key, [])])
+            self.ADA = [tuple(entry) for entry in checkpoint_dict.get(ADA_SERIES_KEY, [])]
         if 'Generator_attrs' in checkpoint_dict and 'Discriminator_attrs' in checkpoint_dict:
             # (the WGAN nets list no saved_attrs: the reference fails there, utils.py:194-198; here they count as empty)
             gen_attrs = {k: v for k, v in checkpoint_dict['Generator_attrs'].items() if k in getattr(self.Generator_net, 'saved_attrs', [])}
@@ -242,6 +254,20 @@ class Checkpointer:
             if filename is None and hasattr(self.trainer, 'grad_pen_mode'):
                 # a resumed run continues the lazy-regularisation schedule where it stopped (a weights-only load restarts it)
                 self.trainer.grad_pen_iteration = int(checkpoint_dict.get('grad_pen_iteration', PENALTY_KEYS['grad_pen_iteration']))
+            if filename is None and getattr(self.trainer, 'ada_enabled', False):
+                # a resumed run counts, draws and updates where it stopped; a file without the keys was trained with it off
+                if 'ada_target' in checkpoint_dict:
+                    saved = tuple(checkpoint_dict[k] for k in ADA_KEYS[:3])
+                    own = tuple(self.trainer.ada_state()[k] for k in ADA_KEYS[:3])
+                    if saved != own:
+                        print('{} was trained with ada_target={:g}, ada_interval={}, ada_kimg={:g}; the run goes on with ada_target={:g}, '
+                              'ada_interval={}, ada_kimg={:g}'.format(source, *saved, *own))
+                    self.trainer.load_ada_state(checkpoint_dict)
+                else:
+                    print('{} holds no adaptive augmentation state; p starts from ada_p_init'.format(source))
+            elif filename is None and 'ada_target' in checkpoint_dict:
+                print('{} was trained with ada_target={:g}; the run goes on with a fixed augmentation probability'.format(
+                    source, checkpoint_dict['ada_target']))
             if getattr(self.trainer, 'ema_enabled', False):
                 self.trainer.load_ema_state(checkpoint_dict.get(EMA_KEY, {}))
                 if EMA_KEY not in checkpoint_dict:
