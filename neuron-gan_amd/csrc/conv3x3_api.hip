@@ -79,6 +79,7 @@ extern "C" int ngan_conv3x3_fwd_ex(const float* x, const float* packed, const fl
         if (precision == 3) {
             NGAN_REQUIRE((epilogue == EPI_NONE || epilogue == EPI_LRELU_PN) && out_mode == 0, NGAN_ERR_ARG,
                          "conv3x3_fwd: the folded bilinear kernel has epilogues 0 and 1");
+            NGAN_REQUIRE(B < 65536, NGAN_ERR_SHAPE, "conv3x3_fwd: B=%d: the border-ring kernel takes at most 65535 images per call", B);
             const int st = ngan::conv3x3_up2f_launch(a, epilogue, s);
             if (st || (flags & NGAN_CONV_SKIP_BORDER)) return st;      // the caller launches ngan_conv3x3_up2_border itself
             return ngan::conv3x3_up2_border_launch(a, epilogue, s);
@@ -94,8 +95,11 @@ extern "C" int ngan_conv3x3_fwd_ex(const float* x, const float* packed, const fl
     }
     // many channels, small image: the kernel of conv3x3_mid.hip, split-bf16 (precision 2: K = 16 padded to 32) or exact fp32
     // (fp32 with a pooled input stays on the generic kernel, which measured 10 % faster there)
-    if (precision >= 1 || (resample != NGAN_RESAMPLE_POOL2 && ngan::conv3x3_mid_eligible(B, H, W, K, N)))
+    if (precision >= 1 || (resample != NGAN_RESAMPLE_POOL2 && ngan::conv3x3_mid_eligible(B, H, W, K, N))) {
+        // the staging of a plain input goes through a buffer descriptor of the tile's image, its byte offsets formed in `int`
+        NGAN_REQUIRE((long)H * W * K * 4 < (1L << 31), NGAN_ERR_SHAPE, "conv3x3_fwd: one input image must stay below 2 GiB (H=%d W=%d K=%d)", H, W, K);
         return ngan::conv3x3_mid_launch(x, packed, bias, y, rnorm, aux_in, aux_rn, B, H, W, K, N, resample, epilogue, out_mode, slope, eps, precision, s);
+    }
     // generic exact-fp32 kernel: it has epilogues 0 and 1; the PixelNorm backward runs as a second launch, in place
     const int epi = epilogue == EPI_PN_BWD ? EPI_NONE : epilogue;
     const int st = ngan::conv3x3_generic_launch(a, resample, epi, out_mode, s);
@@ -108,6 +112,7 @@ extern "C" int ngan_conv3x3_up2_border(const float* x, const float* packed, cons
     NGAN_REQUIRE(x && packed && y, NGAN_ERR_ARG, "conv3x3_up2_border: null pointer");
     NGAN_REQUIRE(ngan_conv3x3_algorithm(B, H, W, K, N, NGAN_RESAMPLE_UP2, 1) == 3, NGAN_ERR_SHAPE,
                  "conv3x3_up2_border: B=%d H=%d W=%d K=%d N=%d is not a folded-bilinear (precision 3) shape", B, H, W, K, N);
+    NGAN_REQUIRE(B < 65536, NGAN_ERR_SHAPE, "conv3x3_up2_border: B=%d: at most 65535 images per call (one grid row per image)", B);
     NGAN_REQUIRE(epilogue == EPI_NONE || (epilogue == EPI_LRELU_PN && rnorm), NGAN_ERR_ARG, "conv3x3_up2_border: epilogue %d", epilogue);
     ConvArgs a{x, packed, bias, y, rnorm, B, H, W, K, N, 0, 0, slope, eps, nullptr, nullptr, nullptr};
     return ngan::conv3x3_up2_border_launch(a, epilogue, (hipStream_t)stream);

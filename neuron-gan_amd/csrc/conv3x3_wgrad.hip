@@ -944,8 +944,10 @@ static int wgrad_entry(const float* x, const float* g, float* gw, float* workspa
     hipStream_t s = (hipStream_t)stream;
     int st;
     NGAN_REQUIRE(precision == 0 || precision == 1 || precision == 5, NGAN_ERR_ARG, "conv3x3_wgrad: precision %d", precision);
-    NGAN_REQUIRE(precision == 0 || (long)H * W * (Cin > Cout ? Cin : Cout) * 16 < (1L << 32), NGAN_ERR_SHAPE,
-                 "conv3x3_wgrad: one image must stay below 1 GiB (H=%d W=%d): the split-bf16 kernel uses 32-bit byte offsets", H, W);
+    // every kernel behind this entry point -- the exact-fp32 one (wgrad_f32_kernel) as well -- addresses x and g through per-image
+    // buffer descriptors with 32-bit byte offsets formed in `int`
+    NGAN_REQUIRE((long)H * W * (Cin > Cout ? Cin : Cout) * 16 < (1L << 32), NGAN_ERR_SHAPE,
+                 "conv3x3_wgrad: one image must stay below 1 GiB (H=%d W=%d): the kernels use 32-bit byte offsets inside an image", H, W);
     if (p.co_s == 32 && p.ci_s == 32) st = launch_wgrad<2, 2>(a, p, resample, precision, s);
     else if (p.co_s == 32) st = launch_wgrad<2, 1>(a, p, resample, precision, s);
     else if (p.ci_s == 32) st = launch_wgrad<1, 2>(a, p, resample, precision, s);

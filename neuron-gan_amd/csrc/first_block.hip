@@ -262,6 +262,8 @@ struct FbPlan { int gx, R, nchunk; long slabs; };
 
 int fb_plan(const char* who, int B, int H, int W, int C, int N, FbPlan& pl) {
     pl = FbPlan{0, 0, 0, 0};
+    NGAN_REQUIRE(B <= 0 || H <= 0 || (long)B * ngan::ceil_div(H, FB_ROWS) < 65536, NGAN_ERR_SHAPE,
+                 "%s: B=%d H=%d: B * ceil(H / %d) must stay below 65536 (one grid row per %d image rows)", who, B, H, FB_ROWS, FB_ROWS);
     NGAN_REQUIRE(fb_shape_ok(B, H, W, C, N), NGAN_ERR_SHAPE,
                  "%s: B=%d H=%d W=%d C=%d N=%d unsupported (N 16 or 32, C <= 64, < 2^31 output elements)", who, B, H, W, C, N);
     pl.gx = ngan::ceil_div((long)W * (N / 4), 256);

@@ -240,7 +240,8 @@ int check_field(const char* what, int B, int H, int W, int C) {
     NGAN_REQUIRE(B > 0 && B < 65536, NGAN_ERR_SHAPE, "%s: B=%d unsupported (1 .. 65535 samples per call)", what, B);
     NGAN_REQUIRE(H > 0 && W > 0 && C > 0 && C % 4 == 0, NGAN_ERR_SHAPE, "%s: H=%d W=%d C=%d unsupported (C a positive multiple of 4)", what, H, W,
                  C);
-    NGAN_REQUIRE((long)B * H * W * C <= (1L << 40), NGAN_ERR_SHAPE, "%s: B=%d H=%d W=%d C=%d too large", what, B, H, W, C);
+    // stdfield_add runs one thread per four elements: its launch must stay below 2^32 threads (ngan_common.h)
+    NGAN_REQUIRE((long)B * H * W * C < (1L << 34) - 1024, NGAN_ERR_SHAPE, "%s: B=%d H=%d W=%d C=%d too large (2^34 elements)", what, B, H, W, C);
     return NGAN_OK;
 }
 
@@ -306,7 +307,7 @@ int ngan_stdfield_ds(const float* g, const float* w_std, float* gs, int B, int H
     NGAN_REQUIRE(g && w_std && gs, NGAN_ERR_ARG, "stdfield_ds: null pointer");
     NGAN_REQUIRE(aligned16(g), NGAN_ERR_ARG, "stdfield_ds: g must start on a 16-byte boundary");
     if (int st = check_field("stdfield_ds", B, H, W, C)) return st;
-    NGAN_REQUIRE((long)H * W * C < (1L << 29) && C <= 4096, NGAN_ERR_SHAPE, "stdfield_ds: H=%d W=%d C=%d too large (C at most 4096)", H, W, C);
+    NGAN_REQUIRE((long)H * W * C < (1L << 29) && C <= 4096, NGAN_ERR_SHAPE, "stdfield_ds: H=%d W=%d C=%d too large (H*W*C below 2^29, C at most 4096)", H, W, C);
     hipLaunchKernelGGL(k_stdfield_ds, dim3(B), dim3(TPB), 9 * C * sizeof(float) + 4 * sizeof(double), (hipStream_t)stream, g, w_std, gs, H, W, C, scale);
     return ngan::launch_status("stdfield_ds");
 }

@@ -31,6 +31,14 @@ inline int launch_status(const char* what) {
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// One-dimensional launches with one thread (or lane group) per item: the runtime refuses a grid of 2^32 threads or more along x, and
+// ceil_div narrows the block count to int.  A launcher that sizes its grid by the tensor states the item count here first, so that
+// the first shape past the limit is NGAN_ERR_SHAPE with the limit in the message instead of a launch error (DESIGN.md section 2,
+// "Index widths").  `items` is the number of threads the launch needs before it is rounded up to whole 256-thread blocks.
+#define NGAN_REQUIRE_THREADS(what, items)                                                                                      \
+    NGAN_REQUIRE((long)(items) <= (1L << 32) - 256, NGAN_ERR_SHAPE, "%s: %ld threads in one launch: must stay below 2^32", what, \
+                 (long)(items))
+
 // stage-2 of every two-stage reduction: out[i] = scale * sum_j partials[j*M + i]
 int reduce_partials(const float* partials, int nparts, int M, float* out, float scale, hipStream_t s);
 int reduce_partials_acc(const float* partials, int nparts, int M, long stride, float* out, int M1, float* out2, float scale, int accumulate,

@@ -133,6 +133,7 @@ bool lpp_ok(int C) {
 #define PN_LAUNCH(KERNEL, VV, ...)                                                                                \
     do {                                                                                                          \
         const int lpp = C / (4 * VV);                                                                             \
+        NGAN_REQUIRE_THREADS("lrelu_pixelnorm", npix * lpp);                                                      \
         const dim3 grid(ngan::ceil_div(npix * lpp, 256)), block(256);                                              \
         hipStream_t s_ = (hipStream_t)stream;                                                                     \
         switch (lpp) {                                                                                            \

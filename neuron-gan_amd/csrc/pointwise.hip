@@ -918,6 +918,7 @@ static int to_image_fwd_impl(const T* x, const float* w, float* t, long npix, in
         return ngan::wide_to_image_fwd(x, w, t, npix, C, Ncol, (hipStream_t)stream);                                        // wide.hip
     NGAN_REQUIRE(npix > 0 && Ncol >= 1 && Ncol <= 4 && pow2_quads(C), NGAN_ERR_SHAPE, "to_image_fwd: npix=%ld C=%d Ncol=%d unsupported",
                  npix, C, Ncol);
+    NGAN_REQUIRE_THREADS("to_image_fwd", npix * (C / 4));
     hipStream_t s = (hipStream_t)stream;
     const int nblk = ceil_div(npix * (C / 4), 256);
 #define CALL(QV) hipLaunchKernelGGL((to_image_fwd_kernel<T, QV>), dim3(nblk), dim3(256), 0, s, x, w, t, npix, C, Ncol)
@@ -1053,10 +1054,12 @@ extern "C" int ngan_up2_adjoint_pnbwd(const float* g, const float* yprev, const 
                                       float slope, void* stream) {
     NGAN_REQUIRE(g && yprev && rnorm && o, NGAN_ERR_ARG, "ngan_up2_adjoint_pnbwd: null pointer");
     if (B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0 && !pow2_quads(C)) {      // wide layers: the two operators one after the other (wide.hip)
+        NGAN_REQUIRE_THREADS("ngan_up2_adjoint_pnbwd", (long)B * h * w);         // (the second launch's limit, stated before the first)
         const int st = ngan_up2_adjoint(g, o, B, h, w, C, stream);
         return st ? st : ngan::wide_pn_bwd<float>(o, nullptr, nullptr, yprev, rnorm, o, (long)B * h * w, C, slope, (hipStream_t)stream);
     }
-    NGAN_REQUIRE(B > 0 && B < 65536 && h > 0 && w > 0 && pow2_quads(C), NGAN_ERR_SHAPE, "ngan_up2_adjoint_pnbwd: bad dims %d %d %d %d", B, h, w, C);
+    NGAN_REQUIRE(B < 65536, NGAN_ERR_SHAPE, "ngan_up2_adjoint_pnbwd: B=%d: at most 65535 images per call (one grid layer per image)", B);
+    NGAN_REQUIRE(B > 0 && h > 0 && w > 0 && pow2_quads(C), NGAN_ERR_SHAPE, "ngan_up2_adjoint_pnbwd: bad dims %d %d %d %d", B, h, w, C);
     return launch_up2_adjoint_strip<float>(g, yprev, rnorm, o, B, h, w, C, slope, (hipStream_t)stream);
 }
 extern "C" int ngan_bf16_up2_adjoint_pnbwd(const ngan_bf16* g, const ngan_bf16* yprev, const float* rnorm, ngan_bf16* o, int B, int h, int w,
@@ -1064,7 +1067,8 @@ extern "C" int ngan_bf16_up2_adjoint_pnbwd(const ngan_bf16* g, const ngan_bf16* 
     NGAN_REQUIRE(g && yprev && rnorm && o, NGAN_ERR_ARG, "ngan_bf16_up2_adjoint_pnbwd: null pointer");
     if (B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0 && !pow2_quads(C))      // wide layers: one fused pass, fp32 intermediate (wide.hip)
         return ngan::wide_up2_adjoint_pnbwd(BF(g), BF(yprev), rnorm, BFM(o), B, h, w, C, slope, (hipStream_t)stream);
-    NGAN_REQUIRE(B > 0 && B < 65536 && h > 0 && w > 0 && pow2_quads(C), NGAN_ERR_SHAPE, "ngan_bf16_up2_adjoint_pnbwd: bad dims %d %d %d %d", B, h, w, C);
+    NGAN_REQUIRE(B < 65536, NGAN_ERR_SHAPE, "ngan_bf16_up2_adjoint_pnbwd: B=%d: at most 65535 images per call (one grid layer per image)", B);
+    NGAN_REQUIRE(B > 0 && h > 0 && w > 0 && pow2_quads(C), NGAN_ERR_SHAPE, "ngan_bf16_up2_adjoint_pnbwd: bad dims %d %d %d %d", B, h, w, C);
     return launch_up2_adjoint_strip<__bf16>(BF(g), BF(yprev), rnorm, BFM(o), B, h, w, C, slope, (hipStream_t)stream);
 }
 

@@ -694,6 +694,7 @@ int ngan_s2_conv(const float* x, const float* Wp, const float* bias, const float
     NGAN_REQUIRE(up || (Hin % 2 == 0 && Win % 2 == 0), NGAN_ERR_SHAPE, "s2_conv(down): input %dx%d is not even", Hin, Win);
     S2Args a{x, Wp, bias, y, Xform{in_scale, in_shift, in_act, slope}, B, Hin, Win, C, M, round_up(M, 64), round_up(C, 16),
              up ? Hin : Hin / 2, up ? Win : Win / 2, tanh_out};
+    NGAN_REQUIRE_THREADS("s2_conv", 4L * B * a.Hq * a.Wq);        // one wave per 16 output pixels of a parity: 4 threads per pixel
     hipStream_t s = (hipStream_t)stream;
     const int mt = M > 32 ? 4 : (M > 16 ? 2 : 1);
     if (up) return mt == 4 ? launch_s2<1, 4>(a, s) : mt == 2 ? launch_s2<1, 2>(a, s) : launch_s2<1, 1>(a, s);
@@ -765,6 +766,7 @@ int ngan_bn_act_bwd(const float* y, const float* g, const float* scale, const fl
     NGAN_REQUIRE((scale == nullptr) == (shift == nullptr), NGAN_ERR_ARG, "bn_act_bwd: scale and shift go together");
     NGAN_REQUIRE(!gamma || (scale && mean && rstd && work), NGAN_ERR_ARG, "bn_act_bwd: training-mode BatchNorm needs its statistics");
     NGAN_REQUIRE(npix > 0 && C > 0, NGAN_ERR_SHAPE, "bn_act_bwd: npix=%ld C=%d", npix, C);
+    NGAN_REQUIRE_THREADS("bn_act_bwd", npix * C);           // the apply pass: one thread per element
     hipStream_t s = (hipStream_t)stream;
     float* coef = nullptr;
     if (gamma) {
@@ -793,6 +795,7 @@ int ngan_bn_act_apply(const float* y, const float* scale, const float* shift, in
     NGAN_REQUIRE((scale == nullptr) == (shift == nullptr), NGAN_ERR_ARG, "bn_act_apply: scale and shift go together");
     const long n = npix * C;
     NGAN_REQUIRE(n > 0, NGAN_ERR_SHAPE, "bn_act_apply: npix=%ld C=%d", npix, C);
+    NGAN_REQUIRE_THREADS("bn_act_apply", n);
     hipLaunchKernelGGL(bn_act_apply_kernel, dim3(ngan::ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, y, scale, shift, act, slope, n,
                        C, out);
     return ngan::launch_status("ngan_bn_act_apply");
@@ -814,6 +817,7 @@ int ngan_chan_sum(const float* g, long npix, int C, float* out, float* work, voi
 int ngan_tanh_bwd(const float* t, const float* g, float* out, long n, void* stream) {
     NGAN_REQUIRE(t && g && out, NGAN_ERR_ARG, "tanh_bwd: null pointer");
     NGAN_REQUIRE(n > 0, NGAN_ERR_SHAPE, "tanh_bwd: n=%ld", n);
+    NGAN_REQUIRE_THREADS("tanh_bwd", n);
     hipLaunchKernelGGL(tanh_bwd_kernel, dim3(ngan::ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, t, g, out, n);
     return ngan::launch_status("ngan_tanh_bwd");
 }
@@ -879,6 +883,7 @@ int ngan_bn_act_bwd_merged(const float* y, const float* g, const float* scale, c
                  "bn_act_bwd_merged: null pointer");
     NGAN_REQUIRE(world >= 1 && rank >= 0 && rank < world && npix > 0 && C > 0, NGAN_ERR_SHAPE,
                  "bn_act_bwd_merged: world=%d rank=%d npix=%ld C=%d", world, rank, npix, C);
+    NGAN_REQUIRE_THREADS("bn_act_bwd_merged", npix * C);    // the apply pass: one thread per element
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_bwd_merged_finish, dim3(ngan::ceil_div(C, 256)), dim3(256), 0, s, recs, world, rank, C, n_total, gamma, rstd,
                        dgamma, dbeta, work);

@@ -88,12 +88,33 @@ __global__ __launch_bounds__(256) void wide_pn_bwdbwd_kernel(const T* __restrict
     gr_out[pix] = -(float)C * (u - s * t) * inv_r * inv_r;
 }
 
+// A thread's sum over the pixels, in three levels: runs of 1024 pixels, runs of 1024 such runs, and the rest.  One sequential fp32
+// accumulator over n terms is off by ~ 2^-24 sqrt(n) of the terms' magnitude, 1.4e-4 of the result at 4.5e7 pixels (measured:
+// tests/test_gpu_large_offsets.py); in levels the longest run is 1024 terms whatever n is.  Up to 1024 pixels there is one run and
+// the order, and with it every bit, is the single accumulator's.  add(p, acc) returns acc with pixel p's term added.
+constexpr long kSumRun = 1024;
+template <typename F>
+__device__ __forceinline__ float wide_pixel_sum(long npix, F add) {
+    float s2 = 0.f;
+    for (long p2 = 0; p2 < npix; p2 += kSumRun * kSumRun) {
+        const long e2 = p2 + kSumRun * kSumRun < npix ? p2 + kSumRun * kSumRun : npix;
+        float s1 = 0.f;
+        for (long p1 = p2; p1 < e2; p1 += kSumRun) {
+            const long e1 = p1 + kSumRun < e2 ? p1 + kSumRun : e2;
+            float s0 = 0.f;
+            for (long p = p1; p < e1; ++p) s0 = add(p, s0);
+            s1 += s0;
+        }
+        s2 += s1;
+    }
+    return s2;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void wide_channel_sum_kernel(const T* __restrict__ g, float* __restrict__ out, long npix, int C, float scale) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    float s = 0.f;
-    for (long p = 0; p < npix; ++p) s += lda1(g + p * C + c);
+    const float s = wide_pixel_sum(npix, [&](long p, float acc) { return acc + lda1(g + p * C + c); });
     out[c] = s * scale;
 }
 
@@ -146,9 +167,10 @@ __global__ __launch_bounds__(256) void wide_to_image_dw_kernel(const float* __re
     const int i = blockIdx.x * 256 + threadIdx.x;          // (k, c)
     if (i >= Ncol * C) return;
     const int k = i / C, c = i - k * C;
-    float s = 0.f;
-    for (long p = 0; p < npix; ++p) { const float tv = t[p * Ncol + k]; s = fmaf(lda1(x + p * C + c), g[p * Ncol + k] * (1.0f - tv * tv), s); }
-    gw[i] = s;
+    gw[i] = wide_pixel_sum(npix, [&](long p, float acc) {
+        const float tv = t[p * Ncol + k];
+        return fmaf(lda1(x + p * C + c), g[p * Ncol + k] * (1.0f - tv * tv), acc);
+    });
 }
 
 __device__ __forceinline__ float wide_img(const float* __restrict__ x, int b, int yy, int xx, int k, int H, int W, int Ncol, int pool) {
@@ -182,16 +204,17 @@ __global__ __launch_bounds__(256) void wide_from_image_dw_kernel(const float* __
                                                                  float* __restrict__ gb, int B, int H, int W, int Ncol, int C, int pool) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f}, sb = 0.f;
-    for (int b = 0; b < B; ++b)
-        for (int yy = 0; yy < H; ++yy)
-            for (int xx = 0; xx < W; ++xx) {
-                const float gv = lda1(g + (((long)b * H + yy) * W + xx) * C + c);
-                sb += gv;
-                for (int k = 0; k < Ncol; ++k) acc[k] = fmaf(gv, wide_img(x, b, yy, xx, k, H, W, Ncol, pool), acc[k]);
-            }
-    for (int k = 0; k < Ncol; ++k) gw[c * Ncol + k] = acc[k];
-    if (gb) gb[c] = sb;
+    // the pixels in their order (b, yy, xx), each of the Ncol + 1 sums in the levels of wide_pixel_sum
+    const long npix = (long)B * H * W;
+    auto pixel = [&](long p, int& b, int& yy, int& xx) { xx = (int)(p % W); const long r = p / W; yy = (int)(r % H); b = (int)(r / H); };
+    if (gb)
+        gb[c] = wide_pixel_sum(npix, [&](long p, float acc) { return acc + lda1(g + p * C + c); });
+    for (int k = 0; k < Ncol; ++k)
+        gw[c * Ncol + k] = wide_pixel_sum(npix, [&](long p, float acc) {
+            int b, yy, xx;
+            pixel(p, b, yy, xx);
+            return fmaf(lda1(g + p * C + c), wide_img(x, b, yy, xx, k, H, W, Ncol, pool), acc);
+        });
 }
 
 // bilinear x2 adjoint followed by the LeakyReLU -> PixelNorm backward of the layer that produced the low-resolution input (gr = 0),
@@ -248,17 +271,20 @@ namespace ngan {
 // T = float: the fp32 contract, T = __bf16: the bf16-storage entry points)
 template <typename T>
 int wide_pn_fwd(const T* c, const float* bias, T* y, float* rn, long npix, int C, float slope, float eps, hipStream_t s) {
+    NGAN_REQUIRE_THREADS("lrelu_pixelnorm_fwd(wide)", npix);
     hipLaunchKernelGGL(wide_pn_fwd_kernel<T>, dim3(ceil_div(npix, 256)), dim3(256), 0, s, c, bias, y, rn, npix, C, slope, eps);
     return launch_status("ngan_lrelu_pixelnorm_fwd(wide)");
 }
 template <typename T>
 int wide_pn_bwd(const T* gy, const T* gy2, const float* gr, const T* y, const float* rn, T* gc, long npix, int C, float slope, hipStream_t s) {
+    NGAN_REQUIRE_THREADS("lrelu_pixelnorm_bwd(wide)", npix);
     hipLaunchKernelGGL(wide_pn_bwd_kernel<T>, dim3(ceil_div(npix, 256)), dim3(256), 0, s, gy, gy2, gr, y, rn, gc, npix, C, slope);
     return launch_status("ngan_lrelu_pixelnorm_bwd(wide)");
 }
 template <typename T>
 int wide_pn_bwdbwd(const T* h, const T* gy, const T* y, const float* rn, T* ggy, T* gy_out, float* gr_out, long npix, int C, float slope,
                    hipStream_t s) {
+    NGAN_REQUIRE_THREADS("lrelu_pixelnorm_bwdbwd(wide)", npix);
     hipLaunchKernelGGL(wide_pn_bwdbwd_kernel<T>, dim3(ceil_div(npix, 256)), dim3(256), 0, s, h, gy, y, rn, ggy, gy_out, gr_out, npix, C, slope);
     return launch_status("ngan_lrelu_pixelnorm_bwdbwd(wide)");
 }
@@ -269,18 +295,21 @@ int wide_channel_sum(const T* g, float* out, long npix, int C, float scale, hipS
 }
 template <typename T>
 int wide_to_image_fwd(const T* x, const float* w, float* t, long npix, int C, int Ncol, hipStream_t s) {
+    NGAN_REQUIRE_THREADS("to_image_fwd(wide)", npix);
     hipLaunchKernelGGL(wide_to_image_fwd_kernel<T>, dim3(ceil_div(npix, 256)), dim3(256), 0, s, x, w, t, npix, C, Ncol);
     return launch_status("ngan_to_image_fwd(wide)");
 }
 template <typename T>
 int wide_to_image_bwd(const float* g, const float* t, const T* x, const float* w, T* gx, float* gw, long npix, int C, int Ncol, const float* rn,
                       float slope, hipStream_t s) {
+    NGAN_REQUIRE_THREADS("to_image_bwd(wide)", npix);
     hipLaunchKernelGGL(wide_to_image_dw_kernel<T>, dim3(ceil_div((long)Ncol * C, 256)), dim3(256), 0, s, g, t, x, gw, npix, C, Ncol);
     hipLaunchKernelGGL(wide_to_image_dx_kernel<T>, dim3(ceil_div(npix, 256)), dim3(256), 0, s, g, t, x, w, gx, npix, C, Ncol, rn, slope);
     return launch_status("ngan_to_image_bwd(wide)");
 }
 template <typename T>
 int wide_from_image_dx(const T* g, const float* w, float* gx, int B, int H, int W, int Ncol, int C, int pool, hipStream_t s) {
+    NGAN_REQUIRE_THREADS("from_image_dx(wide)", (long)B * H * W);
     hipLaunchKernelGGL(wide_from_image_dx_kernel<T>, dim3(ceil_div((long)B * H * W, 256)), dim3(256), 0, s, g, w, gx, B, H, W, Ncol, C, pool);
     return launch_status("ngan_from_image_dx(wide)");
 }
@@ -291,6 +320,7 @@ int wide_from_image_dw(const float* x, const T* g, float* gw, float* gb, int B, 
 }
 template <typename T>
 int wide_up2_adjoint_pnbwd(const T* g, const T* yprev, const float* rn, T* o, int B, int h, int w, int C, float slope, hipStream_t s) {
+    NGAN_REQUIRE_THREADS("up2_adjoint_pnbwd(wide)", (long)B * h * w);
     hipLaunchKernelGGL(wide_up2_adjoint_pnbwd_kernel<T>, dim3(ceil_div((long)B * h * w, 256)), dim3(256), 0, s, g, yprev, rn, o, B, h, w, C, slope);
     return launch_status("ngan_bf16_up2_adjoint_pnbwd(wide)");
 }

@@ -45,7 +45,10 @@ to a double rounding); an infinite g' makes m' NaN once 1 - b1 >= 0.5, as torch'
 inf - inf) and as `adam_update` does.  `wrong=` names a fault; each misses a bound, a count or a class on a case
 named in the CPU test.
 
-Offsets beyond 2^31 elements are not tested: they would need 8 GB buffers.  The kernels index with `long` throughout."""
+Offsets beyond 2^31 elements are not tested here: the optimiser steps walk the flat parameter buffers (a few hundred MB at the widest
+preset: 2^26 elements), which do not come near a 32-bit boundary in any step, so they are outside the scope of the index-width audit.
+The activation-sized entry points are inside it: tests/large_offset_cases.py holds the table of their index widths and limits, and
+tests/test_gpu_large_offsets.py runs them on tensors beyond 2^31 bytes, 2^32 bytes and 2^31 elements."""
 import zlib
 
 import numpy as np

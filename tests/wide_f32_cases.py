@@ -179,6 +179,8 @@ CHANNEL_SUM_SCALE = 0.5
 
 
 def channel_sum_emulate(g):
+    # (csrc/wide.hip sums the pixels in runs of 1024 -- wide_pixel_sum; up to 1024 pixels, i.e. for every case of PIXELS, that is this
+    # one sequential accumulator, bit for bit.  tests/test_gpu_large_offsets.py runs the reductions at 4.5e7 pixels.)
     s = np.zeros(g.shape[1], f32)
     for p in range(g.shape[0]):
         s = s + g[p]
