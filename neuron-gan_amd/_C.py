@@ -225,6 +225,15 @@ ADA_SIGNATURES = {
     "ngada_diffgeo_params": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
 }
 
+# Arbor skeletons traced into rooted trees (include/ngtree.h, a fourth header that none of the other three includes; prefix ngtree_).
+# Same library, same conventions; tests/test_tree_host_cpu.py holds every row to its prototype.
+TREE_SIGNATURES = {
+    "ngtree_trace": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+}
+TREE_NON_STATUS = {
+    "ngtree_workspace_bytes": ([_I, _I], _Z),
+}
+
 _lib = None
 
 
@@ -236,11 +245,12 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                f"or `make -C neuron-gan_amd/csrc`; there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(ADA_SIGNATURES.items()):
+        for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(ADA_SIGNATURES.items()) + \
+                list(TREE_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
-        for name, (argtypes, restype) in list(NON_STATUS.items()) + list(EXT_NON_STATUS.items()):
+        for name, (argtypes, restype) in list(NON_STATUS.items()) + list(EXT_NON_STATUS.items()) + list(TREE_NON_STATUS.items()):
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype

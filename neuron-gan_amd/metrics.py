@@ -1320,6 +1320,198 @@ def format_branches(result, title="Arbor branches"):
     return _format_arbor(result, title, BRANCH_STATISTICS, width=16, profile=("length", "mean branches per bin, bins {:.4f} image widths wide"))
 
 
+# ---- arbor trees: skeletons rooted at the soma, and SWC files (csrc/tree.hip; include/ngtree.h) ------------------------------------------
+TREE_STATISTICS = ("trees", "cycles", "tips", "forks", "path_max", "path_mean", "contraction", "max_order")
+TREE_STATS = ("pixels", "trees", "orth", "diag", "cycles", "leaves", "tips", "forks", "path_max", "max_order", "main_root", "main_pixels")
+TREE_ORTH = 408                              # the cost of an orth edge (a diag edge costs 577): a path length in pixels is cost / 408
+
+
+def _trace(skeleton, centre, want_order):
+    """arbor_tree's dictionary and the workspace of the call (tools/tree_time.py reads the sweep counts there)"""
+    skeleton = _square_bytes(skeleton, "skeleton")
+    b, r, _ = skeleton.shape
+    if not (MORPH_MIN <= r <= SKEL_MAX and r & (r - 1) == 0):
+        raise ValueError(f"R={r}: a power of two in {MORPH_MIN} .. {SKEL_MAX}")
+    if not (isinstance(centre, torch.Tensor) and centre.dtype == torch.int32 and tuple(centre.shape) == (b, 3)):
+        raise TypeError(f"centre: expected an int32 tensor {(b, 3)}")
+    dev = skeleton.device
+    plane = lambda: torch.empty(b, r, r, device=dev, dtype=torch.int32)   # noqa: E731
+    out = {"cost": plane(), "parent": plane(), "order": plane() if want_order else None,
+           "stats": torch.empty(b, len(TREE_STATS), device=dev, dtype=torch.int32), "sums": torch.empty(b, 2, device=dev, dtype=torch.float64)}
+    ws = torch.empty(max(16, _C.lib().ngtree_workspace_bytes(b, r)), device=dev, dtype=torch.uint8)
+    _C.call("ngtree_trace", skeleton, centre.contiguous(), out["cost"], out["parent"], out["order"], out["stats"], out["sums"], ws, b, r)
+    return out, ws
+
+
+def arbor_tree(skeleton, centre, want_order=True):
+    """{cost, parent, order, stats, sums} of (B, R, R) uint8 skeletons (any mask; non-zero: set), R a power of two in 16 .. 512, and
+    centres (B, 3) int32 {y, x, .} (`distance_transform`'s soma as it is).  The set pixels are the vertices of the graph of
+    `branch_graph`; an orth edge costs 408 and a diag edge 577.  In every component the pixel nearest the centre (the smallest index
+    among equals) is a root, and the component of the nearest root of all is the main tree (include/ngtree.h).
+    cost (B, R, R) int32: -1 on the background, else the cost of the cheapest path from the component's root (pixels: cost / 408).
+    parent (B, R, R) int32: -2 on the background, -1 on a root, else the neighbour on a cheapest path, the smallest index among equals.
+    order (B, R, R) int32 (None with want_order=False; the others are the same bits either way): -1 on the background, 0 on a root,
+    else order[parent] + (parent has two or more children), the centrifugal branch order.
+    stats (B, 12) int32 in the order of TREE_STATS; sums (B, 2) fp64: {the summed cost of the tips, the sum over the tips with a
+    cost of their Euclidean distance from the root over their path length}.  An image whose centre is {-1, -1, .} has no root: the
+    background values everywhere, zeros in stats but main_root = -1, zeros in sums"""
+    return _trace(skeleton, centre, want_order)[0]
+
+
+def tree_statistics(images, otsu_class=1, min_size=1, threshold=None):
+    """Per-image tree statistics of channels-last fp32 images (B, R, R, C) in [-1, 1], R up to 512, fp64 tensors on the device (no host
+    read-back): the kept mask of `arbor_statistics` (same otsu_class, min_size, threshold) is thinned and distance-transformed, and the
+    skeleton is traced outwards from the soma, the centre of the largest inscribed disc:
+        trees         components of the skeleton                      cycles       its cycle rank, edges - pixels + trees: 0 for a forest
+        tips          pixels where a path from a root ends            forks        pixels where one splits
+        path_max      the longest path from a root, in image widths   path_mean    the mean over the tips of their path lengths
+        contraction   the mean over the tips of the Euclidean distance from the root over the path length (1: straight)
+        max_order     the largest centrifugal branch order
+        scored        as in skeleton_statistics: the others are not to be used where it is False
+    The two means divide by max(1, tips); an isolated pixel is a tip with path 0 and contraction 0."""
+    r, ok, stats, kept = _kept_mask(images, otsu_class, min_size, threshold)
+    skeleton, sk = thin(kept)
+    _, soma = distance_transform(kept)
+    t = arbor_tree(skeleton, soma, want_order=False)
+    s = t["stats"].to(torch.float64)
+    tips = s[:, 6].clamp(min=1.0)
+    return {"trees": s[:, 1], "cycles": s[:, 4], "tips": s[:, 6], "forks": s[:, 7], "path_max": s[:, 8] / float(TREE_ORTH) / float(r),
+            "path_mean": t["sums"][:, 0] / tips / float(TREE_ORTH) / float(r), "contraction": t["sums"][:, 1] / tips, "max_order": s[:, 9],
+            "scored": ok & (stats[:, 3] > 0) & (sk[:, 0] > 0)}
+
+
+class Tree(Skeleton):
+    """Collects the per-image tree statistics of real and generated images and compares their distributions, as Skeleton does:
+
+        m = Tree(image_size=64); m.feed('real', x); m.feed('fake', G(z)); m.result()
+
+    It thins, so it is active for the stages the thinning kernel takes, 16 x 16 .. 512 x 512: otherwise feed() does nothing and result()
+    says so."""
+    STATISTICS = TREE_STATISTICS
+
+    def _statistics(self, x):
+        return tree_statistics(x, self.otsu_class, self.min_size)
+
+
+def evaluate_tree(generator, dataset, n_images=8192, batch_size=64, seed=0, otsu_class=1, min_size=1, real_from=None, return_metric=False):
+    """The tree statistics of `generator`'s samples against `dataset`'s images at the generator's current resolution, with the contract
+    of evaluate_skeleton: private generators seeded seed + 1 (augmentation) and seed + 2 (latents), the data set's generator and image
+    size restored afterwards, torch's global and device generators never consumed; real_from: a Tree that an earlier call returned
+    (return_metric=True) with the same settings, whose data side is taken over."""
+    return _evaluate_two_sets(Tree, generator, dataset, n_images, batch_size, seed, otsu_class, min_size, real_from, return_metric)
+
+
+def format_tree(result, title="Arbor trees"):
+    return _format_arbor(result, title, TREE_STATISTICS)
+
+
+def swc_nodes(skeleton, dist2, soma, tree, fragments=True):
+    """The nodes of the SWC file of ONE traced skeleton, as host arrays {id, type, x, y, z, radius, parent} (int64 but x, y, z, radius:
+    fp64): skeleton (R, R), dist2 (R, R) and soma (3) of its mask, tree: arbor_tree's cost and parent of that image, (R, R) each (tensors
+    or arrays).  Node 1 is the soma centre: type 1, radius sqrt(soma dist2), parent -1.  The main tree's root is its child, or node 1
+    itself where the two coincide; every other node is type 3 with x the column, y the row, z 0 and radius sqrt(dist2) in pixels, its
+    parent the node of its parent pixel.  The main tree comes first, ordered by (cost, index), so a parent always precedes its
+    children; the fragments follow in the order of their roots' indices, each ordered likewise, their roots with parent -1
+    (fragments=False: the main tree alone).  No node without a soma ({-1, -1, .}).  Plain host code: this is no hot path, and the
+    pixel-level tree is neither resampled nor smoothed."""
+    import numpy as np
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)   # noqa: E731
+    sk, d2, cost, parent = (host(a) for a in (skeleton, dist2, tree["cost"], tree["parent"]))
+    sy, sx, sd = (int(v) for v in host(soma).reshape(-1)[:3])
+    r = sk.shape[-1]
+    sk, d2, cost, parent = sk.reshape(-1) != 0, d2.reshape(-1), cost.reshape(-1).astype(np.int64), parent.reshape(-1).astype(np.int64)
+    empty = {"id": np.zeros(0, np.int64), "type": np.zeros(0, np.int64), "x": np.zeros(0), "y": np.zeros(0), "z": np.zeros(0),
+             "radius": np.zeros(0), "parent": np.zeros(0, np.int64)}
+    if sy < 0:
+        return empty
+    pixels = np.flatnonzero(sk & (cost >= 0))
+    # every pixel's root: follow the parents; costs fall along them, so pixels taken in ascending cost find their parent's root done
+    pixels = pixels[np.lexsort((pixels, cost[pixels]))]
+    root = np.full(sk.size, -1, np.int64)
+    for p in pixels:
+        root[p] = p if parent[p] < 0 else root[parent[p]]
+    roots = pixels[parent[pixels] < 0]
+    if roots.size:
+        key = (roots // r - sy) ** 2 + (roots % r - sx) ** 2
+        main = int(roots[np.lexsort((roots, key))[0]])
+    else:
+        main = -1
+    soma_is_root = main == sy * r + sx
+    mine = pixels[root[pixels] == main]                                  # (already in (cost, index) order)
+    rest = pixels[root[pixels] != main] if fragments else pixels[:0]
+    rest = rest[np.lexsort((rest, cost[rest], root[rest]))]
+    order = np.concatenate([mine[1:] if soma_is_root else mine, rest])
+    node_of = np.full(sk.size, -1, np.int64)
+    if soma_is_root:
+        node_of[main] = 1
+    node_of[order] = np.arange(2, 2 + order.size)
+    up = np.where(parent[order] >= 0, node_of[np.maximum(parent[order], 0)], np.where(order == main, 1, -1))
+    one = np.ones(1, np.int64)
+    return {"id": np.arange(1, 2 + order.size), "type": np.concatenate([one, np.full(order.size, 3, np.int64)]),
+            "x": np.concatenate([[float(sx)], (order % r).astype(np.float64)]), "y": np.concatenate([[float(sy)], (order // r).astype(np.float64)]),
+            "z": np.zeros(1 + order.size), "radius": np.sqrt(np.concatenate([[float(sd)], d2[order].astype(np.float64)])),
+            "parent": np.concatenate([-one, up])}
+
+
+def write_swc(path, nodes, comments=()):
+    """writes swc_nodes' arrays as an SWC file: `#` comment lines first, then one line per node, `id type x y z radius parent`"""
+    with open(path, "w") as f:
+        for line in comments:
+            f.write("# " + str(line).replace("\n", " ") + "\n")
+        f.write("# id type x y z radius parent\n")
+        for i in range(len(nodes["id"])):
+            f.write("{:d} {:d} {:.1f} {:.1f} {:.1f} {!r} {:d}\n".format(int(nodes["id"][i]), int(nodes["type"][i]), float(nodes["x"][i]),
+                                                                   float(nodes["y"][i]), float(nodes["z"][i]), float(nodes["radius"][i]),
+                                                                   int(nodes["parent"][i])))
+
+
+ARBOR_CSV = ("file",) + TREE_STATISTICS + ("length", "soma", "scored")
+
+
+def export_arbors(images, directory, prefix, otsu_class=1, min_size=1, threshold=None, fragments=True, first=0):
+    """Writes, for image i of `images` ((B, R, R, C) or (B, C, R, R) fp32 in [-1, 1], R up to 512), <prefix>_<first + i>.swc -- its
+    skeleton traced from the soma (swc_nodes; fragments=False: the main tree alone) --, <prefix>_<first + i>.png -- the 8-bit image as
+    the metrics see it --, and one row of <directory>/arbors.csv (appended; the header when the file is new): the file name, the
+    tree statistics, the skeleton's `length` and the soma radius in pixels, and `scored`.  Returns the rows as dictionaries."""
+    import csv
+    import os
+    from PIL import Image
+    x = channels_last(images)
+    levels, _ = morph_levels(x)
+    r, ok, stats, kept = _kept_mask(x, otsu_class, min_size, threshold)
+    skeleton, sk = thin(kept)
+    dist2, soma = distance_transform(kept)
+    tree = arbor_tree(skeleton, soma, want_order=False)
+    st = tree_statistics(x, otsu_class, min_size, threshold)
+    length = (sk[:, 4].to(torch.float64) + math.sqrt(2.0) * sk[:, 5].to(torch.float64)) / float(r)
+    os.makedirs(directory, exist_ok=True)
+    table = os.path.join(directory, "arbors.csv")
+    new = not os.path.exists(table)
+    host = {k: v.cpu() for k, v in dict(tree, skeleton=skeleton, dist2=dist2, soma=soma, levels=levels, length=length, **st).items()
+            if v is not None}
+    rows = []
+    with open(table, "a", newline="") as f:
+        out = csv.writer(f)
+        if new:
+            out.writerow(ARBOR_CSV)
+        for i in range(x.shape[0]):
+            name = f"{prefix}_{first + i:04d}"
+            one = {"cost": host["cost"][i], "parent": host["parent"][i]}
+            nodes = swc_nodes(host["skeleton"][i], host["dist2"][i], host["soma"][i], one, fragments=fragments)
+            s = dict(zip(TREE_STATS, host["stats"][i].tolist()))
+            write_swc(os.path.join(directory, name + ".swc"), nodes, comments=(
+                f"{name}: {r} x {r} pixels, threshold class {otsu_class}, components below {min_size} pixels dropped",
+                "skeleton (Guo-Hall thinning) traced from the soma, the centre of the largest inscribed disc; pixel units, not resampled",
+                f"trees {s['trees']} cycles {s['cycles']} tips {s['tips']} forks {s['forks']} main_pixels {s['main_pixels']}"
+                + ("" if fragments else " (main tree alone)")))
+            Image.fromarray(host["levels"][i].numpy()).save(os.path.join(directory, name + ".png"))
+            row = dict({"file": name}, **{k: float(host[k][i]) for k in TREE_STATISTICS}, length=float(host["length"][i]),
+                       soma=math.sqrt(float(host["soma"][i, 2])), scored=int(bool(host["scored"][i])))
+            out.writerow([row[k] for k in ARBOR_CSV])
+            rows.append(row)
+    return rows
+
+
 def format_table(result, title="SWD x 1e3"):
     if "scales" in result:
         return format_msssim(result) if title == "SWD x 1e3" else format_msssim(result, title)
